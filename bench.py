@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload hod|pk] [--nmesh M] [--no-cpu]
+    python bench.py --gpus N --steps K --warmup W [--workload hod|pk] [--nmesh M] [--dump-outputs DIR] [--full [--no-cpu]]
 
 Metric (BASELINE.json): halos/sec of AbacusHOD population.  Workload at N=1 = BASELINE config 2:
 10^7 synthetic halos + 10^7 subsample particles (seed 600), the LRG HOD of the reference's
 tests/abacus_hod.yaml:31-47, rsd=True.  A step = one full populate of the resident catalog (decide centrals,
 decide satellites, scan, ordered emission); inputs are in HBM before the timed region and the galaxy catalog
 stays in HBM (device-resident rate; the PCIe-inclusive rate is quoted in DESIGN.md).  The second part of the
-metric - wall-clock of the TSC + FFT + binning P(k) - is reported in the "pk" object of the same JSON line
+metric - wall-clock of the TSC + FFT + binning P(k) - is reported in the "pk" object of the `--full` line
 (`--workload pk` makes it the headline instead).
+
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` then writes what the last timed
+step computed (the galaxy catalogue a caller receives, or the binned spectrum) as DIR/<name>.npy.  Everything else - the
+per-kernel table and roofline, the host-synchronised / PCIe-inclusive / reseed variants, the CPU baselines, the other HOD
+mixes and sizes and the P(k) / pairs / catalogue / prepare legs (and at N > 1 the `pk_slab` leg) - runs with `--full`.
 
 N > 1: one process per GPU.  `python bench.py --gpus N` starts the N rank processes itself (abacusutils_amd/launch.py:
 the parent never touches the GPU; fresh children with RANK / LOCAL_RANK / WORLD_SIZE set; a stuck or crashed rank is
@@ -17,7 +22,7 @@ ended by PID and the line is still printed, with an `error` field); under `pytho
 process starts only its own child.  Collectives are RCCL through the C ABI (abacusutils_amd/comm.py) - no torch in any
 of these processes.  Two legs per N: the headline, every rank populating its own 10^7-halo slab catalogue (weak scaling,
 no data-path collective - halos are independent; the reference's unit is the slab chunk,
-abacusnbody/hod/abacus_hod.py:301-312), and `pk_slab`: ONE nmesh^3 TSC + FFT P(k) decomposed over the N GPUs (strong
+abacusnbody/hod/abacus_hod.py:301-312), and with `--full` `pk_slab`: ONE nmesh^3 TSC + FFT P(k) decomposed over the N GPUs (strong
 scaling: ghost exchange, all-to-all pencil transpose, histogram all-reduce).
 """
 import argparse
@@ -32,7 +37,7 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 
 
-from bench_pk import pmc_traffic  # noqa: E402
+from bench_pk import dump_outputs, pmc_traffic  # noqa: E402
 
 
 def parse():
@@ -41,6 +46,10 @@ def parse():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workload', default='hod', choices=['hod', 'pk'])
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (per-kernel table, roofline, CPU baselines, other legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float64)')
     ap.add_argument('--nhalo', type=int, default=10_000_000)
     ap.add_argument('--npart', type=int, default=10_000_000)
     ap.add_argument('--nmesh', type=int, default=2048)
@@ -56,7 +65,10 @@ def parse():
     ap.add_argument('--option', action='append', default=[], metavar='NAME=VALUE',
                     help='diagnostic option of the library (abacus_set_option), e.g. hod_nocls=1: A/B timing of a comparator path')
     ap.add_argument('--leg', default=None, choices=['hod', 'pk_slab'], help='internal: run one leg as a rank process')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def filter_bytes_per_object(tracers, enable_ranks, two_stage=True):
@@ -75,13 +87,15 @@ def filter_bytes_per_object(tracers, enable_ranks, two_stage=True):
     return 12.0 + (8.0 if env else 0.0) + (4.0 if shear else 0.0), 12.0 + (16.0 if enable_ranks else 0.0)
 
 
-def measure_hod(args, dist, nh, npart, tracers, enable_ranks, with_ranks, label, extras=True):
+def measure_hod(args, dist, nh, npart, tracers, enable_ranks, with_ranks, label, extras=True, dump=False):
     """one HOD measurement: stage a synthetic catalogue (seed 600 + rank), populate `steps` times with everything
-    resident in HBM; returns (result dict, inputs for the CPU baseline)"""
+    resident in HBM; returns (result dict, inputs for the CPU baseline).  Without `--full` only the timed steps and the
+    headline fields; `dump`: the last step's catalogue to --dump-outputs"""
     import numpy as np
     from abacusutils_amd import _lib, synth
     from abacusutils_amd.hod import GRAND_HOD as G
 
+    full = args.full
     hd, pd, params = synth.synth_hod_inputs(nh, npart, seed=600 + dist.rank, with_ranks=with_ranks)
     p = G.marshal_params(tracers, params, enable_ranks, True)
     st = G.StagedCatalog(hd, pd)  # H2D once: inputs resident in HBM from here on
@@ -89,57 +103,59 @@ def measure_hod(args, dist, nh, npart, tracers, enable_ranks, with_ranks, label,
     # first populate: builds keys, shadows, records, column ranges (one-off staging work outside the timed region: whole
     # durations -> stage_ms) and sizes the catalog buffers; its launches also carry one-time code-object loads
     _lib.profile_reset()
-    _lib.profile_enable(True)
+    _lib.profile_enable(full)
     st.populate(p)
     _lib.profile_enable(False)
     stage_ms = sum(ms for k, (ms, n) in _lib.profile_get().items()
                    if n and k in ('hod_shadow', 'hod_build_recs', 'hod_refresh_recs', 'hod_build_keys', 'hod_minmax', 'hod_check_pinds'))
     _lib.profile_reset()
-    _lib.profile_enable(True)
+    _lib.profile_enable(full)
     for _ in range(max(args.warmup, 1)):  # steady-state kernel durations
         st.populate(p)
     counts = st.wait_counts()
     ngal = int(np.sum(counts))
     _lib.profile_enable(False)
-    wprof = _lib.profile_get()
-    # one-off work that only happens from the second populate on (the mass-sorted key index of the sparse mixes) is staging too
-    index_names = ('hod_index_keys', 'hod_index_sort', 'hod_index_last')
-    stage_ms += sum(ms for k, (ms, n) in wprof.items() if n and k in index_names)
-    STEP = ('hod_filter', 'hod_deal', 'hod_exact', 'hod_emit')
-    warm = {k: ms / n for k, (ms, n) in wprof.items() if n and k not in index_names}
-    launches = {k: n / max(args.warmup, 1) for k, (ms, n) in wprof.items() if n and k not in index_names}
-    if 'hod_deal' in warm and 'hod_filter' in warm:   # the warm-up's first populate still streamed the keys
-        del warm['hod_filter'], launches['hod_filter']
-        launches['hod_deal'] = 1.0
-    # the kernels of a step lie within a few microseconds of each other at C2 and the warm-up averages carry first launches
-    # (the key index is built during it): the dominant kernel is picked from a few more, steady, untimed populates
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    for _ in range(20):
-        st.populate(p)
-    st.wait_counts()
-    _lib.profile_enable(False)
-    warm.update({k: ms / n for k, (ms, n) in _lib.profile_get().items() if n and k in warm})
-    cand = st.candidates()
+    dom_name = None
+    if full:   # the dominant kernel of a step, for the per-kernel table and the roofline
+        wprof = _lib.profile_get()
+        # one-off work that only happens from the second populate on (the mass-sorted key index of the sparse mixes) is staging too
+        index_names = ('hod_index_keys', 'hod_index_sort', 'hod_index_last')
+        stage_ms += sum(ms for k, (ms, n) in wprof.items() if n and k in index_names)
+        STEP = ('hod_filter', 'hod_deal', 'hod_exact', 'hod_emit')
+        warm = {k: ms / n for k, (ms, n) in wprof.items() if n and k not in index_names}
+        launches = {k: n / max(args.warmup, 1) for k, (ms, n) in wprof.items() if n and k not in index_names}
+        if 'hod_deal' in warm and 'hod_filter' in warm:   # the warm-up's first populate still streamed the keys
+            del warm['hod_filter'], launches['hod_filter']
+            launches['hod_deal'] = 1.0
+        # the kernels of a step lie within a few microseconds of each other at C2 and the warm-up averages carry first launches
+        # (the key index is built during it): the dominant kernel is picked from a few more, steady, untimed populates
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        for _ in range(20):
+            st.populate(p)
+        st.wait_counts()
+        _lib.profile_enable(False)
+        warm.update({k: ms / n for k, (ms, n) in _lib.profile_get().items() if n and k in warm})
+        cand = st.candidates()
 
-    # timed region: HIP events only around the dominant kernel (a pair of event records per launch costs a few
-    # microseconds, which is not negligible against a 0.1-ms step); the other kernels' durations are the warm-up's.
-    # The dominant kernel is the one that takes the LONGEST per step (duration x launches, from the 20 steady populates above);
-    # the pick by bytes among the near-equal kernels of the C2 index path (rounds 3 - 4) is reported beside it as `bytes_pick`
-    bh0, bp0 = filter_bytes_per_object(tracers, enable_ranks)
-    nc0 = float(cand[0] + cand[1])
-    dom_bytes = {'hod_filter': bh0 * nh + bp0 * npart, 'hod_deal': 6.0 * nc0, 'hod_exact': 130.0 * nc0, 'hod_emit': 192.0 * ngal}
-    per_step = {k: warm[k] * launches.get(k, 1.0) for k in warm if k in STEP}
-    tmax = max(per_step.values(), default=0.0)
-    # name-agnostic: the kernel that takes longest per step; kernels within 15 % of the longest are a tie at this clock (the
-    # kernels of the C2 index path lie within two microseconds of each other and trade places from run to run), which goes to
-    # the one that moves the most algorithmic bytes.  Every kernel of the step is reported in `roofline.alternatives`
-    near = [k for k in per_step if per_step[k] >= 0.85 * tmax]
-    dom_name = max(near, key=lambda k: dom_bytes.get(k, 0.0), default=None)
-    bytes_pick = max((k for k in per_step if per_step[k] >= 0.5 * tmax), key=lambda k: dom_bytes.get(k, 0.0), default=None)
+        # timed region: HIP events only around the dominant kernel (a pair of event records per launch costs a few
+        # microseconds, which is not negligible against a 0.1-ms step); the other kernels' durations are the warm-up's.
+        # The dominant kernel is the one that takes the LONGEST per step (duration x launches, from the 20 steady populates above);
+        # the pick by bytes among the near-equal kernels of the C2 index path (rounds 3 - 4) is reported beside it as `bytes_pick`
+        bh0, bp0 = filter_bytes_per_object(tracers, enable_ranks)
+        nc0 = float(cand[0] + cand[1])
+        dom_bytes = {'hod_filter': bh0 * nh + bp0 * npart, 'hod_deal': 6.0 * nc0, 'hod_exact': 130.0 * nc0, 'hod_emit': 192.0 * ngal}
+        per_step = {k: warm[k] * launches.get(k, 1.0) for k in warm if k in STEP}
+        tmax = max(per_step.values(), default=0.0)
+        # name-agnostic: the kernel that takes longest per step; kernels within 15 % of the longest are a tie at this clock (the
+        # kernels of the C2 index path lie within two microseconds of each other and trade places from run to run), which goes to
+        # the one that moves the most algorithmic bytes.  Every kernel of the step is reported in `roofline.alternatives`
+        near = [k for k in per_step if per_step[k] >= 0.85 * tmax]
+        dom_name = max(near, key=lambda k: dom_bytes.get(k, 0.0), default=None)
+        bytes_pick = max((k for k in per_step if per_step[k] >= 0.5 * tmax), key=lambda k: dom_bytes.get(k, 0.0), default=None)
     _lib.profile_reset()
     _lib.profile_select(dom_name)
-    _lib.profile_enable(True)
+    _lib.profile_enable(full)
     dist.barrier()
     _lib.sync()
     t0 = time.perf_counter()
@@ -171,6 +187,17 @@ def measure_hod(args, dist, nh, npart, tracers, enable_ranks, with_ranks, label,
         'config': {'workload': label, 'n_halo': nh, 'n_part': npart, 'n_gal': ngal, 'tracers': list(tracers),
                    'enable_ranks': bool(enable_ranks)},
     }
+    if dump:
+        # what run_hod hands its caller for the last timed step: every tracer's eight columns (ids as float64: exact below 2^53)
+        cols = {}
+        for tr in tracers:
+            cat = st.fetch(tr)
+            cols[f'{tr}_ncent'] = np.array([cat['Ncent']])
+            cols.update({f'{tr}_{c}': cat[c] for c in ('x', 'y', 'z', 'vx', 'vy', 'vz', 'mass', 'id')})
+        dump_outputs(args.dump_outputs, cols)
+    if not full:
+        st.free()
+        return out, (hd, pd, params)
     if extras:
         # MCMC pattern: host needs the counts every step (one sync per step)
         t1 = time.perf_counter()
@@ -271,15 +298,16 @@ def measure_hod(args, dist, nh, npart, tracers, enable_ranks, with_ranks, label,
 
 
 def bench_hod(args, dist):
-    """headline: BASELINE config 2 (LRG, 1e7 + 1e7); at N = 1 also `hod_multi` (BASELINE config 5's HOD: LRG + ELG + QSO
-    with assembly bias, ranks, conformity on the same catalogue) and `hod_large` (4e7 + 4e7: a 1-GB filter stream, four
-    times the 256-MiB Infinity Cache)"""
+    """headline: BASELINE config 2 (LRG, 1e7 + 1e7); with --full at N = 1 also `hod_multi` (BASELINE config 5's HOD: LRG +
+    ELG + QSO with assembly bias, ranks, conformity on the same catalogue) and `hod_large` (4e7 + 4e7: a 1-GB filter stream,
+    four times the 256-MiB Infinity Cache)"""
     from abacusutils_amd import synth
     nh, npart = args.nhalo, args.npart
     out, inputs = measure_hod(args, dist, nh, npart, {'LRG': synth.LRG_PARAMS}, False, False,
                               f'C2: {nh:.0e} synthetic halos + {npart:.0e} subsample particles per GPU (seed 600+rank), '
-                              'LRG HOD of tests/abacus_hod.yaml:31-47, rsd=True, catalog resident in HBM')
-    single = dist.rank == 0 and dist.world == 1
+                              'LRG HOD of tests/abacus_hod.yaml:31-47, rsd=True, catalog resident in HBM',
+                              dump=bool(args.dump_outputs) and dist.rank == 0)
+    single = dist.rank == 0 and dist.world == 1 and args.full
     if single and not args.no_cpu:   # CPU baseline: rank 0 at N = 1 only
         out['cpu_baseline'] = cpu_baseline_hod(*inputs, {'LRG': synth.LRG_PARAMS}, nh)
     del inputs
@@ -452,11 +480,13 @@ def orchestrate(args, under_launcher):
               '--npart', str(args.npart), '--nmesh', str(args.nmesh), '--npk', str(args.npk), '--no-cpu']
     if args.slab_presorted:
         common.append('--slab-presorted')
+    if args.full:
+        common.append('--full')
     for o in args.option:
         common += ['--option', o]
 
-    def leg(name, timeout):
-        res = launch_ranks([sys.executable, os.path.abspath(__file__), '--leg', name] + common, world, ranks=ranks,
+    def leg(name, timeout, extra=()):
+        res = launch_ranks([sys.executable, os.path.abspath(__file__), '--leg', name] + common + list(extra), world, ranks=ranks,
                            timeout=timeout, tag='BENCH-LEG', key=f'{key0}_{name}', env=env)
         ok = all(c == 0 for c in res['returncodes'].values())
         return (res['results'].get(0) if is_root else None), ok, (None if ok else failure_summary(res))
@@ -474,7 +504,7 @@ def orchestrate(args, under_launcher):
                 'warmup': args.warmup, 'ms_per_step': None, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
                 'dtype': 'f64', 'data': 'synthetic', 'config': {'workload': 'C2 per GPU (not measured)'}}
     try:
-        out, ok, err = leg('hod', args.hod_timeout)
+        out, ok, err = leg('hod', args.hod_timeout, ['--dump-outputs', args.dump_outputs] if args.dump_outputs else ())
         if out is None:
             out = dict(fallback)
         if err:
@@ -482,7 +512,7 @@ def orchestrate(args, under_launcher):
         rc = 0 if ok else 1
         if not ok and not is_root:
             time.sleep(3.0)     # under a launcher that ends every rank at the first failure: rank 0 reports first
-        if not args.no_slab and not args.no_pk:
+        if args.full and not args.no_slab and not args.no_pk:
             slab, sok, serr = leg('pk_slab', args.slab_timeout)
             slab = slab or {}
             if serr:
@@ -509,7 +539,7 @@ def single(args):
         _lib.set_option(name, int(val or 1))
     if args.workload == 'hod':
         out = bench_hod(args, dist)
-        if not args.no_pk:
+        if args.full and not args.no_pk:
             import bench_pk
             for key, fn in (('calls', lambda: bench_calls(args, dist)),
                             ('pk', lambda: bench_pk.bench_pk(args, dist, headline=False, cpu=False)),
@@ -544,7 +574,7 @@ def single(args):
                     out['pk']['cpu_baseline_error'] = repr(e)
     else:
         from bench_pk import bench_pk
-        out = bench_pk(args, dist, headline=True)
+        out = bench_pk(args, dist, headline=True, cpu=args.full, variants=args.full, detail=args.full)
     print(json.dumps(out), flush=True)
     return 0
 

@@ -13,6 +13,22 @@ import numpy as np
 
 HBM_PEAK_GBS = 8000.0
 REPO = os.path.dirname(os.path.abspath(__file__))
+DUMP_BYTES = 60_000_000        # bench.py --dump-outputs stays under 64 MB, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """bench.py --dump-outputs: every array as <path>/<name>.npy in float64.  Above DUMP_BYTES in all, the same seeded rows of
+    every array are kept (a fixed sample, so two builds can be compared output for output), their indices in <name>_rows.npy"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES and a.ndim and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_BYTES / (2 * total)))     # data + row indices stay within DUMP_BYTES
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            np.save(os.path.join(path, f'{name}_rows.npy'), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f'{name}.npy'), a)
 
 
 def pmc_traffic(workload, kernel):
@@ -34,7 +50,9 @@ def pmc_traffic(workload, kernel):
     return None
 
 
-def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
+def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True, detail=True):
+    """headline: exactly --steps timed steps after --warmup (at least one) warm-ups, the spectrum of the last one to
+    --dump-outputs; as a secondary leg at most 10 / 2.  `detail`: the per-kernel table and the roofline"""
     import ctypes as C
     from abacusutils_amd import _lib
     from abacusutils_amd.analysis import power_spectrum as ps
@@ -58,30 +76,33 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
             _lib.ptr(W), int(interlaced), _lib.ptr(ke), len(ke) - 1, _lib.ptr(me), len(me) - 1, _lib.ptr(poles),
             len(poles), *[_lib.ptr(o) for o in outs]))
 
-    steps = max(1, min(args.steps, 10))
+    steps = args.steps if headline else max(1, min(args.steps, 10))
+    warmup = max(1, args.warmup) if headline else max(1, min(args.warmup, 2))
     _lib.sync()
     tf = time.perf_counter()
     step()                                   # the first call of this mesh: allocations, twiddle tables, the geometry descriptor
     _lib.sync()                              # of the (k, mu) bins, an exact (synchronous) list build
     first_call_ms = (time.perf_counter() - tf) * 1e3
-    for _ in range(max(1, min(args.warmup, 2)) - 1):
+    for _ in range(warmup - 1):
         step()
     lib.abacus_power_geometry_ms.restype = C.c_double
     geometry_ms = float(lib.abacus_power_geometry_ms())   # one-off pass of the first call (cached per (nmesh, edges))
     xbin_gen = int(lib.abacus_power_xbin_generation())
     # per-kernel table from two untimed steps with every launch bracketed by HIP events; in the TIMED region only the dominant
     # kernel is bracketed (a pair of event records per launch costs a few microseconds of a 10-ms step and a barrier packet each)
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    for _ in range(2):
-        step()
-    _lib.sync()
-    _lib.profile_enable(False)
-    kern = {k: ms / c for k, (ms, c) in _lib.profile_get().items() if c}
-    dom0 = max(kern, key=kern.get)
+    kern, dom0 = {}, None
+    if detail:
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        for _ in range(2):
+            step()
+        _lib.sync()
+        _lib.profile_enable(False)
+        kern = {k: ms / c for k, (ms, c) in _lib.profile_get().items() if c}
+        dom0 = max(kern, key=kern.get)
     _lib.profile_reset()
     _lib.profile_select(dom0)
-    _lib.profile_enable(True)
+    _lib.profile_enable(detail)
     dist.barrier()
     _lib.sync()
     t0 = time.perf_counter()
@@ -94,6 +115,8 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
     _lib.profile_enable(False)
     _lib.profile_select(None)
     kern.update({k: ms / c for k, (ms, c) in _lib.profile_get().items() if c})   # the dominant kernel: measured in the timed steps
+    if headline and args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(('power', 'N_mode', 'binned_poles', 'N_mode_poles', 'k_avg'), outs)))
 
     power = outs[0].copy()
     shot = L**3 / n
@@ -118,15 +141,13 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
         'tsc_lines_fcount': 16.0 * REC * n,
         'tsc_lines_fine': 16.0 * REC * n + 8.0 * ENT * n,
     }
-    dom = max((k for k in kern if k in alg), key=lambda k: kern[k])
-    ach = alg[dom] / (kern[dom] * 1e-3) / 1e9
     out = {
         'metric': f'wall-clock of {nmesh}^3 TSC+FFT P(k)',
         'value': dt * 1e3,
         'unit': 'ms',
         'n_gpus': dist.world,
         'steps': steps,
-        'warmup': max(1, min(args.warmup, 2)),
+        'warmup': warmup,
         'ms_per_step': dt * 1e3,
         'higher_is_better': False,
         'scaling': 'weak',
@@ -136,19 +157,23 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
         'config': {'workload': f'{"BASELINE config 3" if nmesh == 1024 else "C3-style"}: {n:.0e} uniform float32 particles (seed 300+rank), L=2000, nmesh={nmesh}, '
                                'TSC, non-interlaced, uncompensated, 4 mu bins, poles 0/2/4; particles resident in HBM',
                    'nmesh': nmesh, 'n_particles': n},
-        'kernels_ms': {k: round(v, 4) for k, v in kern.items()},
         'geometry_ms': round(geometry_ms, 3),
         'first_call_ms': round(first_call_ms, 2),
         'geometry_note': 'N_mode, k_avg and the cell table of the (k, mu) bins depend on (nmesh, edges) alone: one pass over the '
                          f'modes at the first spectrum of a mesh / edge set, cached (fused last pass generation {xbin_gen}); outside the timed steps',
         'mean_P_over_shot_noise': float(np.mean(power[len(power) // 4:, :]) / shot),
-        'roofline': {'bound': 'hbm', 'kernel': dom, 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': ach / HBM_PEAK_GBS, 'algorithmic_bytes': alg[dom],
-                     'per_kernel_frac': {k: round(alg[k] / (kern[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) for k in kern if k in alg},
-                     'traffic': pmc_traffic('pk2048', dom) if (nmesh, n) == (2048, 100_000_000) else None,
-                     'whole_step_GBs': alg_bytes_total / dt / 1e9,
-                     'whole_step_frac': alg_bytes_total / dt / 1e9 / HBM_PEAK_GBS},
     }
+    if detail:
+        dom = max((k for k in kern if k in alg), key=lambda k: kern[k])
+        ach = alg[dom] / (kern[dom] * 1e-3) / 1e9
+        out['kernels_ms'] = {k: round(v, 4) for k, v in kern.items()}
+        out['roofline'] = {'bound': 'hbm', 'kernel': dom, 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                           'frac': ach / HBM_PEAK_GBS, 'algorithmic_bytes': alg[dom],
+                           'per_kernel_frac': {k: round(alg[k] / (kern[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) for k in kern if k in alg},
+                           'traffic': pmc_traffic('pk2048', dom) if (nmesh, n) == (2048, 100_000_000) else None,
+                           'whole_step_GBs': alg_bytes_total / dt / 1e9,
+                           'whole_step_frac': alg_bytes_total / dt / 1e9 / HBM_PEAK_GBS}
+    vsteps = max(1, min(args.steps, 10))     # the variants below: as many steps as in a secondary leg
     # interlaced + compensated variant (the calc_power defaults): 24 N + 80 M algorithmic bytes
     if variants:
         try:
@@ -157,10 +182,10 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
             step(1, W)
             _lib.sync()
             t1 = time.perf_counter()
-            for _ in range(max(1, steps // 2)):
+            for _ in range(max(1, vsteps // 2)):
                 step(1, W)
             _lib.sync()
-            dti = (time.perf_counter() - t1) / max(1, steps // 2)
+            dti = (time.perf_counter() - t1) / max(1, vsteps // 2)
             _lib.profile_reset()
             _lib.profile_enable(True)
             step(1, W)
@@ -190,10 +215,10 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
             cstep()
             _lib.sync()
             t1 = time.perf_counter()
-            for _ in range(max(1, steps // 2)):
+            for _ in range(max(1, vsteps // 2)):
                 cstep()
             _lib.sync()
-            dtc = (time.perf_counter() - t1) / max(1, steps // 2)
+            dtc = (time.perf_counter() - t1) / max(1, vsteps // 2)
             _lib.profile_reset()
             _lib.profile_enable(True)
             cstep()
@@ -222,7 +247,7 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
                         qstep()
                     _lib.sync()
                     return (time.perf_counter() - t1_) / reps
-                dtq = timed(max(1, steps // 3))
+                dtq = timed(max(1, vsteps // 3))
                 _lib.profile_reset()
                 _lib.profile_enable(True)
                 qstep()
@@ -230,7 +255,7 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
                 _lib.profile_enable(False)
                 kq = {k: ms for k, (ms, c) in _lib.profile_get().items() if c}
                 _lib.set_option('pk_noxbin_cross', 1)
-                dtu = timed(max(1, steps // 3))
+                dtu = timed(max(1, vsteps // 3))
                 _lib.set_option('pk_noxbin_cross', 0)
                 out['interlaced_cross'] = {'ms_per_step': dtq * 1e3, 'unfused_ms_per_step': dtu * 1e3, 'n_particles_2': n2,
                                            'kernels_ms_per_step': kq}
@@ -243,7 +268,7 @@ def bench_pk(args, dist, headline, nmesh=None, cpu=True, variants=True):
     dpos.free()
     # the drop-in call itself: calc_power on the NumPy positions (PCIe included; never the `value`): the upload runs in batches
     # on a copy stream, each batch deposited while the next is on the link (csrc/power.hip, HostSrc)
-    if nmesh == 1024 and dist.world == 1 and variants is False:
+    if nmesh == 1024 and dist.world == 1 and variants is False and detail:
         try:
             ckw = dict(kbins=min(512, nmesh // 2), mubins=4, k_max=np.pi * nmesh / L + 1e-6, paste='TSC', nmesh=nmesh, compensated=False,
                        interlaced=False, poles=[0, 2, 4])

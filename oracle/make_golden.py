@@ -37,7 +37,10 @@ What is captured
         for its file layer (CompaSOHaloCatalog -> synth tables, h5py -> capture): three configurations (MT / LRG-only,
         ranks, assembly bias with the padded Menv, shear).
 
-usage: python oracle/make_golden.py [hod] [tsc] [power] [helpers] [catalog] [sweep] [ngal] [pairs] [prepare]
+  Mini_N64_L32/ref_hod/       the reference's prepare_sim HDF5 files of Mini_N64_L32 (its test data), for
+        tests/test_staging.py.
+
+usage: python oracle/make_golden.py [hod] [tsc] [power] [helpers] [catalog] [sweep] [ngal] [pairs] [prepare] [staging]
 """
 import ctypes
 import os
@@ -1027,8 +1030,24 @@ def gen_mini_prepare():
     print('prepare_mini / compaso_mini written;', sum(f.stat().st_size for f in dst.rglob('*') if f.is_file()) // 1024, 'KiB of input files')
 
 
+def gen_staging_inputs():
+    """the prepare_sim HDF5 subsample files of Mini_N64_L32 (the reference's test DATA, tests/ref_hod/Mini_N64_L32/z0.000:
+    six files, 170 KB) copied to tests/golden/Mini_N64_L32/ref_hod/ in the reference's directory layout: the files
+    tests/test_staging.py stages AbacusHOD from"""
+    import shutil
+    src = REF / 'tests' / 'ref_hod' / 'Mini_N64_L32' / 'z0.000'
+    dst = GOLD / 'Mini_N64_L32' / 'ref_hod' / 'Mini_N64_L32' / 'z0.000'
+    if dst.exists():
+        shutil.rmtree(dst)
+    dst.mkdir(parents=True)
+    for f in sorted(src.glob('*.h5')):
+        shutil.copyfile(f, dst / f.name)
+        (dst / f.name).chmod(0o644)
+    print('staging inputs written:', ', '.join(sorted(f.name for f in dst.iterdir())))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['hod', 'tsc', 'power', 'helpers', 'exports', 'catalog', 'sweep', 'ngal', 'pairs', 'prepare', 'mini', 'power64']
+    which = sys.argv[1:] or ['hod', 'tsc', 'power', 'helpers', 'exports', 'catalog', 'sweep', 'ngal', 'pairs', 'prepare', 'mini', 'power64', 'staging']
     G, T, P, C = import_reference()
     GOLD.mkdir(parents=True, exist_ok=True)
     if 'hod' in which:
@@ -1055,3 +1074,5 @@ if __name__ == '__main__':
         gen_pair_wrappers()
     if 'prepare' in which:
         gen_prepare()
+    if 'staging' in which:
+        gen_staging_inputs()

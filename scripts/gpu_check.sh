@@ -18,11 +18,11 @@ only:*)
   timeout 2400 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider -k "${w#only:}" > "$O/gpu_only.log" 2>&1; tail -40 "$O/gpu_only.log"
   ;;
 bench)
-  timeout 1500 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"; cat "$O/bench_default.json"; tail -3 "$O/bench_default.err"
+  timeout 1500 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"; cat "$O/bench_default.json"; tail -3 "$O/bench_default.err"
   ;;
 bench2)
   # two ranks on a one-GPU box: RCCL refuses the duplicate device - the line must still be printed, with the error
-  timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --hod-timeout 200 --slab-timeout 120 > "$O/bench_gpus2.json" 2> "$O/bench_gpus2.err"; echo "rc=$?"; cut -c1-1500 "$O/bench_gpus2.json"; tail -3 "$O/bench_gpus2.err"
+  timeout 900 python bench.py --full --gpus 2 --steps 3 --warmup 1 --hod-timeout 200 --slab-timeout 120 > "$O/bench_gpus2.json" 2> "$O/bench_gpus2.err"; echo "rc=$?"; cut -c1-1500 "$O/bench_gpus2.json"; tail -3 "$O/bench_gpus2.err"
   ;;
 esac
 done

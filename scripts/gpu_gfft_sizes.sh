@@ -8,7 +8,7 @@ for NM in ${MESHES:-96 384 550 768 1536}; do
     mode=${spec%%:*}; opt_=()
     [ "$spec" != "$mode" ] && opt_=(--option "${spec#*:}")
     NP=$(( NM > 600 ? 100000000 : 20000000 ))
-    timeout -k 10 300 python bench.py --workload pk --nmesh $NM --npk $NP --steps 6 --warmup 2 --no-cpu "${opt_[@]}" > "$O/pk${NM}_$mode.json" 2> "$O/pk${NM}_$mode.err" || { tail -3 "$O/pk${NM}_$mode.err"; exit 1; }
+    timeout -k 10 300 python bench.py --full --workload pk --nmesh $NM --npk $NP --steps 6 --warmup 2 --no-cpu "${opt_[@]}" > "$O/pk${NM}_$mode.json" 2> "$O/pk${NM}_$mode.err" || { tail -3 "$O/pk${NM}_$mode.err"; exit 1; }
     python - "$O/pk${NM}_$mode.json" "$NM $mode" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -15,7 +15,7 @@ for spec in ${@:-base}; do
     IFS=, read -ra kv <<< "${spec#*:}"
     for o in "${kv[@]}"; do opt_+=(--option "$o"); done
   fi
-  timeout 400 python bench.py --no-pk --no-cpu --steps 30 --warmup 3 "${opt_[@]}" > "$O/hod_$mode.json" 2> "$O/hod_$mode.err" || { tail -3 "$O/hod_$mode.err"; exit 1; }
+  timeout 400 python bench.py --full --no-pk --no-cpu --steps 30 --warmup 3 "${opt_[@]}" > "$O/hod_$mode.json" 2> "$O/hod_$mode.err" || { tail -3 "$O/hod_$mode.err"; exit 1; }
   python - "$O/hod_$mode.json" "$mode" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

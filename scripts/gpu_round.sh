@@ -1,5 +1,5 @@
 #!/bin/bash
-# round check on the GPU box: all gpu tests, smoke, default bench, rocprofv3 kernel stats and PMC traffic passes.
+# round check on the GPU box: all gpu tests, smoke, the --full bench, rocprofv3 kernel stats and PMC traffic passes.
 # usage: bash scripts/gpu_round.sh [tests|bench|prof|pmc ...]   (default: all)
 cd "$GRAFT_REPO_ROOT" || exit 1
 R=$GRAFT_REPO_ROOT
@@ -15,13 +15,13 @@ tests)
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -12 | tee "$O/smoke.log"
   ;;
 bench)
-  timeout 1500 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"; cat "$O/bench_default.json"; tail -3 "$O/bench_default.err"
+  timeout 1500 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"; cat "$O/bench_default.json"; tail -3 "$O/bench_default.err"
   ;;
 prof)
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_hod" -- python3 "$R/bench.py" --steps 20 --warmup 3 --no-cpu --no-pk --no-hod-extra > "$O/prof_hod.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_hod" -- python3 "$R/bench.py" --full --steps 20 --warmup 3 --no-cpu --no-pk --no-hod-extra > "$O/prof_hod.log" 2>&1
   for NM in 1024 1536 2048; do
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_pk$NM" -- python3 "$R/bench.py" --workload pk --nmesh $NM --steps 3 --warmup 1 --no-cpu > "$O/prof_pk$NM.log" 2>&1
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_pk$NM" -- python3 "$R/bench.py" --full --workload pk --nmesh $NM --steps 3 --warmup 1 --no-cpu > "$O/prof_pk$NM.log" 2>&1
   done
   cd "$R"
   for d in prof_hod prof_pk1024 prof_pk1536 prof_pk2048; do
@@ -32,9 +32,9 @@ prof)
 pmc)
   cd /tmp
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$O/pmc_hod_$C" -- python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu --no-pk --no-hod-extra > "$O/pmc_hod_$C.log" 2>&1
+    timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$O/pmc_hod_$C" -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu --no-pk --no-hod-extra > "$O/pmc_hod_$C.log" 2>&1
     for NM in 1024 2048; do
-      timeout 900 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$O/pmc_pk${NM}_$C" -- python3 "$R/bench.py" --workload pk --nmesh $NM --steps 2 --warmup 1 --no-cpu > "$O/pmc_pk${NM}_$C.log" 2>&1
+      timeout 900 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$O/pmc_pk${NM}_$C" -- python3 "$R/bench.py" --full --workload pk --nmesh $NM --steps 2 --warmup 1 --no-cpu > "$O/pmc_pk${NM}_$C.log" 2>&1
     done
   done
   cd "$R"

@@ -1,11 +1,12 @@
 #!/bin/bash
 # kernel + copy timeline of one P(k) step (gaps between device activities): gpu_timeline.sh [nmesh] [npk]
 cd "$GRAFT_REPO_ROOT" || exit 1
+R=$PWD
 NM=${1:-1024}; NP=${2:-100000000}
 O=$GRAFT_REPO_ROOT/gpurun_out/ktrace
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace -d "$O" -o t --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --workload pk --nmesh $NM --npk $NP --steps 4 --warmup 2 --no-cpu $PK_OPTS > "$O/bench.log" 2>&1 || { tail -5 "$O/bench.log"; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace -d "$O" -o t --output-format csv -- python3 "$R/bench.py" --full --workload pk --nmesh $NM --npk $NP --steps 4 --warmup 2 --no-cpu $PK_OPTS > "$O/bench.log" 2>&1 || { tail -5 "$O/bench.log"; exit 1; }
 python3 - "$O" <<'PY'
 import csv, sys
 O = sys.argv[1]

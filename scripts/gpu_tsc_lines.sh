@@ -12,7 +12,7 @@ for NM in ${MESHES:-1024}; do
   for spec in new old:tsc_oldlists=1; do
     mode=${spec%%:*}; opt_=()
     [ "$spec" != "$mode" ] && opt_=(--option "${spec#*:}")
-    timeout -k 10 300 python bench.py --workload pk --nmesh $NM --steps 4 --warmup 1 --no-cpu "${opt_[@]}" > "$O/pk${NM}_$mode.json" 2> "$O/pk${NM}_$mode.err" || { tail -5 "$O/pk${NM}_$mode.err"; exit 1; }
+    timeout -k 10 300 python bench.py --full --workload pk --nmesh $NM --steps 4 --warmup 1 --no-cpu "${opt_[@]}" > "$O/pk${NM}_$mode.json" 2> "$O/pk${NM}_$mode.err" || { tail -5 "$O/pk${NM}_$mode.err"; exit 1; }
     python - "$O/pk${NM}_$mode.json" "$NM $mode" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -64,13 +64,13 @@ def _last_json(stdout):
 
 
 def test_bench_gpus_2_fails_loudly_without_a_gpu():
-    """`python bench.py --gpus 2` in a container without a GPU: the parent starts two rank processes, both report
-    "no HIP device", the line is still printed (value null, error from both ranks) and the exit code is non-zero"""
+    """`python bench.py --gpus 2 --full` in a container without a GPU: the parent starts two rank processes per leg, both
+    report "no HIP device", the line is still printed (value null, error from both ranks) and the exit code is non-zero"""
     from abacusutils_amd import _lib
     if _lib.device_count() > 0:
         import pytest
         pytest.skip('a GPU is present')
-    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0'],
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0', '--full'],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     line = _last_json(r.stdout)

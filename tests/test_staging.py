@@ -1,7 +1,7 @@
 """`AbacusHOD.staging()` (file plumbing, reference abacusnbody/hod/abacus_hod.py:263-702) against the staged arrays of
 tests/golden/hod_mini.npz, which oracle/make_golden.py built from the same prepare_sim HDF5 fixtures with its own
-HDF5 reader.  Needs h5py and the reference's Mini_N64_L32 fixtures, so it only runs in the build container (an
-interpreter with h5py is looked up; the main one has none) and is skipped elsewhere."""
+HDF5 reader.  The fixtures (the reference's Mini_N64_L32 test data: prepare_sim HDF5 subsamples, halo_info, abacus_hod.yaml)
+are stored under tests/golden/Mini_N64_L32.  Needs an interpreter with h5py (one is looked up; the main one has none)."""
 import os
 import shutil
 import subprocess
@@ -11,7 +11,7 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
-REF_TESTS = Path('/root/reference/tests')
+FIXTURES = ROOT / 'tests' / 'golden' / 'Mini_N64_L32'
 
 _SCRIPT = r'''
 import sys, yaml, numpy as np, h5py
@@ -113,11 +113,9 @@ def _python_with_h5py():
 
 
 def test_staging_matches_golden(tmp_path):
-    if not (REF_TESTS / 'ref_hod' / 'Mini_N64_L32').exists():
-        pytest.skip('reference HOD fixtures not present on this machine')
     exe = _python_with_h5py()
     if exe is None:
         pytest.skip('no interpreter with h5py')
-    r = subprocess.run([exe, '-c', _SCRIPT, str(ROOT), str(REF_TESTS), str(tmp_path), 'numpy-standins'], capture_output=True, text=True,
+    r = subprocess.run([exe, '-c', _SCRIPT, str(ROOT), str(FIXTURES), str(tmp_path), 'numpy-standins'], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0 and 'STAGING-OK' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
