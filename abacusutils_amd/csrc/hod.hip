@@ -7,22 +7,31 @@
 // plus what the kernels actually read: a packed 16-bit filter key per object, packed records of whole 128-B memory lines
 // for the sparse phases, and for LRG-only runs a (mass bin, q code)-sorted key index.
 //
-// Kernels (no MFMA - there is no contraction on this path); a populate is filter | deal -> exact -> emit:
+// Kernels (no MFMA - there is no contraction on this path); a populate is filter -> exact -> emit, or for LRG alone with
+// unchanged keys (from the second populate on) exact_index -> emit_bm:
 //   hod_filter_key  streams the keys (2 B per object): `code > threshold[bin]` proves keep = 0 for the bulk of the objects
 //        (an envelope table bounds the marker chain over the bin's masses and the catalogue's environment ranges); the
 //        rest is queued per 2048-object tile.  hod_filter / hod_filter32 are the comparator and fallback filters
 //        (float64 columns of caller-owned catalogues, float32 shadow columns).
-//   hod_deal        LRG alone, from the second populate on: the candidates are prefixes of the sorted key index, found on
-//        the host without reading a key; the kernel hands their indices to the tile queues.
+//   hod_exact_index LRG alone, from the second populate on: the candidates are prefixes of the sorted key index, found on
+//        the host without reading a key (DealTab).  One candidate per lane: index, record line, the classifier below; a kept
+//        object sets its keep byte, a bit of this populate's per-tracer kept bitmap and its superblock's count (non-returning
+//        atomics).  Profiled as hod_exact.
+//   hod_emit_bm     its emission: one workgroup per superblock ranks the rows by a popcount scan of the bitmap words, gathers
+//        and writes them as hod_emit does; it also un-keeps the objects the previous populate kept and this one did not and
+//        zeroes the previous populate's bitmaps and counts (two sets, alternating by populate parity).  Profiled as hod_emit.
+//   hod_deal        the comparator of that path (option hod_deal = 1): hands the candidates' indices to the tile queues
+//        that hod_exact walks.
 //   hod_exact       one workgroup per superblock (16 tiles for LRG alone, 8 for mixes with ELG / QSO): a float32 interval
 //        classifier settles a candidate from one packed record line; the reference's float64 chain (erfc, log10, pow) runs
-//        only where the random lies inside a marker's band.  Writes the int8 keep bytes (for LRG alone it first un-keeps
-//        what the previous populate kept - the filter no longer zeroes the masks) and - through per-tracer LDS bitmaps and
+//        only where the random lies inside a marker's band.  Writes the int8 keep bytes (for LRG alone on the hod_deal path it first
+//        un-keeps what the previous populate kept - the filter no longer zeroes the masks) and - through per-tracer LDS bitmaps and
 //        a popcount scan - the superblock's kept list in index order plus its three counts.
 //   hod_emit        one workgroup per superblock: sums the counters of the superblocks in front of it (a few hundred
 //        L2-resident ints) for its output offset - satellites start at Ncent, so centrals||satellites land
 //        concatenated (no fast_concatenate pass) - and gathers / writes the kept rows in input order (stable
-//        compaction = the reference's order for any Nthread).
+//        compaction = the reference's order for any Nthread).  Workgroup 0 writes the six totals straight into page-locked
+//        host memory mapped for the device: no copy follows a populate.
 // What bounds them is in DESIGN.md section 4: the filter the key stream, the sparse phases the 128-B lines they gather.
 // All FP64 arithmetic that reaches an OUTPUT (velocity bias, RSD) is + - * / sqrt in the reference's order,
 // compiled with -ffp-contract=off, so outputs are bit-identical to the CPU; the keep decision compares
@@ -813,8 +822,9 @@ __global__ __launch_bounds__(FBLOCK) void hod_filter_key(HodPtrs a, const unsign
 // to reject them is most of the filter's 17 us.  Once per catalogue (from its second populate with unchanged keys on) the
 // objects are sorted by (mass bin, q code); the candidates of a populate are then a PREFIX of every bin's segment - the
 // objects with code <= the bin's threshold code - whose length the host reads off a cumulative table without touching the
-// device.  hod_deal hands those indices to the tiles' queues (one global atomic per candidate: a hundred thousand at 1e7 +
-// 1e7); the candidate set is the key filter's, so everything behind it is unchanged.
+// device.  hod_exact_index settles them straight from the index; hod_deal (the comparator, option hod_deal = 1) hands the
+// indices to the tiles' queues instead (one returning global atomic per candidate: a hundred thousand at 1e7 + 1e7) for
+// hod_exact.  The candidate set is the key filter's either way.
 __global__ __launch_bounds__(256) void hod_index_keys(const unsigned short *__restrict__ keys, int64_t n,
                                                       unsigned short *__restrict__ sk, unsigned int *__restrict__ idx) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -925,6 +935,36 @@ struct ExactCand {
     int q, loc;
 };
 
+// a candidate's scalars: one record line, or the staged columns (caller-owned catalogues)
+__device__ __forceinline__ void fetch_cand(const HodPtrs &a, const abacus_hod_params &p, bool sat, int64_t i, bool need_ranks,
+                                           bool need_conf, ExactCand &c) {
+    c.r0 = c.r1 = c.r2 = c.r3 = 1.0;
+    c.pinds = 0;
+    if (!sat) {
+        if (a.hrec) {
+            const HaloRec &r = a.hrec[i];
+            c.mass = r.mass, c.w = r.multis, c.rnd = r.rnd, c.dc = r.deltac, c.fe = r.fenv, c.sh = p.want_ELG ? r.shear : 0.0;
+        } else {
+            c.rnd = a.hrandoms[i];
+            c.mass = a.hmass[i], c.w = a.hmultis[i], c.dc = load1(a.hdeltac, i, 0.0), c.fe = load1(a.hfenv, i, 0.0),
+            c.sh = p.want_ELG ? load1(a.hshear, i, 0.0) : 0.0;
+        }
+    } else {
+        if (a.prec) {
+            const PartRec &r = a.prec[i];   // line 0
+            c.mass = r.mass, c.w = r.weights, c.rnd = r.rnd, c.dc = r.deltac, c.fe = r.fenv, c.sh = p.want_ELG ? r.shear : 0.0;
+            if (need_ranks) c.r0 = r.rank0, c.r1 = r.rank1, c.r2 = r.rank2, c.r3 = r.rank3;
+            if (need_conf) c.pinds = r.pinds;
+        } else {
+            if (need_conf) c.pinds = a.pinds[i];
+            c.rnd = a.prandoms[i];
+            c.mass = a.phmass[i], c.w = a.pweights[i], c.dc = load1(a.pdeltac, i, 0.0), c.fe = load1(a.pfenv, i, 0.0),
+            c.sh = p.want_ELG ? load1(a.pshear, i, 0.0) : 0.0;
+            if (need_ranks) c.r0 = a.pranks[i], c.r1 = a.pranksv[i], c.r2 = a.pranksp[i], c.r3 = a.pranksr[i];
+        }
+    }
+}
+
 template <int XB, bool PIPE, int SBT>
 __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, const abacus_hod_params &p, const SatPre &pre,
                                                const abacus_cls::ClsConst &cc, int use_cls, int clear_prev) {
@@ -983,32 +1023,7 @@ __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, c
     // the candidate's scalars: one record line, or the staged columns (caller-owned catalogues)
     auto fetch = [&](int q, int loc, ExactCand &c) {
         c.q = q, c.loc = loc;
-        const int64_t i = (int64_t)(tile_first + q) * TILE + loc;
-        c.r0 = c.r1 = c.r2 = c.r3 = 1.0;
-        c.pinds = 0;
-        if (!sat) {
-            if (a.hrec) {
-                const HaloRec &r = a.hrec[i];
-                c.mass = r.mass, c.w = r.multis, c.rnd = r.rnd, c.dc = r.deltac, c.fe = r.fenv, c.sh = p.want_ELG ? r.shear : 0.0;
-            } else {
-                c.rnd = a.hrandoms[i];
-                c.mass = a.hmass[i], c.w = a.hmultis[i], c.dc = load1(a.hdeltac, i, 0.0), c.fe = load1(a.hfenv, i, 0.0),
-                c.sh = p.want_ELG ? load1(a.hshear, i, 0.0) : 0.0;
-            }
-        } else {
-            if (a.prec) {
-                const PartRec &r = a.prec[i];   // line 0
-                c.mass = r.mass, c.w = r.weights, c.rnd = r.rnd, c.dc = r.deltac, c.fe = r.fenv, c.sh = p.want_ELG ? r.shear : 0.0;
-                if (need_ranks) c.r0 = r.rank0, c.r1 = r.rank1, c.r2 = r.rank2, c.r3 = r.rank3;
-                if (need_conf) c.pinds = r.pinds;
-            } else {
-                if (need_conf) c.pinds = a.pinds[i];
-                c.rnd = a.prandoms[i];
-                c.mass = a.phmass[i], c.w = a.pweights[i], c.dc = load1(a.pdeltac, i, 0.0), c.fe = load1(a.pfenv, i, 0.0),
-                c.sh = p.want_ELG ? load1(a.pshear, i, 0.0) : 0.0;
-                if (need_ranks) c.r0 = a.pranks[i], c.r1 = a.pranksv[i], c.r2 = a.pranksp[i], c.r3 = a.pranksr[i];
-            }
-        }
+        fetch_cand(a, p, sat, (int64_t)(tile_first + q) * TILE + loc, need_ranks, need_conf, c);
     };
     auto classify = [&](const ExactCand &c, int kc) {   // -1: the random lies inside a marker's band (or the classifier is off)
         if (!use_cls) return -1;
@@ -1191,6 +1206,63 @@ __global__ __launch_bounds__(XB) __attribute__((amdgpu_waves_per_eu(4))) void ho
     hod_exact_body<XB, false, SBT>(a, first_sb, p, pre, cc, use_cls, clear_prev);
 }
 
+// ints per superblock in the counts of the queue-free path: a 128-B line each.  Their ~180 increments per populate are
+// serialised per line where device-scope atomics execute; four superblocks to a line (the layout of sb_counts) made
+// hod_exact_index 25 us instead of 16 at 1e7 + 1e7.
+constexpr int BM_CS = 32;
+// Index path without queues (sparse mixes, unchanged keys; `hod_deal` = 1 restores hod_deal -> hod_exact -> hod_emit): one
+// candidate per lane, straight from the mass-sorted index.  Candidate j lies in the DealTab segment with pre <= j (binary
+// search in LDS), its object index is one coalesced 4-B load and its record line the only gather; it is settled by the same
+// classifier and float64 chains as in hod_exact.  A kept object sets its keep byte, one bit in this populate's bitmap of its
+// tracer (centrals' words first, then the satellites', bit = object index) and adds one to its superblock's count - all
+// three non-returning: no atomic result sits on a dependency chain.  hod_emit_bm reads its rows off the bitmaps.  No ELG
+// conformity here: keep_cent holds the previous populate's bytes until hod_emit_bm (the host takes hod_deal for such mixes).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void hod_exact_index(
+    HodPtrs a, const unsigned int *__restrict__ idx_h, const unsigned int *__restrict__ idx_p, DealTab tab, unsigned int ncand,
+    unsigned int *__restrict__ bm, int64_t bm_words, int *__restrict__ counts, abacus_hod_params p, SatPre pre,
+    abacus_cls::ClsConst cc, int use_cls) {
+    __shared__ unsigned int s_pre[257], s_start[256];
+    __shared__ abacus_hod_params s_p;     // read by the out-of-line float64 chains
+    __shared__ SatPre s_sp;
+    const int tid = threadIdx.x;
+    if (tid < (int)(sizeof(abacus_hod_params) / 8))
+        reinterpret_cast<unsigned long long *>(&s_p)[tid] = reinterpret_cast<const unsigned long long *>(&p)[tid];
+    if (tid < (int)(sizeof(SatPre) / 8))
+        reinterpret_cast<unsigned long long *>(&s_sp)[tid] = reinterpret_cast<const unsigned long long *>(&pre)[tid];
+    for (int q = tid; q <= tab.nseg; q += 256) s_pre[q] = tab.pre[q];
+    for (int q = tid; q < tab.nseg; q += 256) s_start[q] = tab.start[q];
+    __syncthreads();
+    const unsigned int j = blockIdx.x * 256u + tid;
+    if (j >= ncand) return;
+    int lo = 0, hi = tab.nseg - 1;   // largest segment with pre <= j
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_pre[mid] <= j) lo = mid;
+        else hi = mid - 1;
+    }
+    const bool sat = lo >= tab.nseg_c;
+    const int64_t i = (sat ? idx_p : idx_h)[s_start[lo] + (j - s_pre[lo])];
+    if (i >= (sat ? a.np : a.nh)) return;   // never: the index is a permutation of [0, n)
+    ExactCand c;
+    fetch_cand(a, p, sat, i, p.enable_ranks != 0, false, c);
+    const int kc = 0;
+    int kk = -1;
+    if (use_cls)
+        kk = sat ? abacus_cls::sat_classify(cc, c.mass, c.w, c.rnd, c.dc, c.fe, c.sh, c.r0, c.r1, c.r2, c.r3, kc)
+                 : abacus_cls::cent_classify(cc, c.mass, c.w, c.rnd, c.dc, c.fe, c.sh);
+    if (kk < 0)
+        kk = sat ? sat_decide_cold(&s_p, &s_sp, c.mass, c.w, c.rnd, c.dc, c.fe, c.sh, c.r0, c.r1, c.r2, c.r3, kc)
+                 : cent_decide_cold(&s_p, c.mass, c.w, c.rnd, c.dc, c.fe, c.sh);
+    if (kk == 0) return;
+    (sat ? a.keep_s : a.keep_c)[i] = (int8_t)kk;
+    const int64_t o = (sat ? (int64_t)a.ntile_c * TILE : 0) + i;
+    atomicOr(bm + (int64_t)(kk - 1) * bm_words + (o >> 5), 1u << (o & 31));
+    // superblock S owns the tiles [S ntile / nsb, (S + 1) ntile / nsb) (sb_first_tile): the largest S with S ntile / nsb <= tile
+    const int tile = (int)(i / TILE), ntile = sat ? a.ntile_s : a.ntile_c, nsb = sat ? a.nsb_s : a.nsb_c;
+    const int S = (int)(((int64_t)(tile + 1) * nsb - 1) / ntile);
+    atomicAdd(counts + (int64_t)((sat ? a.nsb_c : 0) + S) * BM_CS + (kk - 1), 1);
+}
+
 struct OutCols {
     double *c[3][7];  // [tracer][x,y,z,vx,vy,vz,mass]
     int64_t *id[3];
@@ -1240,44 +1312,26 @@ __device__ __forceinline__ int64_t wave_sum(int64_t v) {
     return v;
 }
 
-struct EmitPtrs {
-    const double *hpos, *hvel, *hvdev, *hmass, *ppos, *pvel, *phvel, *phmass;
-    const int64_t *hid, *phid;
-    const HaloRec *hrec;   // nullptr: gather from the columns
-    const PartRec *prec;
-};
-
-template <int EBLOCK, int SBT>
-__global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int ntile_c, int ntile_s,
-                                                   const unsigned short *__restrict__ kept_c,
-                                                   const unsigned short *__restrict__ kept_s,
-                                                   const int *__restrict__ sb_counts, int64_t *__restrict__ totals,
-                                                   EmitPtrs in, abacus_hod_params p, OutCols o_arg, int dbg) {
-    __shared__ int64_t red[EBLOCK / 64][6];
-    // the column pointers and capacities are indexed by the galaxy's tracer: from a copy in LDS (an LDS read per use, counted
-    // by lgkmcnt) - indexing the kernel arguments at run time made every galaxy load them from the argument segment with
-    // vector memory loads, whose waits sat in front of the column stores
-    __shared__ OutCols o;
-    static_assert(sizeof(OutCols) % 8 == 0, "copied as 8-byte words");
+// the output offsets of superblock g: v[0..2] the counts of the superblocks of its kind in front of it, v[3..5] all central
+// counts (the satellites' offset); workgroup 0 also writes the totals Ncent[3], Nsat[3] for the host.  CS: ints per
+// superblock in sb_counts
+template <int EBLOCK, int CS>
+__device__ __forceinline__ void emit_offsets(int g, bool sat, int S, int nsb_c, int nsb_s, const int *__restrict__ sb_counts,
+                                             int64_t *__restrict__ totals, int64_t (&red)[EBLOCK / 64][6], int64_t (&v)[6]) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid < (int)(sizeof(OutCols) / 8))
-        reinterpret_cast<unsigned long long *>(&o)[tid] = reinterpret_cast<const unsigned long long *>(&o_arg)[tid];
-    const int g = blockIdx.x;
-    const bool sat = g >= nsb_c;
-    const int S = sat ? g - nsb_c : g;
-    const int64_t obj_first = (int64_t)sb_first_tile(S, sat ? ntile_s : ntile_c, sat ? nsb_s : nsb_c) * TILE;
-    const int *sb_c = sb_counts, *sb_s = sb_counts + (int64_t)nsb_c * 4;
+#pragma unroll
+    for (int t = 0; t < 6; t++) v[t] = 0;
+    const int *sb_c = sb_counts, *sb_s = sb_counts + (int64_t)nsb_c * CS;
     const int *sb_mine = sat ? sb_s : sb_c;
     // v[0..2]: counts of the superblocks of my kind in front of me; v[3..5]: all central counts (satellite offset,
     // and block 0 reports the totals)
-    int64_t v[6] = {0, 0, 0, 0, 0, 0};
     for (int s = tid; s < S; s += EBLOCK)
 #pragma unroll
-        for (int t = 0; t < 3; t++) v[t] += sb_mine[(int64_t)s * 4 + t];
+        for (int t = 0; t < 3; t++) v[t] += sb_mine[(int64_t)s * CS + t];
     if (sat || g == 0)
         for (int s = tid; s < nsb_c; s += EBLOCK)
 #pragma unroll
-            for (int t = 0; t < 3; t++) v[3 + t] += sb_c[(int64_t)s * 4 + t];
+            for (int t = 0; t < 3; t++) v[3 + t] += sb_c[(int64_t)s * CS + t];
 #pragma unroll
     for (int t = 0; t < 6; t++) v[t] = wave_sum(v[t]);
     if (lane == 0)
@@ -1294,7 +1348,7 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
         int64_t s3[3] = {0, 0, 0};
         for (int s = tid; s < nsb_s; s += EBLOCK)
 #pragma unroll
-            for (int t = 0; t < 3; t++) s3[t] += sb_s[(int64_t)s * 4 + t];
+            for (int t = 0; t < 3; t++) s3[t] += sb_s[(int64_t)s * CS + t];
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < 3; t++) s3[t] = wave_sum(s3[t]);
@@ -1309,6 +1363,70 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
             totals[tid] = tid == 0 ? v[3] : (tid == 1 ? v[4] : v[5]);
         }
     }
+}
+
+struct EmitPtrs {
+    const double *hpos, *hvel, *hvdev, *hmass, *ppos, *pvel, *phvel, *phmass;
+    const int64_t *hid, *phid;
+    const HaloRec *hrec;   // nullptr: gather from the columns
+    const PartRec *prec;
+};
+
+// one galaxy's row: the kept object's record line (halo / particle line 1), or the staged columns
+__device__ __forceinline__ void emit_gather(const EmitPtrs &in, bool sat, int64_t i, double al, double &x, double &y, double &z,
+                                            double &vx, double &vy, double &vz, double &m, int64_t &id) {
+    if (!sat && in.hrec) {
+        const HaloRec &r = in.hrec[i];
+        x = r.pos0, y = r.pos1, z = r.pos2;
+        vx = r.vel[0] + al * r.vdev[0];
+        vy = r.vel[1] + al * r.vdev[1];
+        vz = r.vel[2] + al * r.vdev[2];
+        m = r.mass, id = r.id;
+    } else if (sat && in.prec) {
+        const PartRec &r = in.prec[i];   // line 1
+        x = r.pos[0], y = r.pos[1], z = r.pos[2];
+        vx = r.hvel[0] + al * (r.vel0 - r.hvel[0]);
+        vy = r.hvel[1] + al * (r.vel1 - r.hvel[1]);
+        vz = r.hvel[2] + al * (r.vel2 - r.hvel[2]);
+        m = r.mass2, id = r.id;
+    } else if (!sat) {
+        x = in.hpos[3 * i], y = in.hpos[3 * i + 1], z = in.hpos[3 * i + 2];
+        vx = in.hvel[3 * i] + al * in.hvdev[3 * i];  // velocity bias (:301-305)
+        vy = in.hvel[3 * i + 1] + al * in.hvdev[3 * i + 1];
+        vz = in.hvel[3 * i + 2] + al * in.hvdev[3 * i + 2];
+        m = in.hmass[i];
+        id = in.hid[i];
+    } else {
+        x = in.ppos[3 * i], y = in.ppos[3 * i + 1], z = in.ppos[3 * i + 2];
+        vx = in.phvel[3 * i] + al * (in.pvel[3 * i] - in.phvel[3 * i]);  // (:1136-1146)
+        vy = in.phvel[3 * i + 1] + al * (in.pvel[3 * i + 1] - in.phvel[3 * i + 1]);
+        vz = in.phvel[3 * i + 2] + al * (in.pvel[3 * i + 2] - in.phvel[3 * i + 2]);
+        m = in.phmass[i];
+        id = in.phid[i];
+    }
+}
+
+template <int EBLOCK, int SBT>
+__global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int ntile_c, int ntile_s,
+                                                   const unsigned short *__restrict__ kept_c,
+                                                   const unsigned short *__restrict__ kept_s,
+                                                   const int *__restrict__ sb_counts, int64_t *__restrict__ totals,
+                                                   EmitPtrs in, abacus_hod_params p, OutCols o_arg, int dbg) {
+    __shared__ int64_t red[EBLOCK / 64][6];
+    // the column pointers and capacities are indexed by the galaxy's tracer: from a copy in LDS (an LDS read per use, counted
+    // by lgkmcnt) - indexing the kernel arguments at run time made every galaxy load them from the argument segment with
+    // vector memory loads, whose waits sat in front of the column stores
+    __shared__ OutCols o;
+    static_assert(sizeof(OutCols) % 8 == 0, "copied as 8-byte words");
+    const int tid = threadIdx.x;
+    if (tid < (int)(sizeof(OutCols) / 8))
+        reinterpret_cast<unsigned long long *>(&o)[tid] = reinterpret_cast<const unsigned long long *>(&o_arg)[tid];
+    const int g = blockIdx.x;
+    const bool sat = g >= nsb_c;
+    const int S = sat ? g - nsb_c : g;
+    const int64_t obj_first = (int64_t)sb_first_tile(S, sat ? ntile_s : ntile_c, sat ? nsb_s : nsb_c) * TILE;
+    int64_t v[6];
+    emit_offsets<EBLOCK, 4>(g, sat, S, nsb_c, nsb_s, sb_counts, totals, red, v);
     const int m0 = sb_counts[(int64_t)g * 4], m1 = sb_counts[(int64_t)g * 4 + 1], m2 = sb_counts[(int64_t)g * 4 + 2];
     const int total = m0 + m1 + m2;
     if (total == 0) return;
@@ -1397,34 +1515,8 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
         if (dbg & 2) {   // ablation: no gather
             x = y = z = vx = vy = vz = m = (double)i;
             id = i;
-        } else if (!sat && in.hrec) {
-            const HaloRec &r = in.hrec[i];
-            x = r.pos0, y = r.pos1, z = r.pos2;
-            vx = r.vel[0] + al * r.vdev[0];
-            vy = r.vel[1] + al * r.vdev[1];
-            vz = r.vel[2] + al * r.vdev[2];
-            m = r.mass, id = r.id;
-        } else if (sat && in.prec) {
-            const PartRec &r = in.prec[i];   // line 1
-            x = r.pos[0], y = r.pos[1], z = r.pos[2];
-            vx = r.hvel[0] + al * (r.vel0 - r.hvel[0]);
-            vy = r.hvel[1] + al * (r.vel1 - r.hvel[1]);
-            vz = r.hvel[2] + al * (r.vel2 - r.hvel[2]);
-            m = r.mass2, id = r.id;
-        } else if (!sat) {
-            x = in.hpos[3 * i], y = in.hpos[3 * i + 1], z = in.hpos[3 * i + 2];
-            vx = in.hvel[3 * i] + al * in.hvdev[3 * i];  // velocity bias (:301-305)
-            vy = in.hvel[3 * i + 1] + al * in.hvdev[3 * i + 1];
-            vz = in.hvel[3 * i + 2] + al * in.hvdev[3 * i + 2];
-            m = in.hmass[i];
-            id = in.hid[i];
         } else {
-            x = in.ppos[3 * i], y = in.ppos[3 * i + 1], z = in.ppos[3 * i + 2];
-            vx = in.phvel[3 * i] + al * (in.pvel[3 * i] - in.phvel[3 * i]);  // (:1136-1146)
-            vy = in.phvel[3 * i + 1] + al * (in.pvel[3 * i + 1] - in.phvel[3 * i + 1]);
-            vz = in.phvel[3 * i + 2] + al * (in.pvel[3 * i + 2] - in.phvel[3 * i + 2]);
-            m = in.phmass[i];
-            id = in.phid[i];
+            emit_gather(in, sat, i, al, x, y, z, vx, vy, vz, m, id);
         }
         if (dbg & 1) {   // ablation: no column stores (one conditional store keeps the gather alive)
             if (x + y + z + vx + vy + vz + m == 1.2345e300 && id == 77) o.c[t][0][j] = x;
@@ -1432,6 +1524,136 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
         }
         emit_one(p, o, t, j, x, y, z, vx, vy, vz, m, id);
     }
+}
+
+// Emission of the queue-free index path (hod_exact_index): one workgroup per superblock, rows found in the bitmaps.  Thread t
+// owns words [4t, 4t + 4) of the superblock's 1024 words per tracer (coalesced 16-B loads); a packed 3 x 21-bit popcount scan
+// ranks its bits, and the ranks go through an LDS list (EMIT_WIN rows at a time) so that every lane gathers about the same
+// number of rows.  Two sets of bitmaps and counts alternate by populate parity: the workgroup also un-keeps the objects set in
+// the previous populate's bitmaps and clear in this one's (the only non-zero keep bytes outside this populate's bitmaps),
+// then zeroes its words and counts of the previous set, which nobody reads any more - the next populate starts from a clean
+// set, and a re-emission of this populate (abacus_hod_counts after a capacity growth) finds its own set intact.  The ELG / QSO
+// words are read only where the superblock's count of the set says it kept some (LRG's always: no wait on the counts).
+constexpr int EMIT_WIN = 2048;
+template <int EBLOCK, int SBT>
+__global__ __launch_bounds__(EBLOCK) void hod_emit_bm(int nsb_c, int nsb_s, int ntile_c, int ntile_s,
+                                                      const unsigned int *__restrict__ bm_cur, unsigned int *__restrict__ bm_prev,
+                                                      int64_t bm_words,
+                                                      const int *__restrict__ sb_counts, int *__restrict__ sb_prev,
+                                                      int8_t *__restrict__ keep_c, int8_t *__restrict__ keep_s,
+                                                      int64_t *__restrict__ totals, EmitPtrs in, abacus_hod_params p, OutCols o_arg) {
+    constexpr int WPT = 4;
+    static_assert(SBT * TILE / 32 == WPT * EBLOCK, "one 16-B load per thread and tracer");
+    __shared__ int64_t red[EBLOCK / 64][6];
+    __shared__ OutCols o;   // see hod_emit
+    __shared__ unsigned long long wave_tot[EBLOCK / 64];
+    __shared__ unsigned short lst[EMIT_WIN];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid < (int)(sizeof(OutCols) / 8))
+        reinterpret_cast<unsigned long long *>(&o)[tid] = reinterpret_cast<const unsigned long long *>(&o_arg)[tid];
+    const int g = blockIdx.x;
+    const bool sat = g >= nsb_c;
+    const int S = sat ? g - nsb_c : g;
+    const int ntile = sat ? ntile_s : ntile_c, nsb = sat ? nsb_s : nsb_c;
+    const int tile_first = sb_first_tile(S, ntile, nsb), ntl = sb_first_tile(S + 1, ntile, nsb) - tile_first;   // <= SBT
+    const int64_t obj_first = (int64_t)tile_first * TILE;
+    // the superblock's counts of both sets, then its bitmap words: their loads overlap the offset sums
+    int m[3], pm[3];
+#pragma unroll
+    for (int t = 0; t < 3; t++) m[t] = sb_counts[(int64_t)g * BM_CS + t], pm[t] = sb_prev[(int64_t)g * BM_CS + t];
+    const bool mine = tid * WPT * 32 < ntl * TILE;
+    const int64_t w0 = ((sat ? (int64_t)ntile_c * TILE : 0) + obj_first) / 32 + tid * WPT;
+    unsigned int cur[3][WPT], prv[3][WPT];
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        uint4 c = make_uint4(0u, 0u, 0u, 0u), q = make_uint4(0u, 0u, 0u, 0u);
+        if (mine && (t == 0 || m[t] > 0)) c = *reinterpret_cast<const uint4 *>(bm_cur + t * bm_words + w0);
+        if (mine && (t == 0 || pm[t] > 0)) q = *reinterpret_cast<const uint4 *>(bm_prev + t * bm_words + w0);
+        cur[t][0] = c.x, cur[t][1] = c.y, cur[t][2] = c.z, cur[t][3] = c.w;
+        prv[t][0] = q.x, prv[t][1] = q.y, prv[t][2] = q.z, prv[t][3] = q.w;
+    }
+    int64_t v[6];
+    emit_offsets<EBLOCK, BM_CS>(g, sat, S, nsb_c, nsb_s, sb_counts, totals, red, v);
+    if (mine) {
+        int8_t *keep = (sat ? keep_s : keep_c) + obj_first + tid * WPT * 32;
+#pragma unroll
+        for (int w = 0; w < WPT; w++) {
+            unsigned int gone = (prv[0][w] | prv[1][w] | prv[2][w]) & ~(cur[0][w] | cur[1][w] | cur[2][w]);
+            while (gone) {
+                const int b = __ffs((int)gone) - 1;
+                gone &= gone - 1;
+                keep[w * 32 + b] = 0;
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 3; t++)
+            if (pm[t] > 0) *reinterpret_cast<uint4 *>(bm_prev + t * bm_words + w0) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (tid < 3) sb_prev[(int64_t)g * BM_CS + tid] = 0;   // every thread read them before the barriers of emit_offsets
+    if (m[0] + m[1] + m[2] == 0) return;   // uniform
+    // ranks: packed 3 x 21-bit exclusive scan of the threads' popcounts (tracer-major, index order inside a tracer)
+    unsigned long long mine_c = 0;
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        unsigned int c = 0;
+#pragma unroll
+        for (int w = 0; w < WPT; w++) c += __popc(cur[t][w]);
+        mine_c |= (unsigned long long)c << (21 * t);
+    }
+    unsigned long long incl = mine_c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long u = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += u;
+    }
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < EBLOCK / 64; w++) {
+        if (w < wv) before += wave_tot[w];
+        all += wave_tot[w];
+    }
+    const unsigned long long excl = before + incl - mine_c;
+    // the list holds exactly the bits (equal to the counts: each kept object set one bit and added one)
+    const int n0 = (int)(all & 0x1fffff), n1 = (int)((all >> 21) & 0x1fffff), nall = n0 + n1 + (int)((all >> 42) & 0x1fffff);
+    const int base[3] = {0, n0, n0 + n1};
+    const int64_t off0 = v[0] + (sat ? v[3] : 0), off1 = v[1] + (sat ? v[4] : 0), off2 = v[2] + (sat ? v[5] : 0);
+    const double a0 = sat ? p.L_alpha_s : p.L_alpha_c, a1 = sat ? p.E_alpha_s : p.E_alpha_c,
+                 a2 = sat ? p.Q_alpha_s : p.Q_alpha_c;
+    for (int e0 = 0; e0 < nall; e0 += EMIT_WIN) {   // uniform
+        const int e1 = min(nall, e0 + EMIT_WIN);
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            int r = base[t] + (int)((excl >> (21 * t)) & 0x1fffff);
+#pragma unroll
+            for (int w = 0; w < WPT; w++) {
+                unsigned int bits = cur[t][w];
+                while (bits && r < e1) {
+                    const int b = __ffs((int)bits) - 1;
+                    bits &= bits - 1;
+                    if (r >= e0) lst[r - e0] = (unsigned short)((tid * WPT + w) * 32 + b);
+                    r++;
+                }
+            }
+        }
+        __syncthreads();
+        for (int e = e0 + tid; e < e1; e += EBLOCK) {
+            const int t = e < n0 ? 0 : (e < n0 + n1 ? 1 : 2);
+            const int64_t j = t == 0 ? off0 + e : (t == 1 ? off1 + (e - n0) : off2 + (e - n0 - n1));
+            const double al = t == 0 ? a0 : (t == 1 ? a1 : a2);
+            double x, y, z, vx, vy, vz, m;
+            int64_t id;
+            emit_gather(in, sat, obj_first + lst[e - e0], al, x, y, z, vx, vy, vz, m, id);
+            emit_one(p, o, t, j, x, y, z, vx, vy, vz, m, id);
+        }
+        __syncthreads();
+    }
+}
+
+// totals of a populate without a superblock (empty catalogue)
+__global__ void hod_zero_totals(int64_t *totals) {
+    if (threadIdx.x < 6) totals[threadIdx.x] = 0;
 }
 
 // ---- device RNG for `run_hod(reseed=...)` (hod/abacus_hod.py:775-839) ------------------------------------------------
@@ -1775,8 +1997,17 @@ struct abacus_hod_state {
     int64_t last_cand[2] = {-1, -1};
     bool kept_valid = false;    // the kept lists (superblocks of kept_sb_tiles tiles) name exactly the non-zero mask bytes
     int kept_sb_tiles = 0;
-    int64_t *d_totals = nullptr;  // 6
-    int64_t *h_totals = nullptr;  // pinned, 6
+    // queue-free index path (hod_exact_index / hod_emit_bm): per-tracer kept bitmaps over all objects and superblock counts, two
+    // sets of each alternating by populate parity
+    DevBuf bm, bm_counts;
+    int64_t bm_words = 0;         // words of one tracer's bitmap: (ntile_c + ntile_s) * TILE / 32
+    int bm_cstride = 0;           // ints of one set of counts
+    bool bm_valid = false;        // set bm_par ^ 1 and its counts are zero, and the non-zero keep bytes are the bits of set bm_par
+    int bm_par = 0;               // set of the latest populate of this path
+    bool emit_bm = false;         // the latest populate emits from the bitmaps (re-emission after a capacity growth)
+    int64_t *d_totals = nullptr;  // device scratch (stage_fill)
+    int64_t *h_totals = nullptr;  // 6, page-locked and mapped: hod_emit writes the totals here directly
+    int64_t *h_totals_dev = nullptr;   // its device address
     // outputs
     DevBuf out[3];
     int64_t cap[3] = {0, 0, 0};
@@ -2089,10 +2320,11 @@ void set_superblocks(abacus_hod_state *st, const abacus_hod_params *p) {
     st->nsb_s = count(st->ntile_s);
 }
 
+// the emission of the latest populate; it also writes the six totals into the mapped h_totals (no copy behind it)
 int launch_emit(abacus_hod_state *st) {
     const int nemit = st->nsb_c + st->nsb_s;
     if (nemit == 0) {
-        HIP_TRY(hipMemsetAsync(st->d_totals, 0, 6 * sizeof(int64_t), stream()));
+        ABACUS_LAUNCH("hod_emit", hod_zero_totals, dim3(1), dim3(64), 0, st->h_totals_dev);
         return 0;
     }
     EmitPtrs in;
@@ -2101,6 +2333,16 @@ int launch_emit(abacus_hod_state *st) {
     const bool rec = st->rec_ok && st->rec_rand_ok;
     in.hrec = rec ? st->hrec.as<HaloRec>() : nullptr;
     in.prec = rec ? st->prec.as<PartRec>() : nullptr;
+    if (st->emit_bm) {   // queue-free index path: sparse superblocks, 256 threads
+        const int cur = st->bm_par, prev = cur ^ 1;
+        unsigned int *bm = st->bm.as<unsigned int>();
+        int *cnt = st->bm_counts.as<int>();
+        ABACUS_LAUNCH("hod_emit", (hod_emit_bm<256, SB_TILES_SPARSE>), dim3(nemit), dim3(256), 0, st->nsb_c, st->nsb_s, st->ntile_c,
+                      st->ntile_s, (const unsigned int *)(bm + (int64_t)cur * 3 * st->bm_words), bm + (int64_t)prev * 3 * st->bm_words,
+                      st->bm_words, (const int *)(cnt + (int64_t)cur * st->bm_cstride),
+                      cnt + (int64_t)prev * st->bm_cstride, st->keep_c, st->keep_s, st->h_totals_dev, in, st->params, out_cols(st));
+        return 0;
+    }
     // workgroup size: 384 threads per superblock for the dense mixes (ELG / QSO: a few thousand galaxies per superblock; at
     // its 86 registers three such workgroups fit a CU - all 768 central superblocks of 1e7 halos at once - where only two of
     // 512 threads do: 92 vs 101 us at LRG + ELG + QSO on 1e7 + 1e7, 95 with 256), 256 for LRG alone (12 vs 20 us: the larger
@@ -2109,7 +2351,7 @@ int launch_emit(abacus_hod_state *st) {
     if (eb != 256 && eb != 384 && eb != 512) eb = (st->params.want_ELG || st->params.want_QSO) ? 384 : 256;
 #define EMIT(EB, SBT)                                                                                                       \
     ABACUS_LAUNCH("hod_emit", (hod_emit<EB, SBT>), dim3(nemit), dim3(EB), 0, st->nsb_c, st->nsb_s, st->ntile_c, st->ntile_s, st->kept_c, st->kept_s, \
-                  st->sb_counts, st->d_totals, in, st->params, out_cols(st), option("dbg"))
+                  st->sb_counts, st->h_totals_dev, in, st->params, out_cols(st), option("dbg"))
     const bool sparse = st->sb_tiles == SB_TILES_SPARSE;
     if (eb == 384 && sparse) EMIT(384, SB_TILES_SPARSE);
     else if (eb == 384) EMIT(384, SB_TILES_DENSE);
@@ -2257,6 +2499,41 @@ int build_shadows(abacus_hod_state *st, bool rand_only) {
     return 0;
 }
 
+// queue-free index path: hod_exact_index over the candidate prefixes of the key index, then hod_emit_bm (see there).  Entering
+// it (the first populate, or after any other path) clears the keep masks, both sets of bitmaps and both sets of counts once.
+int populate_bitmaps(abacus_hod_state *st, const abacus_hod_params *p, const SatPre &pre, const HodPtrs &a, const DealTab &deal,
+                     bool was_valid) {
+    if (!was_valid) {
+        const int64_t words = (int64_t)(st->ntile_c + st->ntile_s) * (TILE / 32);
+        const int cstride = (st->nsb_c + st->nsb_s) * BM_CS;
+        ABACUS_TRY(st->bm.reserve((size_t)2 * 3 * words * sizeof(unsigned int)));
+        ABACUS_TRY(st->bm_counts.reserve((size_t)2 * cstride * sizeof(int)));
+        st->bm_words = words, st->bm_cstride = cstride;
+        HIP_TRY(hipMemsetAsync(st->bm.p, 0, (size_t)2 * 3 * words * sizeof(unsigned int), stream()));
+        HIP_TRY(hipMemsetAsync(st->bm_counts.p, 0, (size_t)2 * cstride * sizeof(int), stream()));
+        HIP_TRY(hipMemsetAsync(st->keep_c, 0, (size_t)st->nh, stream()));
+        HIP_TRY(hipMemsetAsync(st->keep_s, 0, (size_t)st->np, stream()));
+    }
+    const int cur = st->bm_par ^ 1;
+    abacus_cls::ClsConst cc;
+    abacus_cls::make_cls_const(*p, pre, cc);
+    const int use_cls = option("hod_nocls") ? 0 : 1;   // A/B: every candidate through the float64 chain
+    const unsigned int *idx = st->index_idx.as<unsigned int>();
+    unsigned int *bm = st->bm.as<unsigned int>() + (int64_t)cur * 3 * st->bm_words;
+    int *cnt = st->bm_counts.as<int>() + (int64_t)cur * st->bm_cstride;
+    const unsigned int total = deal.pre[deal.nseg];
+    if (total > 0)
+        ABACUS_LAUNCH("hod_exact", hod_exact_index, dim3((total + 255u) / 256u), dim3(256), 0, a, idx, idx + st->nh, deal, total, bm,
+                      st->bm_words, cnt, *p, pre, cc, use_cls);
+    st->bm_par = cur;
+    st->emit_bm = true;
+    ABACUS_TRY(launch_emit(st));
+    st->bm_valid = true;
+    st->have_run = true;
+    st->counts_valid = false;
+    return 0;   // kept_valid stays false: this path writes no kept lists; q_count is untouched (q_zero stays as it was)
+}
+
 }  // namespace
 
 __global__ void hod_check_pinds(const int64_t *__restrict__ pinds, int64_t np, int64_t nh, int *__restrict__ flag) {
@@ -2296,11 +2573,12 @@ static int stage_fill(abacus_hod_state *st, const abacus_hod_arrays *a, int on_d
     HIP_TRY(hipMalloc((void **)&st->queue_s, (size_t)(st->ntile_s > 0 ? st->ntile_s : 1) * TILE * sizeof(unsigned short)));
     HIP_TRY(hipMalloc((void **)&st->kept_c, (size_t)(st->ntile_c + SB_TILES_MAX) * TILE * sizeof(unsigned short)));
     HIP_TRY(hipMalloc((void **)&st->kept_s, (size_t)(st->ntile_s + SB_TILES_MAX) * TILE * sizeof(unsigned short)));
-    HIP_TRY(hipHostMalloc((void **)&st->h_totals, 8 * sizeof(int64_t), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **)&st->h_totals, 8 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void **)&st->h_totals_dev, st->h_totals, 0));
     // first guess for the catalog buffers; grown on demand by abacus_hod_counts
     for (int t = 0; t < 3; t++) ABACUS_TRY(set_capacity(st, t, (nh + np) / 64));
     if (st->pinds && st->np > 0) {   // keep_c[pinds[i]] is read unchecked by the kernels: reject a stale / out-of-range index here
-        int *flag = (int *)st->d_totals;   // scratch, rewritten by every populate
+        int *flag = (int *)st->d_totals;   // scratch
         HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), stream()));
         ABACUS_LAUNCH("hod_check_pinds", hod_check_pinds, dim3((unsigned)std::min<int64_t>(ceil_div(st->np, 256), 4096)), dim3(256), 0,
                       st->pinds, st->np, st->nh, flag);
@@ -2439,6 +2717,7 @@ int abacus_hod_populate_nfw(abacus_hod_state *st, const abacus_hod_params *p, co
     memset(&a, 0, sizeof a);
     set_superblocks(st, p);
     st->kept_valid = false;   // the particles' masks and kept lists are left as they are: no lazy masks after this path
+    st->bm_valid = st->emit_bm = false;
     st->q_zero = false, st->last_cand[0] = st->last_cand[1] = -1;
     a.nh = st->nh, a.np = 0, a.ntile_c = st->ntile_c, a.ntile_s = 0, a.nsb_c = st->nsb_c, a.nsb_s = 0;
     a.hmass = st->hmass, a.hmultis = st->hmultis, a.hrandoms = st->hrandoms, a.hdeltac = st->hdeltac,
@@ -2462,7 +2741,6 @@ int abacus_hod_populate_nfw(abacus_hod_state *st, const abacus_hod_params *p, co
             ABACUS_LAUNCH("hod_exact", (hod_exact_plain<256, SB_TILES_DENSE>), dim3(st->nsb_c), dim3(256), 0, a, 0, *p, pre, cc, 1, 0);
     }
     ABACUS_TRY(launch_emit(st));
-    HIP_TRY(hipMemcpyAsync(st->h_totals, st->d_totals, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream()));
     // Poisson satellite numbers per halo and tracer, their exclusive offsets
     const int64_t nh = st->nh;
     ABACUS_TRY(st->nfw_counts.reserve((size_t)(3 * (nh + 1)) * sizeof(unsigned int)));
@@ -2583,17 +2861,24 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
     // lazy keep masks (see hod_exact): only when one key-filter launch covers both kinds, the mix is sparse, and the kept
     // lists of the previous populate describe the masks
     const bool filter_first_ = conf && use32 && cheap.s_ok;
-    const bool lazy_masks = use32 && !option("hod_nokeys") && !option("hod_nolazy") && cheap.c_ok && cheap.s_ok && st->ntile_c > 0 &&
-                            st->ntile_s > 0 && (!conf || filter_first_) && st->sb_tiles == SB_TILES_SPARSE && st->kept_valid &&
-                            st->kept_sb_tiles == st->sb_tiles;
+    const bool lazy_ok = use32 && !option("hod_nokeys") && !option("hod_nolazy") && cheap.c_ok && cheap.s_ok && st->ntile_c > 0 &&
+                         st->ntile_s > 0 && (!conf || filter_first_) && st->sb_tiles == SB_TILES_SPARSE;
+    const bool lazy_masks = lazy_ok && st->kept_valid && st->kept_sb_tiles == st->sb_tiles;
     st->kept_valid = false;   // until this populate's launches are all enqueued
-    // mass-sorted key index (see hod_deal): from the second populate on the same keys, for the mixes that run lazy masks
+    // the index path without queues (hod_exact_index -> hod_emit_bm) - except where the satellites read keep_cent[pinds], which
+    // holds the previous populate's bytes until hod_emit_bm: then, and with `hod_deal` = 1 (the A/B comparator), the index
+    // path is hod_deal -> hod_exact -> hod_emit
+    const bool bm_path = !option("hod_deal") && !conf;
+    const bool bm_was_valid = st->bm_valid;
+    st->bm_valid = st->emit_bm = false;   // until a populate of the queue-free path is enqueued
+    // mass-sorted key index (see hod_deal): from the second populate on the same keys, for the mixes that run lazy masks (the
+    // queue-free path keeps its own record of the masks: it only needs the mix to qualify)
     bool index_mode = false;
     DealTab deal;
     if (use32 && st->sb_tiles == SB_TILES_SPARSE && !option("hod_noindex") && !option("hod_nokeys")) {
         st->key_uses++;
         if (!st->index_ok && st->key_uses >= 2) ABACUS_TRY(build_index(st));
-        if (st->index_ok && lazy_masks) {
+        if (st->index_ok && (bm_path ? lazy_ok : lazy_masks)) {
             unsigned int pre = 0;
             deal.nseg = 0;
             int64_t cand[2] = {0, 0};
@@ -2618,6 +2903,7 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
         }
     }
     if (!index_mode) st->last_cand[0] = st->last_cand[1] = -1;
+    if (index_mode && bm_path) return populate_bitmaps(st, p, pre, a, deal, bm_was_valid);
     const int exact_flags = (lazy_masks ? 1 : 0) | (index_mode ? 2 : 0);
     // `first`, `count` in global tile ids (centrals first): the shadow path launches the two kinds separately
     auto filter32 = [&](int first, int count) -> int {
@@ -2726,9 +3012,9 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
 #undef FILTER
 #undef EXACT
 #undef EXACT_
-    // speculative emission into the current buffers (writes past capacity are suppressed on the device)
+    // speculative emission into the current buffers (writes past capacity are suppressed on the device); its totals land in
+    // the mapped h_totals
     ABACUS_TRY(launch_emit(st));
-    HIP_TRY(hipMemcpyAsync(st->h_totals, st->d_totals, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream()));
     st->have_run = true;
     st->counts_valid = false;
     st->kept_valid = true, st->kept_sb_tiles = st->sb_tiles;   // every mask byte that is set is in a kept list
@@ -2859,6 +3145,7 @@ int abacus_hod_free(abacus_hod_state *st) {
     (void)st->keys.release();
     (void)st->index_idx.release(), (void)st->index_scratch.release(), (void)st->index_tmp.release(), (void)st->index_last.release();
     (void)st->hrec.release(), (void)st->prec.release();
+    (void)st->bm.release(), (void)st->bm_counts.release();
     delete st;
     return 0;
 }
