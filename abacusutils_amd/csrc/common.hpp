@@ -48,6 +48,8 @@ std::recursive_mutex &api_mutex();
 // Diagnostic options (abacus_set_option, include/abacus_hip.h): comparator paths the parity tests and the A/B scripts
 // switch on explicitly - nothing in the library reads the environment.  0 when never set.
 int option(const char *name);
+// bumped by every abacus_set_option: a hot path may keep the options it reads in a snapshot taken at this version
+unsigned int option_version();
 
 // profiler hooks: no-ops unless abacus_profile_enable(1)
 void prof_begin(const char *name);

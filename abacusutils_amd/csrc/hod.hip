@@ -15,11 +15,12 @@
 //        (float64 columns of caller-owned catalogues, float32 shadow columns).
 //   hod_exact_index LRG alone, from the second populate on: the candidates are prefixes of the sorted key index, found on
 //        the host without reading a key (DealTab).  One candidate per lane: index, record line, the classifier below; a kept
-//        object sets its keep byte, a bit of this populate's per-tracer kept bitmap and its superblock's count (non-returning
-//        atomics).  Profiled as hod_exact.
-//   hod_emit_bm     its emission: one workgroup per superblock ranks the rows by a popcount scan of the bitmap words, gathers
-//        and writes them as hod_emit does; it also un-keeps the objects the previous populate kept and this one did not and
-//        zeroes the previous populate's bitmaps and counts (two sets, alternating by populate parity).  Profiled as hod_emit.
+//        object sets its keep byte and a bit of this populate's per-tracer kept bitmap (non-returning atomics), nothing else.
+//        Profiled as hod_exact.
+//   hod_emit_bm     its emission: per superblock, a popcount scan of the bitmap words ranks the rows and a decoupled look-back
+//        over the superblocks' popcount totals gives the output offsets; gathers and writes the rows as hod_emit does; it
+//        also un-keeps the objects the previous populate kept and this one did not and zeroes the previous populate's bitmaps
+//        (two sets, alternating by populate parity).  Profiled as hod_emit.
 //   hod_deal        the comparator of that path (option hod_deal = 1): hands the candidates' indices to the tile queues
 //        that hod_exact walks.
 //   hod_exact       one workgroup per superblock (16 tiles for LRG alone, 8 for mixes with ELG / QSO): a float32 interval
@@ -1206,20 +1207,16 @@ __global__ __launch_bounds__(XB) __attribute__((amdgpu_waves_per_eu(4))) void ho
     hod_exact_body<XB, false, SBT>(a, first_sb, p, pre, cc, use_cls, clear_prev);
 }
 
-// ints per superblock in the counts of the queue-free path: a 128-B line each.  Their ~180 increments per populate are
-// serialised per line where device-scope atomics execute; four superblocks to a line (the layout of sb_counts) made
-// hod_exact_index 25 us instead of 16 at 1e7 + 1e7.
-constexpr int BM_CS = 32;
 // Index path without queues (sparse mixes, unchanged keys; `hod_deal` = 1 restores hod_deal -> hod_exact -> hod_emit): one
 // candidate per lane, straight from the mass-sorted index.  Candidate j lies in the DealTab segment with pre <= j (binary
 // search in LDS), its object index is one coalesced 4-B load and its record line the only gather; it is settled by the same
 // classifier and float64 chains as in hod_exact.  A kept object sets its keep byte, one bit in this populate's bitmap of its
-// tracer (centrals' words first, then the satellites', bit = object index) and adds one to its superblock's count - all
-// three non-returning: no atomic result sits on a dependency chain.  hod_emit_bm reads its rows off the bitmaps.  No ELG
+// tracer (centrals' words first, then the satellites', bit = object index) - both non-returning: no atomic result sits on a
+// dependency chain, and nothing is counted (hod_emit_bm popcounts the bitmaps).  No ELG
 // conformity here: keep_cent holds the previous populate's bytes until hod_emit_bm (the host takes hod_deal for such mixes).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void hod_exact_index(
     HodPtrs a, const unsigned int *__restrict__ idx_h, const unsigned int *__restrict__ idx_p, DealTab tab, unsigned int ncand,
-    unsigned int *__restrict__ bm, int64_t bm_words, int *__restrict__ counts, abacus_hod_params p, SatPre pre,
+    unsigned int *__restrict__ bm, int64_t bm_words, abacus_hod_params p, SatPre pre,
     abacus_cls::ClsConst cc, int use_cls) {
     __shared__ unsigned int s_pre[257], s_start[256];
     __shared__ abacus_hod_params s_p;     // read by the out-of-line float64 chains
@@ -1257,10 +1254,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void h
     (sat ? a.keep_s : a.keep_c)[i] = (int8_t)kk;
     const int64_t o = (sat ? (int64_t)a.ntile_c * TILE : 0) + i;
     atomicOr(bm + (int64_t)(kk - 1) * bm_words + (o >> 5), 1u << (o & 31));
-    // superblock S owns the tiles [S ntile / nsb, (S + 1) ntile / nsb) (sb_first_tile): the largest S with S ntile / nsb <= tile
-    const int tile = (int)(i / TILE), ntile = sat ? a.ntile_s : a.ntile_c, nsb = sat ? a.nsb_s : a.nsb_c;
-    const int S = (int)(((int64_t)(tile + 1) * nsb - 1) / ntile);
-    atomicAdd(counts + (int64_t)((sat ? a.nsb_c : 0) + S) * BM_CS + (kk - 1), 1);
 }
 
 struct OutCols {
@@ -1529,125 +1522,266 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
 // Emission of the queue-free index path (hod_exact_index): one workgroup per superblock, rows found in the bitmaps.  Thread t
 // owns words [4t, 4t + 4) of the superblock's 1024 words per tracer (coalesced 16-B loads); a packed 3 x 21-bit popcount scan
 // ranks its bits, and the ranks go through an LDS list (EMIT_WIN rows at a time) so that every lane gathers about the same
-// number of rows.  Two sets of bitmaps and counts alternate by populate parity: the workgroup also un-keeps the objects set in
-// the previous populate's bitmaps and clear in this one's (the only non-zero keep bytes outside this populate's bitmaps),
-// then zeroes its words and counts of the previous set, which nobody reads any more - the next populate starts from a clean
-// set, and a re-emission of this populate (abacus_hod_counts after a capacity growth) finds its own set intact.  The ELG / QSO
-// words are read only where the superblock's count of the set says it kept some (LRG's always: no wait on the counts).
+// number of rows.  Two sets of bitmaps alternate by populate parity: the workgroup also un-keeps the objects set in the
+// previous populate's bitmaps and clear in this one's (the only non-zero keep bytes outside this populate's bitmaps), then
+// zeroes its words of the previous set, which nobody reads any more - the next populate starts from a clean set, and a
+// re-emission of this populate (abacus_hod_counts after a capacity growth) finds its own set intact.  Tracer t's words of a
+// set are read only where bit t of that set's mask is on (the mix's want flags; LRG always: a random of exactly 0 keeps it).
+//
+// Output offsets: single-pass decoupled look-back over the superblocks in one chained order, the centrals' then the
+// satellites': the exclusive prefix a satellite superblock sees already holds Ncent, so centrals || satellites land
+// concatenated.  A superblock's aggregate is its popcount total; wave t publishes tracer t's as one 8-B status word
+// [tag | inclusive | value] (LB_*), written whole by one agent-scope atomic store and polled by agent-scope atomic loads
+// (past the CU's L1): tag, flag and value are never seen apart.  The tag is the launch's epoch, so no word needs resetting
+// between launches.  The look-back reads LB_WIN predecessors per pass, sums the aggregates back to the nearest inclusive
+// value and publishes its own.  A superblock waits only on smaller ones, and the host caps the grid at what the GPU holds at
+// once (workgroup g then takes superblocks g, g + grid, ... in order): every wait is on a running workgroup.  A per-launch
+// ticket would not need the cap, but its 612 returning atomics on one counter made this kernel 27.7 us instead of 15.6 at
+// 1e7 + 1e7.  Every poll is bounded: a wait given up sets totals[6] (the host fails the populate) and the chain goes on.
+// The last superblock writes the six totals into the mapped host buffer.
 constexpr int EMIT_WIN = 2048;
+constexpr int LB_VBITS = 34, LB_TAG_SHIFT = LB_VBITS + 1;   // value [0, 34), inclusive flag 34, tag [35, 64)
+constexpr unsigned long long LB_VMASK = (1ull << LB_VBITS) - 1, LB_INCL = 1ull << LB_VBITS;
+constexpr unsigned int LB_TAG_MAX = (1u << (64 - LB_TAG_SHIFT)) - 1;
+constexpr int LB_PER_LANE = 8, LB_WIN = 64 * LB_PER_LANE;   // predecessors per look-back pass: 612 superblocks at 1e7 + 1e7
+constexpr int LB_SPIN = 1 << 20;                            // polls of one word before a wait is given up (~1 s)
+typedef __attribute__((address_space(1))) unsigned long long gu64_t;
+
+__device__ __forceinline__ unsigned long long lb_load(const unsigned long long *w) {
+    return __hip_atomic_load((gu64_t *)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void lb_store(unsigned long long *w, unsigned long long v) {
+    __hip_atomic_store((gu64_t *)w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// wave-wide look-back of one tracer for logical superblock g: the exclusive prefix of its aggregates.  `st` = the tracer's
+// status words; uniform in the wave
+__device__ __forceinline__ unsigned long long lb_exclusive(const unsigned long long *st, int g, unsigned long long tg,
+                                                           int lane, bool &failed) {
+    unsigned long long excl = 0;
+    for (int end = g; end > 0;) {   // predecessors [end - LB_WIN, end): word r of lane l is end - LB_WIN + 64 r + l
+        const int first = end - LB_WIN + lane;   // each load instruction of the wave reads 64 consecutive words (4 lines)
+        unsigned long long w[LB_PER_LANE];
+        for (int spins = 0;; spins++) {
+            bool ready = true;
+#pragma unroll
+            for (int r = 0; r < LB_PER_LANE; r++) {
+                const int q = first + 64 * r;
+                const unsigned long long x = lb_load(st + max(q, 0));   // straight-line: no branch per word
+                w[r] = q >= 0 ? x : (tg | LB_INCL);                     // before superblock 0: inclusive 0
+                ready = ready && (w[r] & ~(LB_INCL | LB_VMASK)) == tg;
+            }
+            if (__all(ready)) break;
+            if (spins >= LB_SPIN) {   // uniform: give up, the host reports it
+                failed = true;
+#pragma unroll
+                for (int r = 0; r < LB_PER_LANE; r++) w[r] = tg | LB_INCL;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        // the nearest inclusive value ends the sum: the highest position 64 r + l whose word carries the flag
+        int hi = -1;
+#pragma unroll
+        for (int r = LB_PER_LANE - 1; r >= 0; r--) {
+            const unsigned long long b = __ballot((w[r] & LB_INCL) != 0);
+            if (hi < 0 && b) hi = 64 * r + 63 - __clzll(b);
+        }
+        unsigned long long s = 0;
+#pragma unroll
+        for (int r = 0; r < LB_PER_LANE; r++)
+            if (64 * r + lane >= hi) s += w[r] & LB_VMASK;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        excl += s;
+        if (hi >= 0) break;
+        end -= LB_WIN;
+    }
+    return excl;
+}
+
 template <int EBLOCK, int SBT>
 __global__ __launch_bounds__(EBLOCK) void hod_emit_bm(int nsb_c, int nsb_s, int ntile_c, int ntile_s,
                                                       const unsigned int *__restrict__ bm_cur, unsigned int *__restrict__ bm_prev,
-                                                      int64_t bm_words,
-                                                      const int *__restrict__ sb_counts, int *__restrict__ sb_prev,
+                                                      int64_t bm_words, int mask_cur, int mask_prev,
+                                                      unsigned long long *lb_status, unsigned int tag,
                                                       int8_t *__restrict__ keep_c, int8_t *__restrict__ keep_s,
                                                       int64_t *__restrict__ totals, EmitPtrs in, abacus_hod_params p, OutCols o_arg) {
     constexpr int WPT = 4;
     static_assert(SBT * TILE / 32 == WPT * EBLOCK, "one 16-B load per thread and tracer");
-    __shared__ int64_t red[EBLOCK / 64][6];
+    static_assert(EBLOCK >= 192, "waves 0..2 run the look-backs of the three tracers");
     __shared__ OutCols o;   // see hod_emit
     __shared__ unsigned long long wave_tot[EBLOCK / 64];
     __shared__ unsigned short lst[EMIT_WIN];
+    __shared__ int64_t s_off[3];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nemit = nsb_c + nsb_s;
     if (tid < (int)(sizeof(OutCols) / 8))
         reinterpret_cast<unsigned long long *>(&o)[tid] = reinterpret_cast<const unsigned long long *>(&o_arg)[tid];
-    const int g = blockIdx.x;
-    const bool sat = g >= nsb_c;
-    const int S = sat ? g - nsb_c : g;
-    const int ntile = sat ? ntile_s : ntile_c, nsb = sat ? nsb_s : nsb_c;
-    const int tile_first = sb_first_tile(S, ntile, nsb), ntl = sb_first_tile(S + 1, ntile, nsb) - tile_first;   // <= SBT
-    const int64_t obj_first = (int64_t)tile_first * TILE;
-    // the superblock's counts of both sets, then its bitmap words: their loads overlap the offset sums
-    int m[3], pm[3];
-#pragma unroll
-    for (int t = 0; t < 3; t++) m[t] = sb_counts[(int64_t)g * BM_CS + t], pm[t] = sb_prev[(int64_t)g * BM_CS + t];
-    const bool mine = tid * WPT * 32 < ntl * TILE;
-    const int64_t w0 = ((sat ? (int64_t)ntile_c * TILE : 0) + obj_first) / 32 + tid * WPT;
-    unsigned int cur[3][WPT], prv[3][WPT];
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        uint4 c = make_uint4(0u, 0u, 0u, 0u), q = make_uint4(0u, 0u, 0u, 0u);
-        if (mine && (t == 0 || m[t] > 0)) c = *reinterpret_cast<const uint4 *>(bm_cur + t * bm_words + w0);
-        if (mine && (t == 0 || pm[t] > 0)) q = *reinterpret_cast<const uint4 *>(bm_prev + t * bm_words + w0);
-        cur[t][0] = c.x, cur[t][1] = c.y, cur[t][2] = c.z, cur[t][3] = c.w;
-        prv[t][0] = q.x, prv[t][1] = q.y, prv[t][2] = q.z, prv[t][3] = q.w;
-    }
-    int64_t v[6];
-    emit_offsets<EBLOCK, BM_CS>(g, sat, S, nsb_c, nsb_s, sb_counts, totals, red, v);
-    if (mine) {
-        int8_t *keep = (sat ? keep_s : keep_c) + obj_first + tid * WPT * 32;
-#pragma unroll
-        for (int w = 0; w < WPT; w++) {
-            unsigned int gone = (prv[0][w] | prv[1][w] | prv[2][w]) & ~(cur[0][w] | cur[1][w] | cur[2][w]);
-            while (gone) {
-                const int b = __ffs((int)gone) - 1;
-                gone &= gone - 1;
-                keep[w * 32 + b] = 0;
-            }
-        }
+    const unsigned long long tg = (unsigned long long)tag << LB_TAG_SHIFT;
+    // the grid is co-resident (the host caps it at what the GPU holds at once): superblock g, g + gridDim.x, ... in order.
+    // The aggregates of the superblocks after the first are published up front, so that no look-back waits for a
+    // workgroup to come round to one of them (4e7 + 4e7: 0.090 instead of 0.080 ms per step without this)
+    for (int g = blockIdx.x + gridDim.x; g < nemit; g += gridDim.x) {
+        const bool sat = g >= nsb_c;
+        const int S = sat ? g - nsb_c : g;
+        const int ntile = sat ? ntile_s : ntile_c, nsb = sat ? nsb_s : nsb_c;
+        const int tile_first = sb_first_tile(S, ntile, nsb), ntl = sb_first_tile(S + 1, ntile, nsb) - tile_first;
+        const bool mine = tid * WPT * 32 < ntl * TILE;
+        const int64_t w0 = ((sat ? (int64_t)ntile_c * TILE : 0) + (int64_t)tile_first * TILE) / 32 + tid * WPT;
+        unsigned long long c = 0;
 #pragma unroll
         for (int t = 0; t < 3; t++)
-            if (pm[t] > 0) *reinterpret_cast<uint4 *>(bm_prev + t * bm_words + w0) = make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (tid < 3) sb_prev[(int64_t)g * BM_CS + tid] = 0;   // every thread read them before the barriers of emit_offsets
-    if (m[0] + m[1] + m[2] == 0) return;   // uniform
-    // ranks: packed 3 x 21-bit exclusive scan of the threads' popcounts (tracer-major, index order inside a tracer)
-    unsigned long long mine_c = 0;
+            if (mine && (mask_cur >> t & 1)) {
+                const uint4 q = *reinterpret_cast<const uint4 *>(bm_cur + t * bm_words + w0);
+                c |= (unsigned long long)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w)) << (21 * t);
+            }
 #pragma unroll
-    for (int t = 0; t < 3; t++) {
-        unsigned int c = 0;
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+        if (lane == 0) wave_tot[wv] = c;
+        __syncthreads();
+        unsigned long long all = 0;
 #pragma unroll
-        for (int w = 0; w < WPT; w++) c += __popc(cur[t][w]);
-        mine_c |= (unsigned long long)c << (21 * t);
+        for (int w = 0; w < EBLOCK / 64; w++) all += wave_tot[w];
+        if (wv < 3 && lane == 0 && (mask_cur >> wv & 1)) lb_store(lb_status + (int64_t)wv * nemit + g, tg | ((all >> (21 * wv)) & 0x1fffff));
+        __syncthreads();
     }
-    unsigned long long incl = mine_c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long u = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += u;
-    }
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < EBLOCK / 64; w++) {
-        if (w < wv) before += wave_tot[w];
-        all += wave_tot[w];
-    }
-    const unsigned long long excl = before + incl - mine_c;
-    // the list holds exactly the bits (equal to the counts: each kept object set one bit and added one)
-    const int n0 = (int)(all & 0x1fffff), n1 = (int)((all >> 21) & 0x1fffff), nall = n0 + n1 + (int)((all >> 42) & 0x1fffff);
-    const int base[3] = {0, n0, n0 + n1};
-    const int64_t off0 = v[0] + (sat ? v[3] : 0), off1 = v[1] + (sat ? v[4] : 0), off2 = v[2] + (sat ? v[5] : 0);
-    const double a0 = sat ? p.L_alpha_s : p.L_alpha_c, a1 = sat ? p.E_alpha_s : p.E_alpha_c,
-                 a2 = sat ? p.Q_alpha_s : p.Q_alpha_c;
-    for (int e0 = 0; e0 < nall; e0 += EMIT_WIN) {   // uniform
-        const int e1 = min(nall, e0 + EMIT_WIN);
+    for (int g = blockIdx.x; g < nemit; g += gridDim.x) {
+        __syncthreads();   // the OutCols copy; the LDS of the previous superblock
+        const bool sat = g >= nsb_c;
+        const int S = sat ? g - nsb_c : g;
+        const int ntile = sat ? ntile_s : ntile_c, nsb = sat ? nsb_s : nsb_c;
+        const int tile_first = sb_first_tile(S, ntile, nsb), ntl = sb_first_tile(S + 1, ntile, nsb) - tile_first;   // <= SBT
+        const int64_t obj_first = (int64_t)tile_first * TILE;
+        const bool mine = tid * WPT * 32 < ntl * TILE;
+        const int64_t w0 = ((sat ? (int64_t)ntile_c * TILE : 0) + obj_first) / 32 + tid * WPT;
+        unsigned int cur[3][WPT], prv[3][WPT];
 #pragma unroll
         for (int t = 0; t < 3; t++) {
-            int r = base[t] + (int)((excl >> (21 * t)) & 0x1fffff);
+            uint4 c = make_uint4(0u, 0u, 0u, 0u), q = make_uint4(0u, 0u, 0u, 0u);
+            if (mine && (mask_cur >> t & 1)) c = *reinterpret_cast<const uint4 *>(bm_cur + t * bm_words + w0);
+            if (mine && (mask_prev >> t & 1)) q = *reinterpret_cast<const uint4 *>(bm_prev + t * bm_words + w0);
+            cur[t][0] = c.x, cur[t][1] = c.y, cur[t][2] = c.z, cur[t][3] = c.w;
+            prv[t][0] = q.x, prv[t][1] = q.y, prv[t][2] = q.z, prv[t][3] = q.w;
+        }
+        // ranks: packed 3 x 21-bit exclusive scan of the threads' popcounts (tracer-major, index order inside a tracer)
+        unsigned long long mine_c = 0;
 #pragma unroll
-            for (int w = 0; w < WPT; w++) {
-                unsigned int bits = cur[t][w];
-                while (bits && r < e1) {
-                    const int b = __ffs((int)bits) - 1;
-                    bits &= bits - 1;
-                    if (r >= e0) lst[r - e0] = (unsigned short)((tid * WPT + w) * 32 + b);
-                    r++;
+        for (int t = 0; t < 3; t++) {
+            unsigned int c = 0;
+#pragma unroll
+            for (int w = 0; w < WPT; w++) c += __popc(cur[t][w]);
+            mine_c |= (unsigned long long)c << (21 * t);
+        }
+        unsigned long long incl = mine_c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long u = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += u;
+        }
+        if (lane == 63) wave_tot[wv] = incl;
+        __syncthreads();
+        unsigned long long before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < EBLOCK / 64; w++) {
+            if (w < wv) before += wave_tot[w];
+            all += wave_tot[w];
+        }
+        const unsigned long long excl = before + incl - mine_c;
+        if (wv < 3) {   // wave t: tracer t's look-back (uniform in the wave)
+            const int t = wv;
+            const unsigned long long agg = (all >> (21 * t)) & 0x1fffff;
+            unsigned long long pre = 0, tot = agg;
+            bool failed = false;
+            if (mask_cur >> t & 1) {
+                unsigned long long *st = lb_status + (int64_t)t * nemit;
+                if (g == 0) {
+                    if (lane == 0) lb_store(st, tg | LB_INCL | agg);
+                } else {
+                    // aggregate first (the later superblocks' went out above): successors need not wait for the look-back
+                    if (lane == 0 && g == (int)blockIdx.x) lb_store(st + g, tg | agg);
+                    pre = lb_exclusive(st, g, tg, lane, failed);
+                    if (lane == 0) lb_store(st + g, tg | LB_INCL | ((pre + agg) & LB_VMASK));
                 }
+                tot = pre + agg;
+                if (g == nemit - 1) {   // the last superblock: Ncent = the inclusive value of the last central superblock
+                    unsigned long long nc = tot;
+                    if (nsb_s > 0 && nsb_c == 0) nc = 0;
+                    else if (nsb_s > 0) {
+                        for (int spins = 0;; spins++) {
+                            const unsigned long long w = lb_load(st + nsb_c - 1);
+                            if ((w & ~LB_VMASK) == (tg | LB_INCL)) {
+                                nc = w & LB_VMASK;
+                                break;
+                            }
+                            if (spins >= LB_SPIN) {
+                                failed = true, nc = 0;
+                                break;
+                            }
+                            __builtin_amdgcn_s_sleep(2);
+                        }
+                    }
+                    if (lane == 0) totals[t] = (int64_t)nc, totals[3 + t] = (int64_t)(tot - nc);
+                }
+            } else if (g == nemit - 1 && lane == 0) {
+                totals[t] = 0, totals[3 + t] = 0;
+            }
+            if (lane == 0) {
+                s_off[t] = (int64_t)pre;
+                if (failed) totals[6] = 1;
             }
         }
-        __syncthreads();
-        for (int e = e0 + tid; e < e1; e += EBLOCK) {
-            const int t = e < n0 ? 0 : (e < n0 + n1 ? 1 : 2);
-            const int64_t j = t == 0 ? off0 + e : (t == 1 ? off1 + (e - n0) : off2 + (e - n0 - n1));
-            const double al = t == 0 ? a0 : (t == 1 ? a1 : a2);
-            double x, y, z, vx, vy, vz, m;
-            int64_t id;
-            emit_gather(in, sat, obj_first + lst[e - e0], al, x, y, z, vx, vy, vz, m, id);
-            emit_one(p, o, t, j, x, y, z, vx, vy, vz, m, id);
+        if (mine) {
+            int8_t *keep = (sat ? keep_s : keep_c) + obj_first + tid * WPT * 32;
+#pragma unroll
+            for (int w = 0; w < WPT; w++) {
+                unsigned int gone = (prv[0][w] | prv[1][w] | prv[2][w]) & ~(cur[0][w] | cur[1][w] | cur[2][w]);
+                while (gone) {
+                    const int b = __ffs((int)gone) - 1;
+                    gone &= gone - 1;
+                    keep[w * 32 + b] = 0;
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 3; t++)
+                if (mask_prev >> t & 1) *reinterpret_cast<uint4 *>(bm_prev + t * bm_words + w0) = make_uint4(0u, 0u, 0u, 0u);
         }
         __syncthreads();
+        // the list holds exactly the bits
+        const int n0 = (int)(all & 0x1fffff), n1 = (int)((all >> 21) & 0x1fffff), nall = n0 + n1 + (int)((all >> 42) & 0x1fffff);
+        if (nall == 0) continue;   // uniform
+        const int base[3] = {0, n0, n0 + n1};
+        const int64_t off0 = s_off[0], off1 = s_off[1], off2 = s_off[2];
+        const double a0 = sat ? p.L_alpha_s : p.L_alpha_c, a1 = sat ? p.E_alpha_s : p.E_alpha_c,
+                     a2 = sat ? p.Q_alpha_s : p.Q_alpha_c;
+        for (int e0 = 0; e0 < nall; e0 += EMIT_WIN) {   // uniform
+            const int e1 = min(nall, e0 + EMIT_WIN);
+#pragma unroll
+            for (int t = 0; t < 3; t++) {
+                int r = base[t] + (int)((excl >> (21 * t)) & 0x1fffff);
+#pragma unroll
+                for (int w = 0; w < WPT; w++) {
+                    unsigned int bits = cur[t][w];
+                    while (bits && r < e1) {
+                        const int b = __ffs((int)bits) - 1;
+                        bits &= bits - 1;
+                        if (r >= e0) lst[r - e0] = (unsigned short)((tid * WPT + w) * 32 + b);
+                        r++;
+                    }
+                }
+            }
+            __syncthreads();
+            for (int e = e0 + tid; e < e1; e += EBLOCK) {
+                const int t = e < n0 ? 0 : (e < n0 + n1 ? 1 : 2);
+                const int64_t j = t == 0 ? off0 + e : (t == 1 ? off1 + (e - n0) : off2 + (e - n0 - n1));
+                const double al = t == 0 ? a0 : (t == 1 ? a1 : a2);
+                double x, y, z, vx, vy, vz, m;
+                int64_t id;
+                emit_gather(in, sat, obj_first + lst[e - e0], al, x, y, z, vx, vy, vz, m, id);
+                emit_one(p, o, t, j, x, y, z, vx, vy, vz, m, id);
+            }
+            __syncthreads();
+        }
     }
 }
 
@@ -1997,13 +2131,16 @@ struct abacus_hod_state {
     int64_t last_cand[2] = {-1, -1};
     bool kept_valid = false;    // the kept lists (superblocks of kept_sb_tiles tiles) name exactly the non-zero mask bytes
     int kept_sb_tiles = 0;
-    // queue-free index path (hod_exact_index / hod_emit_bm): per-tracer kept bitmaps over all objects and superblock counts, two
-    // sets of each alternating by populate parity
-    DevBuf bm, bm_counts;
+    // queue-free index path (hod_exact_index / hod_emit_bm): per-tracer kept bitmaps over all objects, two sets alternating by
+    // populate parity, and the look-back words of the emission
+    DevBuf bm;
     int64_t bm_words = 0;         // words of one tracer's bitmap: (ntile_c + ntile_s) * TILE / 32
-    int bm_cstride = 0;           // ints of one set of counts
-    bool bm_valid = false;        // set bm_par ^ 1 and its counts are zero, and the non-zero keep bytes are the bits of set bm_par
+    bool bm_valid = false;        // set bm_par ^ 1 is zero, and the non-zero keep bytes are the bits of set bm_par
     int bm_par = 0;               // set of the latest populate of this path
+    int bm_mask[2] = {0, 0};      // per set: the tracers whose words may hold bits (bit t; 0: the set is known to be zero)
+    DevBuf lb;                    // [3][lb_n] status words of hod_emit_bm
+    int lb_n = 0;                 // superblocks the status words are laid out for
+    unsigned int lb_tag = 0;      // tag of the latest emission; the words hold smaller tags (or 0)
     bool emit_bm = false;         // the latest populate emits from the bitmaps (re-emission after a capacity growth)
     int64_t *d_totals = nullptr;  // device scratch (stage_fill)
     int64_t *h_totals = nullptr;  // 6, page-locked and mapped: hod_emit writes the totals here directly
@@ -2028,6 +2165,26 @@ struct abacus_hod_state {
 
 namespace {
 
+
+// the diagnostic options a populate reads, re-read only when one has been set since (option_version): a lookup takes the API
+// mutex and builds a std::string, about a dozen of them per populate.  Callers hold the API mutex.
+struct HodOpts {
+    int sbtiles, nobalance, norec, one_stage, f64filter, nokeys, nolazy, deal, noindex, nocls, pipe, eblock, dbg;
+};
+const HodOpts &hod_opts() {
+    static HodOpts o;
+    static unsigned int seen = 0;
+    static bool have = false;
+    const unsigned int v = option_version();
+    if (!have || v != seen) {
+        o.sbtiles = option("hod_sbtiles"), o.nobalance = option("hod_nobalance"), o.norec = option("hod_norec");
+        o.one_stage = option("hod_one_stage"), o.f64filter = option("hod_f64filter"), o.nokeys = option("hod_nokeys");
+        o.nolazy = option("hod_nolazy"), o.deal = option("hod_deal"), o.noindex = option("hod_noindex");
+        o.nocls = option("hod_nocls"), o.pipe = option("hod_pipe"), o.eblock = option("hod_eblock"), o.dbg = option("dbg");
+        seen = v, have = true;
+    }
+    return o;
+}
 
 // host side of the float32 rejection filter: constants rounded so that every bound stays an upper bound
 Filt make_filter(const abacus_hod_params &p, const SatPre &pre) {
@@ -2109,7 +2266,7 @@ inline void prod_range(double c, const ColRange &r, double &lo, double &hi) {   
 Cheap make_cheap(const abacus_hod_params &p, const Filt &F, const HodRanges &R) {
     Cheap c;
     memset(&c, 0, sizeof c);
-    const bool one_stage = option("hod_one_stage") != 0;
+    const bool one_stage = hod_opts().one_stage != 0;
     c.c_ok = F.cent_ok && (p.want_LRG || p.want_ELG || p.want_QSO) && !one_stage;
     c.s_ok = F.sat_basic && (p.want_LRG || p.want_ELG || p.want_QSO) && !one_stage;
     auto up = [](double v) { return std::max((float)(v * 1.00001), 1e-30f); };
@@ -2149,21 +2306,43 @@ Cheap make_cheap(const abacus_hod_params &p, const Filt &F, const HodRanges &R) 
     c.dec_max = (float)(dec * 1.0001);
     auto half_erfc = [](double lM, double lc, double sigma) { return 0.5 * std::erfc((lc - lM) / (1.41421356 * sigma)); };
     auto powa = [](double x, double a) { return a == 1.0 ? x : std::pow(x, a); };
-    // ((M - kappa M_cut') / M1')^alpha at its largest: smallest kappa * 10^lc and smallest 10^l1 of the ranges
-    auto plaw = [&](double M, double kappa, const LR &lc, const LR &l1, double alpha) {
-        const double kM = std::min(kappa * std::pow(10.0, lc.lo), kappa * std::pow(10.0, lc.hi));
-        const double x = M - kM;
-        return x < 0 ? 0.0 : powa(x / std::pow(10.0, l1.lo), alpha);
+    // ((M - kappa M_cut') / M1')^alpha at its largest: smallest kappa * 10^lc and smallest 10^l1 of the ranges.  The two
+    // mass-independent factors are evaluated once per call, not per level (their pow() calls were most of this function)
+    struct PL {
+        double kM, M1, alpha;
     };
+    auto plaw_of = [](double kappa, const LR &lc, const LR &l1, double alpha) {
+        return PL{std::min(kappa * std::pow(10.0, lc.lo), kappa * std::pow(10.0, lc.hi)), std::pow(10.0, l1.lo), alpha};
+    };
+    auto plaw = [&](double M, const PL &f) {
+        const double x = M - f.kM;
+        return x < 0 ? 0.0 : powa(x / f.M1, f.alpha);
+    };
+    const PL pL = plaw_of(p.L_kappa, Lc_p, L1, p.L_alpha), pE = plaw_of(p.E_kappa, Ec_p, E1, p.E_alpha),
+             pEL = plaw_of(p.E_kappa, Ec_p, E1L, p.E_alpha_EL), pEE = plaw_of(p.E_kappa, Ec_p, E1E, p.E_alpha_EE),
+             pQ = plaw_of(p.Q_kappa, Qc_p, Q1, p.Q_alpha);
+    // upper edges of the bins and their log10: constants of the binning, evaluated once per process
+    struct Edges {
+        double T[CH_NLEV], lM[CH_NLEV];
+    };
+    static const Edges edges = [] {
+        Edges e;
+        for (int j = 0; j < CH_NLEV; j++) {
+            const uint32_t bits = (uint32_t)(CH_BASE + j + 1) << CH_SHIFT;   // upper edge of bin j (exclusive)
+            float Tf;
+            memcpy(&Tf, &bits, 4);
+            e.T[j] = (double)Tf, e.lM[j] = std::log10(e.T[j]);
+        }
+        return e;
+    }();
+    // without an environment term the LRG centrals and satellites share logM_cut': one erfc per level serves both
+    const bool L_same = Lc_h.lo == Lc_p.lo;
     double lM_prev = -INFINITY;   // bin 0 also takes every smaller mass
     for (int j = 0; j < CH_NLEV; j++) {
-        const uint32_t bits = (uint32_t)(CH_BASE + j + 1) << CH_SHIFT;   // upper edge of bin j (exclusive)
-        float Tf;
-        memcpy(&Tf, &bits, 4);
-        const double T = (double)Tf, lM = std::log10(T);
-        double bc = 0, bs = 0;
+        const double T = edges.T[j], lM = edges.lM[j];
+        double bc = 0, bs = 0, eLc = 0;
         if (c.c_ok) {
-            if (p.want_LRG) bc += half_erfc(lM, Lc_h.lo, p.L_sigma) * p.L_ic;
+            if (p.want_LRG) bc += (eLc = half_erfc(lM, Lc_h.lo, p.L_sigma)) * p.L_ic;
             if (p.want_QSO) bc += half_erfc(lM, Qc_h.lo, p.Q_sigma) * p.Q_ic;   // 0.5 (1 + erf(u)) = 0.5 erfc(-u)
             if (p.want_ELG) {
                 // d = logM - logM_cut' over the bin (its lower edge widened by the round-up of the shadow mass) and the range
@@ -2176,13 +2355,12 @@ Cheap make_cheap(const abacus_hod_params &p, const Filt &F, const HodRanges &R) 
             }
         }
         if (c.s_ok) {
-            if (p.want_LRG) bs += plaw(T, p.L_kappa, Lc_p, L1, p.L_alpha) * half_erfc(lM, Lc_p.lo, p.L_sigma) * p.L_ic;
+            if (p.want_LRG) bs += plaw(T, pL) * (L_same && c.c_ok ? eLc : half_erfc(lM, Lc_p.lo, p.L_sigma)) * p.L_ic;
             if (p.want_ELG) {
-                const double v = std::max(plaw(T, p.E_kappa, Ec_p, E1, p.E_alpha),
-                                          std::max(plaw(T, p.E_kappa, Ec_p, E1L, p.E_alpha_EL), plaw(T, p.E_kappa, Ec_p, E1E, p.E_alpha_EE)));
+                const double v = std::max(plaw(T, pE), std::max(plaw(T, pEL), plaw(T, pEE)));
                 bs += p.E_A_s * v * p.E_ic;
             }
-            if (p.want_QSO) bs += plaw(T, p.Q_kappa, Qc_p, Q1, p.Q_alpha) * p.Q_ic;
+            if (p.want_QSO) bs += plaw(T, pQ) * p.Q_ic;
         }
         if (!std::isfinite(bc)) c.c_ok = 0;
         if (!std::isfinite(bs)) c.s_ok = 0;
@@ -2249,7 +2427,7 @@ OutCols out_cols(abacus_hod_state *st) {
 
 // packed records of an owned catalogue: built once; the random / hveldev fields rewritten after a reseed or an update
 int build_records(abacus_hod_state *st) {
-    const bool norec = option("hod_norec") != 0;
+    const bool norec = hod_opts().norec != 0;
     if (!st->owns || norec || (st->rec_ok && st->rec_rand_ok)) return 0;
     ABACUS_TRY(st->hrec.reserve((size_t)std::max<int64_t>(st->nh, 1) * sizeof(HaloRec)));
     ABACUS_TRY(st->prec.reserve((size_t)std::max<int64_t>(st->np, 1) * sizeof(PartRec)));
@@ -2304,7 +2482,7 @@ HodPtrs make_ptrs(const abacus_hod_state *st) {
 
 // superblock size of a populate: 16 tiles for LRG alone, 8 for the dense mixes (see SB_TILES_*)
 void set_superblocks(abacus_hod_state *st, const abacus_hod_params *p) {
-    int sbt = option("hod_sbtiles");
+    int sbt = hod_opts().sbtiles;
     if (sbt != SB_TILES_DENSE && sbt != SB_TILES_SPARSE) sbt = (p->want_ELG || p->want_QSO) ? SB_TILES_DENSE : SB_TILES_SPARSE;
     st->sb_tiles = sbt;
     // Dense mixes: hod_exact is one round of workgroups (three fit a CU at its ~150 registers), and a CU that holds three of
@@ -2313,7 +2491,7 @@ void set_superblocks(abacus_hod_state *st, const abacus_hod_params *p) {
     const int per_round = 3 * 256;
     auto count = [&](int ntile) {
         int n = (int)ceil_div(ntile, sbt);
-        if (sbt == SB_TILES_DENSE && n > 256 && !option("hod_nobalance")) n = (int)ceil_div(n, per_round) * per_round;
+        if (sbt == SB_TILES_DENSE && n > 256 && !hod_opts().nobalance) n = (int)ceil_div(n, per_round) * per_round;
         return std::min(n, std::max(ntile, 0));
     };
     st->nsb_c = count(st->ntile_c);
@@ -2336,22 +2514,44 @@ int launch_emit(abacus_hod_state *st) {
     if (st->emit_bm) {   // queue-free index path: sparse superblocks, 256 threads
         const int cur = st->bm_par, prev = cur ^ 1;
         unsigned int *bm = st->bm.as<unsigned int>();
-        int *cnt = st->bm_counts.as<int>();
-        ABACUS_LAUNCH("hod_emit", (hod_emit_bm<256, SB_TILES_SPARSE>), dim3(nemit), dim3(256), 0, st->nsb_c, st->nsb_s, st->ntile_c,
-                      st->ntile_s, (const unsigned int *)(bm + (int64_t)cur * 3 * st->bm_words), bm + (int64_t)prev * 3 * st->bm_words,
-                      st->bm_words, (const int *)(cnt + (int64_t)cur * st->bm_cstride),
-                      cnt + (int64_t)prev * st->bm_cstride, st->keep_c, st->keep_s, st->h_totals_dev, in, st->params, out_cols(st));
+        // look-back words: tags keep the words of earlier launches apart, so they are cleared only when (re)laid out and
+        // when the tag wraps
+        if (st->lb_n != nemit || st->lb_tag == LB_TAG_MAX) {
+            const size_t bytes = (size_t)3 * nemit * sizeof(unsigned long long);
+            ABACUS_TRY(st->lb.reserve(bytes));
+            HIP_TRY(hipMemsetAsync(st->lb.p, 0, bytes, stream()));
+            st->lb_n = nemit, st->lb_tag = 0;
+        }
+        // the look-back waits only on smaller superblocks: deadlock-free when every workgroup of the grid can be resident at
+        // once, so the grid is capped there.  The runtime's answer counts registers and LDS; the hardware also admits at most
+        // 800 / (SGPRs rounded up to 16, + 16) 256-thread workgroups per CU - 6 at this kernel's ~100 - which the runtime
+        // does not check (at 133 VGPRs its answer is 3: 768 workgroups at once, 612 superblocks at 1e7 + 1e7)
+        static int resident = 0;
+        if (!resident) {
+            int dev = 0, ncu = 0, per_cu = 0;
+            HIP_TRY(hipGetDevice(&dev));
+            HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hod_emit_bm<256, SB_TILES_SPARSE>, 256, 0));
+            resident = std::min(std::max(per_cu, 1), 5) * std::max(ncu, 1);
+        }
+        ABACUS_LAUNCH("hod_emit", (hod_emit_bm<256, SB_TILES_SPARSE>), dim3(std::min(nemit, resident)), dim3(256), 0, st->nsb_c,
+                      st->nsb_s, st->ntile_c, st->ntile_s, (const unsigned int *)(bm + (int64_t)cur * 3 * st->bm_words),
+                      bm + (int64_t)prev * 3 * st->bm_words, st->bm_words, st->bm_mask[cur], st->bm_mask[prev],
+                      reinterpret_cast<unsigned long long *>(st->lb.p), st->lb_tag + 1, st->keep_c, st->keep_s, st->h_totals_dev,
+                      in, st->params, out_cols(st));
+        st->lb_tag++;
+        st->bm_mask[prev] = 0;   // this emission zeroes the previous set
         return 0;
     }
     // workgroup size: 384 threads per superblock for the dense mixes (ELG / QSO: a few thousand galaxies per superblock; at
     // its 86 registers three such workgroups fit a CU - all 768 central superblocks of 1e7 halos at once - where only two of
     // 512 threads do: 92 vs 101 us at LRG + ELG + QSO on 1e7 + 1e7, 95 with 256), 256 for LRG alone (12 vs 20 us: the larger
     // workgroups only cost launch time)
-    int eb = option("hod_eblock");
+    int eb = hod_opts().eblock;
     if (eb != 256 && eb != 384 && eb != 512) eb = (st->params.want_ELG || st->params.want_QSO) ? 384 : 256;
 #define EMIT(EB, SBT)                                                                                                       \
     ABACUS_LAUNCH("hod_emit", (hod_emit<EB, SBT>), dim3(nemit), dim3(EB), 0, st->nsb_c, st->nsb_s, st->ntile_c, st->ntile_s, st->kept_c, st->kept_s, \
-                  st->sb_counts, st->h_totals_dev, in, st->params, out_cols(st), option("dbg"))
+                  st->sb_counts, st->h_totals_dev, in, st->params, out_cols(st), hod_opts().dbg)
     const bool sparse = st->sb_tiles == SB_TILES_SPARSE;
     if (eb == 384 && sparse) EMIT(384, SB_TILES_SPARSE);
     else if (eb == 384) EMIT(384, SB_TILES_DENSE);
@@ -2500,32 +2700,31 @@ int build_shadows(abacus_hod_state *st, bool rand_only) {
 }
 
 // queue-free index path: hod_exact_index over the candidate prefixes of the key index, then hod_emit_bm (see there).  Entering
-// it (the first populate, or after any other path) clears the keep masks, both sets of bitmaps and both sets of counts once.
+// it (the first populate, or after any other path) clears the keep masks and both sets of bitmaps once.
 int populate_bitmaps(abacus_hod_state *st, const abacus_hod_params *p, const SatPre &pre, const HodPtrs &a, const DealTab &deal,
                      bool was_valid) {
     if (!was_valid) {
         const int64_t words = (int64_t)(st->ntile_c + st->ntile_s) * (TILE / 32);
-        const int cstride = (st->nsb_c + st->nsb_s) * BM_CS;
         ABACUS_TRY(st->bm.reserve((size_t)2 * 3 * words * sizeof(unsigned int)));
-        ABACUS_TRY(st->bm_counts.reserve((size_t)2 * cstride * sizeof(int)));
-        st->bm_words = words, st->bm_cstride = cstride;
+        st->bm_words = words;
+        st->bm_mask[0] = st->bm_mask[1] = 0;
         HIP_TRY(hipMemsetAsync(st->bm.p, 0, (size_t)2 * 3 * words * sizeof(unsigned int), stream()));
-        HIP_TRY(hipMemsetAsync(st->bm_counts.p, 0, (size_t)2 * cstride * sizeof(int), stream()));
         HIP_TRY(hipMemsetAsync(st->keep_c, 0, (size_t)st->nh, stream()));
         HIP_TRY(hipMemsetAsync(st->keep_s, 0, (size_t)st->np, stream()));
     }
     const int cur = st->bm_par ^ 1;
     abacus_cls::ClsConst cc;
     abacus_cls::make_cls_const(*p, pre, cc);
-    const int use_cls = option("hod_nocls") ? 0 : 1;   // A/B: every candidate through the float64 chain
+    const int use_cls = hod_opts().nocls ? 0 : 1;   // A/B: every candidate through the float64 chain
     const unsigned int *idx = st->index_idx.as<unsigned int>();
     unsigned int *bm = st->bm.as<unsigned int>() + (int64_t)cur * 3 * st->bm_words;
-    int *cnt = st->bm_counts.as<int>() + (int64_t)cur * st->bm_cstride;
     const unsigned int total = deal.pre[deal.nseg];
     if (total > 0)
         ABACUS_LAUNCH("hod_exact", hod_exact_index, dim3((total + 255u) / 256u), dim3(256), 0, a, idx, idx + st->nh, deal, total, bm,
-                      st->bm_words, cnt, *p, pre, cc, use_cls);
+                      st->bm_words, *p, pre, cc, use_cls);
     st->bm_par = cur;
+    // the tracers this populate may keep: the wanted ones, and LRG always (a random of exactly 0 passes its zero marker)
+    st->bm_mask[cur] = 1 | (p->want_ELG ? 2 : 0) | (p->want_QSO ? 4 : 0);
     st->emit_bm = true;
     ABACUS_TRY(launch_emit(st));
     st->bm_valid = true;
@@ -2575,6 +2774,7 @@ static int stage_fill(abacus_hod_state *st, const abacus_hod_arrays *a, int on_d
     HIP_TRY(hipMalloc((void **)&st->kept_s, (size_t)(st->ntile_s + SB_TILES_MAX) * TILE * sizeof(unsigned short)));
     HIP_TRY(hipHostMalloc((void **)&st->h_totals, 8 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent));
     HIP_TRY(hipHostGetDevicePointer((void **)&st->h_totals_dev, st->h_totals, 0));
+    memset(st->h_totals, 0, 8 * sizeof(int64_t));   // [6]: set by an emission whose look-back gave up a wait
     // first guess for the catalog buffers; grown on demand by abacus_hod_counts
     for (int t = 0; t < 3; t++) ABACUS_TRY(set_capacity(st, t, (nh + np) / 64));
     if (st->pinds && st->np > 0) {   // keep_c[pinds[i]] is read unchecked by the kernels: reject a stale / out-of-range index here
@@ -2849,7 +3049,7 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
     const int ntile = st->ntile_c + st->ntile_s, nsb = st->nsb_c + st->nsb_s;
     // owned catalogues: the filter streams the float32 shadow columns (half the bytes); caller-owned device arrays can
     // change behind the library's back, so they are streamed as they are
-    const bool force64 = option("hod_f64filter") != 0;
+    const bool force64 = hod_opts().f64filter != 0;
     const bool use32 = st->owns && !force64;
     if (use32 && !st->shadow_ok) ABACUS_TRY(build_shadows(st, false));
     else if (use32 && !st->shadow_rand_ok) ABACUS_TRY(build_shadows(st, true));
@@ -2861,21 +3061,21 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
     // lazy keep masks (see hod_exact): only when one key-filter launch covers both kinds, the mix is sparse, and the kept
     // lists of the previous populate describe the masks
     const bool filter_first_ = conf && use32 && cheap.s_ok;
-    const bool lazy_ok = use32 && !option("hod_nokeys") && !option("hod_nolazy") && cheap.c_ok && cheap.s_ok && st->ntile_c > 0 &&
+    const bool lazy_ok = use32 && !hod_opts().nokeys && !hod_opts().nolazy && cheap.c_ok && cheap.s_ok && st->ntile_c > 0 &&
                          st->ntile_s > 0 && (!conf || filter_first_) && st->sb_tiles == SB_TILES_SPARSE;
     const bool lazy_masks = lazy_ok && st->kept_valid && st->kept_sb_tiles == st->sb_tiles;
     st->kept_valid = false;   // until this populate's launches are all enqueued
     // the index path without queues (hod_exact_index -> hod_emit_bm) - except where the satellites read keep_cent[pinds], which
     // holds the previous populate's bytes until hod_emit_bm: then, and with `hod_deal` = 1 (the A/B comparator), the index
     // path is hod_deal -> hod_exact -> hod_emit
-    const bool bm_path = !option("hod_deal") && !conf;
+    const bool bm_path = !hod_opts().deal && !conf;
     const bool bm_was_valid = st->bm_valid;
     st->bm_valid = st->emit_bm = false;   // until a populate of the queue-free path is enqueued
     // mass-sorted key index (see hod_deal): from the second populate on the same keys, for the mixes that run lazy masks (the
     // queue-free path keeps its own record of the masks: it only needs the mix to qualify)
     bool index_mode = false;
     DealTab deal;
-    if (use32 && st->sb_tiles == SB_TILES_SPARSE && !option("hod_noindex") && !option("hod_nokeys")) {
+    if (use32 && st->sb_tiles == SB_TILES_SPARSE && !hod_opts().noindex && !hod_opts().nokeys) {
         st->key_uses++;
         if (!st->index_ok && st->key_uses >= 2) ABACUS_TRY(build_index(st));
         if (st->index_ok && (bm_path ? lazy_ok : lazy_masks)) {
@@ -2914,7 +3114,7 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
                   p->want_ELG, p->want_QSO, p->enable_ranks, need_env, need_shear, F, cheap)
         const bool c2 = cheap.c_ok != 0, s2 = cheap.s_ok != 0;
         // two-stage kinds stream the packed keys (4 B per object), whole tile groups: only full-kind ranges take this path
-        const bool keyed = !option("hod_nokeys");
+        const bool keyed = !hod_opts().nokeys;
         const unsigned short *hk = st->keys.as<unsigned short>(), *pk = hk + (int64_t)std::max(st->ntile_c, 1) * TILE;
         const bool kc = keyed && c2 && c0 == 0 && c1 == st->ntile_c && c1 > c0, ks = keyed && s2 && s0 == 0 && s1 == st->ntile_s && s1 > s0;
         const int gc = (int)ceil_div(st->ntile_c, KEY_TILES), gs = (int)ceil_div(st->ntile_s, KEY_TILES);
@@ -2970,11 +3170,11 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
             ABACUS_LAUNCH("hod_filter", hod_filter, dim3(count), dim3(FBLOCK), 0, a, first, p->want_LRG, p->want_ELG, \
                           p->want_QSO, p->enable_ranks, need_env, need_shear, F);                                    \
     }
-    const bool nocls = option("hod_nocls") != 0;   // A/B: every candidate through the float64 chain
+    const bool nocls = hod_opts().nocls != 0;   // A/B: every candidate through the float64 chain
     abacus_cls::ClsConst cc;
     abacus_cls::make_cls_const(*p, pre, cc);
     // software-pipelined candidate loop for the dense mixes (see hod_exact); `hod_pipe` = 1 / 2 forces it off / on (A/B)
-    const int pipe_opt = option("hod_pipe");
+    const int pipe_opt = hod_opts().pipe;
     const bool pipe = a.hrec && a.prec && (pipe_opt == 2 || (pipe_opt != 1 && (p->want_ELG || p->want_QSO)));
     const bool sparse_sb = st->sb_tiles == SB_TILES_SPARSE;
 #define EXACT_(PIPE, SBT, first, count)                                                                                      \
@@ -3027,6 +3227,11 @@ int abacus_hod_counts(abacus_hod_state *st, int64_t counts[6]) {
     if (!st || !st->have_run) return fail("abacus_hod_counts: populate has not been called");
     if (!st->counts_valid) {
         HIP_TRY(hipStreamSynchronize(stream()));
+        if (st->h_totals[6]) {
+            const long long code = (long long)st->h_totals[6];
+            st->h_totals[6] = 0;
+            return fail("abacus_hod_counts: the emission's offset look-back failed (code %lld)", code);
+        }
         bool grew = false;
         for (int t = 0; t < 3; t++) {
             st->counts[t] = st->h_totals[t];
@@ -3145,7 +3350,7 @@ int abacus_hod_free(abacus_hod_state *st) {
     (void)st->keys.release();
     (void)st->index_idx.release(), (void)st->index_scratch.release(), (void)st->index_tmp.release(), (void)st->index_last.release();
     (void)st->hrec.release(), (void)st->prec.release();
-    (void)st->bm.release(), (void)st->bm_counts.release();
+    (void)st->bm.release(), (void)st->lb.release();
     delete st;
     return 0;
 }

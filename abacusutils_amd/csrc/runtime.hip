@@ -1,5 +1,6 @@
 // Runtime entry points of include/abacus_hip.h: device selection, the library stream, raw device memory,
 // HIP-event timers and the per-kernel profiler.
+#include <atomic>
 #include <cstring>
 #include <map>
 #include <string>
@@ -199,11 +200,15 @@ std::map<std::string, int> &option_table() {
 }
 }  // namespace
 
+static std::atomic<unsigned int> g_option_version{0};
+
 int option(const char *name) {
     std::lock_guard<std::recursive_mutex> guard(api_mutex());
     auto it = option_table().find(name);
     return it == option_table().end() ? 0 : it->second;
 }
+
+unsigned int option_version() { return g_option_version.load(std::memory_order_acquire); }
 
 }  // namespace abacus
 
@@ -220,6 +225,7 @@ int abacus_set_option(const char *name, int value) {
     if (!ok) return abacus::fail("abacus_set_option: unknown option '%s'", name);
     std::lock_guard<std::recursive_mutex> guard(abacus::api_mutex());
     abacus::option_table()[name] = value;
+    abacus::g_option_version.fetch_add(1, std::memory_order_release);
     return 0;
 }
 
