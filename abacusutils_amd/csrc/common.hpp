@@ -24,6 +24,8 @@ int scratch_trim_idle();
 // mesh of the out-of-place passes) hold nothing between calls: given back when an allocation of the caller's fails (abacus_malloc)
 int power_trim_caches();
 int fft_trim_scratch();
+// the in-place hipFFT plans shear.hip keeps for the last mesh size (their work areas are device memory)
+int shear_release_plans();
 
 #define HIP_TRY(expr)                                                                                       \
     do {                                                                                                    \

@@ -305,6 +305,11 @@ int abacus_memcpy_d2h(void *dst, const void *src, uint64_t nbytes) {
     HIP_TRY(hipStreamSynchronize(g_stream));
     return 0;
 }
+int abacus_memcpy_d2d(void *dst, const void *src, uint64_t nbytes) {
+    ABACUS_ENTER();
+    HIP_TRY(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToDevice, g_stream));
+    return 0;
+}
 int abacus_memset(void *dptr, int value, uint64_t nbytes) {
     ABACUS_ENTER();
     HIP_TRY(hipMemsetAsync(dptr, value, nbytes, g_stream));
@@ -380,6 +385,7 @@ int abacus_profile_enable(int on) {
 }
 int abacus_scratch_release(void) {
     ABACUS_ENTER();
+    ABACUS_TRY(shear_release_plans());
     return scratch_trim();
 }
 int abacus_profile_select(const char *name) {

@@ -369,6 +369,15 @@ def _prepare_slab_device(halos, parts, Mpart, h, MT, want_ranks, want_AB, fenv_r
     return out, P, mask
 
 
+def _shear_at(shearmark, g):
+    """shearmark[g[:, 0], g[:, 1], g[:, 2]]: a host array is fancy-indexed as before; a field that stays on the device
+    (`_lib.DeviceArray`, what `shearmark_from_positions(device_out=True)` returns) is looked up there (abacus_mesh_gather_dev)"""
+    if isinstance(shearmark, _lib.DeviceArray):
+        from ..analysis.shear import mesh_gather
+        return mesh_gather(shearmark, g)
+    return shearmark[g[:, 0], g[:, 1], g[:, 2]]
+
+
 def prepare_slab_arrays(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=True, Menv=None, shearmark=None, Lbox=None,
                         mcut=1e11, halo_lc=False, rng='numpy', part_index0=0, halo_index0=0, origins=None, lc_seed=None,
                         rad_outer=10):
@@ -409,7 +418,7 @@ def prepare_slab_arrays(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=Tr
         if shearmark is not None:
             ndim = len(shearmark)
             g = (hcol('x_L2com') / (Lbox / ndim)).astype(int) % ndim
-            shear = rank_in_mass_bins(shearmark[g[:, 0], g[:, 1], g[:, 2]], hN * Mpart, mbins)
+            shear = rank_in_mass_bins(_shear_at(shearmark, g), hN * Mpart, mbins)
         return _prepare_slab_device(halos, parts, Mpart, h, MT, want_ranks, want_AB, fenv, shear, mbins, seed, part_index0, halo_index0)
     N = np.ascontiguousarray(halos['N'], dtype=np.uint32)
     masses = halos['N'] * Mpart
@@ -444,7 +453,7 @@ def prepare_slab_arrays(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=Tr
     if shearmark is not None:                                                        # (:776-796)
         ndim = len(shearmark)
         g = (np.asarray(halos['x_L2com']) / (Lbox / ndim)).astype(int) % ndim
-        H['shear_rank'] = rank_in_mass_bins(shearmark[g[:, 0], g[:, 1], g[:, 2]], masses, mbins)
+        H['shear_rank'] = rank_in_mass_bins(_shear_at(shearmark, g), masses, mbins)
     else:
         H['shear_rank'] = zeros.copy()
 
@@ -674,6 +683,38 @@ _SECONDARY_Z = [0.15, 0.25, 0.35, 0.45, 0.575, 0.65, 0.725, 0.875, 0.95, 1.025, 
                 2.75, 3.0, 5.0, 8.0]
 
 
+def calc_shearmark(simdir, simname, z_mock, N_dim, R, fn, partdown=100, rng=None):
+    """The shear field of a simulation snapshot (hod/prepare_sim.py:1055-1127, the reference's signature): `len // partdown` randomly
+    chosen particles of every `field_rv_A` and `halo_rv_A` file, TSC counts on N_dim^3 cells, Gaussian smoothing with scale `R`,
+    the tidal shear - deposit, filter, transforms and shear in one device call (abacus_shearmark_dev).  Saves `fn + '.npy'` and
+    returns the field.  `rng` (extension): a numpy.random.Generator for the down-sampling; default NumPy's global state, which the
+    reference draws from."""
+    import glob
+
+    from ..analysis.shear import shearmark_from_positions
+    from ..data.asdf import AsdfFile
+    from ..data.bitpacked import unpack_rvint
+    N_dim = int(N_dim)
+    if N_dim % 2:
+        raise ValueError(f'N_dim = {N_dim} is odd: the reference fails there (irfftn returns N - 1 cells); use an even mesh')
+    zdir = simdir + '/' + simname + '/halos/z' + str(z_mock).ljust(5, '0')
+    choice = np.random.choice if rng is None else rng.choice
+    partpos, Lbox = [], None
+    for kind in ('field_rv_A', 'halo_rv_A'):
+        for efn in glob.glob(zdir + '/' + kind + '/*asdf'):
+            af = AsdfFile(efn)
+            header = af.tree['header']
+            Lbox = header['BoxSizeHMpc']
+            pos, _ = unpack_rvint(af.array('rvint'), header['BoxSize'], float_dtype=np.float32, velout=False)
+            partpos.append(pos[choice(len(pos), size=int(len(pos) / partdown), replace=False)])
+    if not partpos:
+        raise ValueError(f'no field_rv_A / halo_rv_A files found in {zdir}')
+    pos_parts = np.ascontiguousarray(np.concatenate(partpos), dtype=np.float32)
+    shearmark = shearmark_from_positions(pos_parts, N_dim, Lbox, R)
+    np.save(fn + '.npy', shearmark)
+    return shearmark
+
+
 def main(path2config, params=None, alt_simname=None, alt_z=None, newseed=600, halo_lc=False, overwrite=1):
     """prepare_sim for every slab of the simulation a config names (hod/prepare_sim.py:1130-1291, the reference's signature).
     The slabs are prepared one after the other in this process (the reference spreads them over a process pool; a GPU process
@@ -728,8 +769,7 @@ def main(path2config, params=None, alt_simname=None, alt_z=None, newseed=600, ha
         if os.path.exists(shear_fn + '.npy'):
             shearmark = np.load(shear_fn + '.npy')
         else:
-            raise NotImplementedError('the shear field (calc_shearmark, :1055-1127: field particles, smoothing, tidal tensor) is not '
-                                      f'computed by the MI355X build: supply {shear_fn}.npy')
+            shearmark = calc_shearmark(simdir, simname, z_mock, Ndim, Rsm, shear_fn, partdown=partdown)     # (:1235)
     for i in range(numslabs):
         prepare_slab(i, savedir=savedir, simdir=simdir, simname=simname, z_mock=z_mock, z_type=ztype, tracer_flags=tracer_flags,
                      MT=MT, want_ranks=want_ranks, want_AB=want_AB, want_shear=want_shear, shearmark=shearmark, cleaning=cleaning,

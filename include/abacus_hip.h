@@ -41,6 +41,7 @@ int abacus_malloc(void **dptr, uint64_t nbytes);
 int abacus_free(void *dptr);
 int abacus_memcpy_h2d(void *dst, const void *src, uint64_t nbytes);
 int abacus_memcpy_d2h(void *dst, const void *src, uint64_t nbytes);
+int abacus_memcpy_d2d(void *dst, const void *src, uint64_t nbytes);   /* enqueued on the library stream */
 int abacus_memset(void *dptr, int value, uint64_t nbytes);
 /* page-locked host memory (hipHostMalloc): device-to-host copies into it are single DMAs at link speed.  The Python side
  * hands catalogue columns out as NumPy views of such blocks and recycles them (abacusutils_amd/_lib.py pinned_empty) */
@@ -620,6 +621,32 @@ int abacus_unpack_pack9(const uint8_t *data, int64_t nrec, double boxsize, doubl
 int abacus_menv(const void *pos, int pos_f64, const void *mass, int mass_f64, int64_t n, const void *r_inner,
                 int64_t n_inner, const void *r_outer, int64_t n_outer, int r_f64, double r_outer_max, double Lbox,
                 int periodic, const double *lo, const double *hi, double mcut, double *Menv);
+
+/* ---------------------------------------------------------------- tidal shear field --------------------- */
+/*
+ * The chain particles -> density -> Gaussian smoothing -> tidal tensor -> shear on DEVICE pointers (csrc/shear.hip); every call
+ * enqueues on the library stream.  Meshes are C-contiguous (n, n, n) float32.
+ */
+/* replaces: smooth_density (analysis/shear.py:15-21) = scipy.ndimage.gaussian_filter with its defaults: three separable passes
+ * along axes 0, 1, 2, float64 sums rounded to float32 after each pass, boundary mode 'reflect' (not periodic).  weights: HOST array of
+ * radius + 1 float64 values, weights[k] = the normalised kernel at distance k from the centre.  In place on `mesh`; tmp: n^3 floats. */
+int abacus_gauss_smooth_dev(float *mesh, float *tmp, int n, const double *weights, int radius);
+/* replaces: get_shear (analysis/shear.py:96-131) = rfftn + get_tidal (:38-66) + six irfftn + get_shear_nb (:69-93).  dens is
+ * not modified; out (n^3 floats) overlaps nothing.  R_or_negative >= 0: the top-hat window Wth (:24-29) of that radius; < 0: R = None.
+ * n even (the reference fails on odd sizes).  The modes with a zero index on any axis are dropped and the Nyquist plane of the last
+ * axis carries fftfreq's negative wavenumber, as in the reference.  Two padded work meshes come from the scratch pool; the call
+ * fails up front, naming the largest mesh that fits, when they do not fit the free device memory. */
+int abacus_shear_dev(float *dens, float *out, int n, double Lbox, double R_or_negative);
+/* replaces: the compute part of calc_shearmark (hod/prepare_sim.py:1113-1123): tsc_parallel(pos, n, Lbox) raw counts (positions
+ * wrapped into the box on a copy), smooth_density with sigma_cells = R / (Lbox / n) (<= 0: none), get_shear with R = None.
+ * pos: (np, 3) float32; out: n^3 floats, also used as a work mesh. */
+int abacus_shearmark_dev(const float *pos, int64_t np, int n, double Lbox, double sigma_cells, float *out);
+/* replaces: get_tidal (analysis/shear.py:38-66) as it returns: dfour (n, n, n/2+1) complex64, karr (n) float32 wavenumbers,
+ * out (n, n, n/2+1, 6) complex64 = the six FULL components k_i k_j / k^2 dfour in the order xx xy xz yy yz zz */
+int abacus_tidal_dev(const void *dfour_c64, const float *karr, int n, double R_or_negative, void *out_c64);
+/* replaces: the fancy-indexed look-up shearmark[g[:, 0], g[:, 1], g[:, 2]] (hod/prepare_sim.py:786-791) in a field that stays on
+ * the device: g (nh, 3) int64 cell indices, out (nh) float32; an index outside [0, n) gives NaN */
+int abacus_mesh_gather_dev(const float *mesh, int n, const int64_t *g, int64_t nh, float *out);
 
 #ifdef __cplusplus
 }
