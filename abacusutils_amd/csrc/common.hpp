@@ -26,6 +26,8 @@ int power_trim_caches();
 int fft_trim_scratch();
 // the in-place hipFFT plans shear.hip keeps for the last mesh size (their work areas are device memory)
 int shear_release_plans();
+// the same for zcv.hip
+int zcv_release_plans();
 
 #define HIP_TRY(expr)                                                                                       \
     do {                                                                                                    \

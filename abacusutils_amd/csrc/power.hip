@@ -1889,6 +1889,41 @@ int power_trim_caches() {
     ABACUS_TRY(fft_trim_scratch());
     return 0;
 }
+
+// For zcv.hip.  What get_field_fft returns (deposit, transform, interlacing combine, compensation) for DEVICE particles, written
+// into the caller's padded spectrum `dest` (n * n rows of pitch_r(n) / 2 complex): the work meshes of the context are free again
+// when this returns, the spectrum stays with the caller.
+int power_field_spectrum_dev(float *pos, int64_t n, const float *w, double Lbox, int nmesh, int paste, const float *W_host, int interlaced,
+                             void *dest) {
+    ABACUS_TRY(check_common(nmesh, paste));
+    ABACUS_TRY(ensure_phase(nmesh));
+    const float *W_dev;
+    ABACUS_TRY(upload_W(W_host, nmesh, &W_dev));
+    ABACUS_TRY(field_fft_dev(pos, n, w, Lbox, nmesh, paste, interlaced, 0));
+    SpecArgs s;
+    fill_spec(s, nmesh, 1, interlaced, W_dev, false);
+    s.a = g_ctx.mesh[0].as<float2>();
+    s.as = interlaced ? g_ctx.mesh[1].as<float2>() : nullptr;
+    s.b = s.bs = nullptr;
+    const int64_t total = (int64_t)nmesh * nmesh * (nmesh / 2 + 1);
+    const int grid = (int)std::min<int64_t>(ceil_div(total, 256), 256 * 32);
+    ABACUS_LAUNCH("spectrum_apply", spectrum_apply, dim3(grid), dim3(256), 0, s, static_cast<float2 *>(dest));
+    return 0;
+}
+
+// calc_pk_from_deltak on finished spectra that lie in HBM in the padded layout; `b` == nullptr: auto power
+int power_bin_padded_dev(const void *a, const void *b, int nmesh, double Lbox, const double *kedges, int Nk, const double *muedges, int Nmu,
+                         const int64_t *poles, int Np, float *power, int64_t *N_mode, float *binned_poles, int64_t *N_mode_poles,
+                         float *k_avg) {
+    if (nmesh < 2 || nmesh > 32767) return fail("power: nmesh %d out of range", nmesh);
+    SpecArgs s;
+    fill_spec(s, nmesh, 0, 0, nullptr, b != nullptr);
+    s.pitch = pitch_r(nmesh) / 2;
+    s.a = static_cast<const float2 *>(a);
+    s.b = static_cast<const float2 *>(b);
+    s.as = s.bs = nullptr;
+    return run_bin(s, Lbox, kedges, Nk, muedges, Nmu, poles, Np, power, N_mode, binned_poles, N_mode_poles, k_avg);
+}
 }  // namespace abacus
 
 extern "C" {

@@ -12,7 +12,8 @@ host RAM across calls, :193-197); `reseed` rewrites the three random arrays in H
 and mirrors them to the host dicts (:824-835).
 `AbacusHOD.from_arrays` builds the object from in-memory arrays (tests, synthetic data); the regular constructor
 runs `staging()` (needs h5py for the `halos_xcom_*`/`particles_xcom_*` files).
-ZCV (`apply_zcv*`) is outside the hot path and not provided.
+ZCV: the fields, their advection and the spectra are in `abacusutils_amd.hod.zcv`; `apply_zcv*` (the combination with the
+ZeNBu model) is not provided.
 """
 import logging
 import math
@@ -627,12 +628,13 @@ class AbacusHOD:
         return clustering
 
     def apply_zcv(self, mock_dict, config, load_presaved=False):
-        """signature of hod/abacus_hod.py:1474; Zel'dovich control variates (hod/zcv) are outside the MI355X hot-path scope"""
-        raise NotImplementedError('Zel\'dovich control variates (hod/zcv) are outside the MI355X hot-path scope')
+        """signature of hod/abacus_hod.py:1474; not built (needs ZeNBu and classy).  `abacusutils_amd.hod.zcv` produces the spectra that
+        the reference's `tools_cv.run_zcv` combines"""
+        raise NotImplementedError('tools_cv.run_zcv needs ZeNBu and classy and is not built; the device half of ZCV (fields, advection, spectra) is abacusutils_amd.hod.zcv')
 
     def apply_zcv_xi(self, mock_dict, config, load_presaved=False):
         """signature of hod/abacus_hod.py:1663; see apply_zcv"""
-        raise NotImplementedError('Zel\'dovich control variates (hod/zcv) are outside the MI355X hot-path scope')
+        raise NotImplementedError('tools_cv.run_zcv needs ZeNBu and classy and is not built; the device half of ZCV (fields, advection, spectra) is abacusutils_amd.hod.zcv')
 
     def gal_reader(self, output_dir=None, simname=None, sim_dir=None, z_mock=None, want_rsd=None, tracers=None):
         """Load `{tracer}s.dat` ECSV catalogs written by run_hod(write_to_disk=True) (:1887-1950)."""

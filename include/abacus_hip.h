@@ -648,6 +648,60 @@ int abacus_tidal_dev(const void *dfour_c64, const float *karr, int n, double R_o
  * the device: g (nh, 3) int64 cell indices, out (nh) float32; an index outside [0, n) gives NaN */
 int abacus_mesh_gather_dev(const float *mesh, int n, const int64_t *g, int64_t nh, float *out);
 
+/* ---------------------------------------------------------------- Zel'dovich control variates ----------- */
+/*
+ * The heavy half of abacusnbody/hod/zcv on DEVICE pointers (csrc/zcv.hip); every call enqueues on the library stream.  Meshes are
+ * C-contiguous (n, n, n) float32, caller spectra C-contiguous (n, n, n/2+1) complex64 (un-normalised rfftn output); "padded"
+ * spectra are n * n rows of abacus_slab_pitch(n) / 2 complex (abacus_zcv_spectrum_bytes bytes).  n is even where an inverse
+ * transform is involved (the reference fails on odd sizes).  Wavenumbers as the reference forms them: dk = float32(2 pi / Lbox),
+ * index i -> i below n/2, i - n from n/2 on (x, y), 0 .. n/2 on z.
+ */
+/* replaces: gaussian_filter (hod/zcv/ic_fields.py:79-107) = rfftn, filter_field, irfftn.  field is not modified; out may be field. */
+int abacus_zcv_filter_dev(const float *field, float *out, int n, double Lbox, double kcut);
+/* replaces: filter_field (:110-148; op 0, exp(-k^2 / (2 kcut^2)), dst may be src), get_n2_fft (:151-189; op 1, -k^2) and
+ * get_sij_fft (:192-255; op 2, k_i k_j / k^2 - delta_ij / 3 for component (ci, cj), the zero vector -> -delta_ij / 3) */
+int abacus_zcv_spectral_dev(const void *src_c64, void *dst_c64, int n, double Lbox, int op, int ci, int cj, double kcut);
+/* replaces: add_ij (:258-268): final_field += float32(factor) * field_to_add^2 */
+int abacus_zcv_add_ij_dev(float *final_field, const float *field_to_add, int n, double factor);
+/* replaces: get_dk_to_s2 (:271-309; which = 0) and get_dk_to_n2 (:312-333; which = 1) on a caller spectrum.  The s_ij spectra
+ * are not Hermitian on the planes c = 0 and c = n/2 (negative Nyquist wavenumber on x and y, positive on z); the reference's irfftn
+ * uses the Hermitian part of those planes, which is written out here before the C2R. */
+int abacus_zcv_dk_to_dev(const void *delta_k_c64, int n, double Lbox, int which, float *out);
+/* replaces: get_fields (:336-366) in one call: d = delta - mean, d2 = delta^2 - mean, s2 = s_ij s_ij - mean, n2 = nabla^2 delta;
+ * one R2C, seven multiplier + C2R rounds; the means are deterministic two-stage float64 sums.  Two padded work meshes come from the
+ * scratch pool; the call fails up front, naming the largest mesh that fits, when they do not fit the free device memory.
+ * delta is not modified; d may be delta. */
+int abacus_zcv_fields_dev(const float *delta, int n, double Lbox, float *d, float *d2, float *s2, float *n2);
+/* replaces: hod/zcv/advect_fields.py main :213-239: pos (n^3, 3) = ((disp * f32(D) [z: * f32(1 + f_growth)]) + f32(index) / f32(n))
+ * * f32(Lbox) % f32(Lbox), every operation a correctly rounded float32 operation, the remainder NumPy's */
+int abacus_zcv_lattice_dev(const float *disp_x, const float *disp_y, const float *disp_z, int n, double Lbox, double D, double f_growth,
+                           float *pos);
+/* replaces: tracer_power.py:157-158 on (np, 3) float32 device positions: pos += f32(Lbox / 2); pos %= f32(Lbox), in place */
+int abacus_zcv_shift_wrap_dev(float *pos, int64_t np, double Lbox);
+/* bytes of one padded spectrum of an n^3 mesh */
+int abacus_zcv_spectrum_bytes(int n, uint64_t *bytes);
+/* fails, naming the largest mesh that fits, when `nfield` padded spectra + the work meshes of one deposit + transform + the
+ * particles (np, or the n^3 lattice when np = 0) do not fit the free device memory */
+int abacus_zcv_check_memory(int n, int nfield, int interlaced, int64_t np);
+/* replaces: get_field_fft (analysis/power_spectrum.py:1001-1070) for DEVICE particles: the finished spectrum (interlacing
+ * combined, compensated when W_host != NULL) into the caller's padded spectrum.  TSC wraps pos in place.  w: np floats or NULL. */
+int abacus_zcv_spectrum_dev(float *pos, int64_t np, const float *w, double Lbox, int n, int paste, const float *W_host, int interlaced,
+                            void *out_padded);
+/* replaces: advect_fields.py main :213-285: the lattice positions (never on the host) deposited once per field with the mesh
+ * weights[f] (device, n^3 floats used where they lie; NULL: unweighted), transformed and finished into out_padded[f].
+ * weights / out_padded: HOST arrays of nfield device pointers. */
+int abacus_zcv_advect_dev(const float *disp_x, const float *disp_y, const float *disp_z, int n, double Lbox, double D, double f_growth,
+                          int nfield, const float *const *weights, int paste, const float *W_host, int interlaced, void *const *out_padded);
+/* replaces: calc_pk_from_deltak (analysis/power_spectrum.py:730-805) on two padded spectra in HBM (b_padded NULL: auto power);
+ * outputs as abacus_pk_from_deltak returns them */
+int abacus_zcv_power_pair(const void *a_padded, const void *b_padded, int n, double Lbox, const double *kedges, int Nk, const double *muedges,
+                          int Nmu, const int64_t *poles, int Np, float *power, int64_t *N_mode, float *binned_poles, int64_t *N_mode_poles,
+                          float *k_avg);
+/* a padded device spectrum as the (n, n, n/2+1) complex64 host array get_field_fft returns */
+int abacus_zcv_spectrum_fetch(const void *padded, int n, void *out_c64_host);
+/* releases the cached hipFFT plans of this section (abacus_scratch_release does so too) */
+int abacus_zcv_release(void);
+
 #ifdef __cplusplus
 }
 #endif
