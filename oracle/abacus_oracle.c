@@ -19,6 +19,7 @@
  * /root/reference/abacusnbody/).  Arithmetic order and dtypes follow the
  * reference; build with -ffp-contract=off so no FMA contraction changes it.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1130,6 +1131,214 @@ void oracle_reseed_particles(int64_t n, int64_t index0, uint64_t seed, double *p
         uint32_t a[4];
         philox4x32_10(c, key, a);
         prandoms[i] = (double)rs_u01(a[g & 3]);
+    }
+}
+
+/* ------------------------------------------------------------------------- */
+/* NFW satellites (hod/GRAND_HOD.py:417-822)                                  */
+/* ------------------------------------------------------------------------- */
+/* The reference draws from unseeded generators, so the link reference -> this restatement is statistical
+ * (tests/test_oracle_nfw.py holds the laws below to hod/GRAND_HOD.py:433-441,497-516,634-706,787-789 with large samples).
+ * The link restatement -> device is exact: the build draws from counter-based streams, restated here from their layout:
+ *   a stream is the word sequence of Philox4x32-10 blocks with counter (g lo, g hi, s, block number 0, 1, ...) and key
+ *   (k lo, k hi), g = global halo index, words of a block in order 0..3;  u = (word + 0.5) 2^-32, one word per uniform;
+ *   numbers of satellites: s = 10 + tracer, k = seed, uniforms consumed by the Poisson sampler alone;
+ *   satellite `rank` of a halo:  s = 20 + tracer, k = seed ^ (rank * 0x9E3779B97F4A7C15), uniforms in the order
+ *     u1, u2 (direction), one for `u < exp_frac`, then either one for the exponential radius or one per table probe
+ *     (at most 256; one more for the fallback radius c * u if none has NFW_draw[k] <= c), then four for the velocity:
+ *     two Box-Muller radii sqrt(-2 log u), two angles 2 pi u; vx, vy from the first pair (cos, sin), vz from the second (cos).
+ * Poisson(lam): lam < 10 by multiplication of uniforms until the product falls to exp(-lam) (Knuth); lam >= 10 by
+ * transformed rejection with squeeze, algorithm PTRS of W. Hoermann, Insurance: Mathematics and Economics 12 (1993) 39-45. */
+typedef struct {
+    uint32_t ctr[4], key[2], buf[4];
+    int used; /* words of buf already handed out; 4 = none left */
+} nfw_stream;
+
+static void nfw_stream_init(nfw_stream *g, uint64_t key, uint64_t index, uint32_t s) {
+    g->ctr[0] = (uint32_t)index, g->ctr[1] = (uint32_t)(index >> 32), g->ctr[2] = s, g->ctr[3] = 0u;
+    g->key[0] = (uint32_t)key, g->key[1] = (uint32_t)(key >> 32);
+    g->used = 4;
+}
+static double nfw_uniform(nfw_stream *g) {
+    if (g->used == 4) {
+        philox4x32_10(g->ctr, g->key, g->buf);
+        g->ctr[3]++;
+        g->used = 0;
+    }
+    return ((double)g->buf[g->used++] + 0.5) * 0x1p-32;
+}
+
+#define NFW_EPS 0x1p-36 /* decisions closer than this (relative) are left to the math library: see nfw_counts in oracle.py */
+static int nfw_close(double a, double b) { return fabs(a - b) <= NFW_EPS * fmax(fabs(a), fabs(b)); }
+
+/* one Poisson deviate; *fragile is raised if any comparison of the draw is decided by less than NFW_EPS */
+static int64_t nfw_poisson(nfw_stream *g, double lam, int *fragile) {
+    if (!(lam > 0.0)) return 0;
+    if (lam <= NFW_EPS || nfw_close(lam, 10.0)) *fragile = 1;
+    if (lam < 10.0) {
+        const double L = exp(-lam);
+        int64_t k = 0;
+        double prod = nfw_uniform(g);
+        for (;;) {
+            if (nfw_close(prod, L)) *fragile = 1;
+            if (!(prod > L) || k >= 1000) return k;
+            k++;
+            prod *= nfw_uniform(g);
+        }
+    }
+    const double slam = sqrt(lam), loglam = log(lam);
+    const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
+    const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
+    for (int it = 0; it < 1000; it++) {
+        const double U = nfw_uniform(g) - 0.5, V = nfw_uniform(g);
+        const double us = 0.5 - fabs(U);
+        const double t = (2.0 * a / us + b) * U, x = t + lam + 0.43;
+        const double k = floor(x);
+        if (fabs(x - rint(x)) <= NFW_EPS * (fabs(t) + lam + 0.43)) *fragile = 1;
+        if (nfw_close(us, 0.07) || nfw_close(V, vr)) *fragile = 1;
+        if (us >= 0.07 && V <= vr) return (int64_t)k;
+        if (nfw_close(us, 0.013) || nfw_close(V, us)) *fragile = 1;
+        if (k < 0.0 || (us < 0.013 && V > us)) continue;
+        int sg;
+        const double lhs = log(V) + log(invalpha) - log(a / (us * us) + b), rhs = -lam + k * loglam - lgamma_r(k + 1.0, &sg);
+        if (fabs(lhs - rhs) <= NFW_EPS * (fabs(lhs) + fabs(rhs))) *fragile = 1;
+        if (lhs <= rhs) return (int64_t)k;
+    }
+    return (int64_t)lam;
+}
+
+/* n deviates of the given means through the stream layout of tracer `t` (the sampler on its own, for the law tests) */
+void oracle_nfw_poisson(int64_t n, const double *lam, uint64_t seed, int64_t index0, int t, int64_t *out, uint8_t *fragile) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        nfw_stream g;
+        int fr = 0;
+        nfw_stream_init(&g, seed, (uint64_t)(index0 + i), 10u + (uint32_t)t);
+        out[i] = nfw_poisson(&g, lam[i], &fr);
+        fragile[i] = (uint8_t)fr;
+    }
+}
+
+/* `M_h - kappa M_cut < 0` of n_sat_LRG_modified / N_sat_generic switches lam between 0 and a positive value */
+static int nfw_cut_close(double M_h, double kappa, double M_cut) { return nfw_close(M_h, kappa * M_cut); }
+
+/* means (:634-706), numbers and fragility flags per tracer and halo: counts / lam / fragile are [3][nh] */
+void oracle_nfw_counts(int64_t nh, const double *hmass, const double *hdeltac, const double *hfenv, const double *hshear,
+                       const int8_t *keep_cent, const oracle_hod_params *p, uint64_t seed, int64_t index0,
+                       int64_t *counts, double *lam, uint8_t *fragile) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nh; i++) {
+        const double m = hmass[i], dc = hdeltac ? hdeltac[i] : 0.0, fe = hfenv ? hfenv[i] : 0.0, sh = hshear ? hshear[i] : 0.0;
+        double l[3] = {0.0, 0.0, 0.0};
+        int fr[3] = {0, 0, 0};
+        const int want[3] = {p->want_LRG, p->want_ELG, p->want_QSO};
+        if (p->want_LRG) { /* :637-651 */
+            const double M1 = pow(10.0, p->L_logM1 + p->L_Asat * dc + p->L_Bsat * fe);
+            const double lc = p->L_logM_cut + p->L_Acent * dc + p->L_Bcent * fe, Mc = pow(10.0, lc);
+            l[0] = n_sat_LRG_modified(m, lc, Mc, M1, p->L_sigma, p->L_alpha, p->L_kappa) * p->L_ic;
+            fr[0] = nfw_cut_close(m, p->L_kappa, Mc);
+        }
+        if (p->want_ELG) { /* :653-694, conformity by the central's flag */
+            double M1 = pow(10.0, p->E_logM1 + p->E_Asat * dc + p->E_Bsat * fe + p->E_Csat * sh), alpha = p->E_alpha;
+            const double lc = p->E_logM_cut + p->E_Acent * dc + p->E_Bcent * fe + p->E_Ccent * sh, Mc = pow(10.0, lc);
+            if (keep_cent[i] == 1) M1 = pow(10.0, p->E_logM1_EL + p->E_Asat * dc + p->E_Bsat * fe), alpha = p->E_alpha_EL;
+            else if (keep_cent[i] == 2) M1 = pow(10.0, p->E_logM1_EE + p->E_Asat * dc + p->E_Bsat * fe), alpha = p->E_alpha_EE;
+            l[1] = N_sat_generic(m, Mc, p->E_kappa, M1, alpha, p->E_A_s) * p->E_ic;
+            fr[1] = nfw_cut_close(m, p->E_kappa, Mc);
+        }
+        if (p->want_QSO) { /* :697-705 */
+            const double M1 = pow(10.0, p->Q_logM1 + p->Q_Asat * dc + p->Q_Bsat * fe);
+            const double lc = p->Q_logM_cut + p->Q_Acent * dc + p->Q_Bcent * fe, Mc = pow(10.0, lc);
+            l[2] = N_sat_generic(m, Mc, p->Q_kappa, M1, p->Q_alpha, 1.0) * p->Q_ic;
+            fr[2] = nfw_cut_close(m, p->Q_kappa, Mc);
+        }
+        for (int t = 0; t < 3; t++) {
+            int64_t k = 0;
+            if (want[t]) {
+                nfw_stream g;
+                nfw_stream_init(&g, seed, (uint64_t)(index0 + i), 10u + (uint32_t)t);
+                k = nfw_poisson(&g, l[t], &fr[t]);
+            }
+            counts[t * nh + i] = k, lam[t * nh + i] = l[t], fragile[t * nh + i] = (uint8_t)fr[t];
+        }
+    }
+}
+
+int oracle_ldbl_mant_dig(void) { return LDBL_MANT_DIG; }
+
+/* satellites (halo[j], rank[j]) of tracer t: positions (:433-441,497-510), velocities (:511-516), RSD (:787-789).
+ * Every branch is taken on IEEE double values that involve no library call; the values are then evaluated twice, in
+ * double (out_d, [6][ns]) and in long double (out_l): the second is the reference of the device comparison, the
+ * distance between the two its noise floor.  r = eta Rvir, sig, branch (0 table, 1 exponential, 2 fallback) per row. */
+void oracle_nfw_satellites(int64_t ns, const int64_t *halo, const int64_t *rank, int t, const double *hpos,
+                           const double *hvel, const double *hvrms, const double *hc, const double *hrvir,
+                           const double *draw, int64_t n_draw, double f_sigv, double exp_frac, double exp_scale,
+                           double nfw_rescale, int rsd, double inv_velz2kms, double lbox, uint64_t seed, int64_t index0,
+                           double *out_d, long double *out_l, double *r_out, double *sig_out, uint8_t *branch) {
+    const double TWO_PI = 6.283185307179586, PI = 3.141592653589793;
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < ns; j++) {
+        const int64_t h = halo[j];
+        nfw_stream g;
+        nfw_stream_init(&g, seed ^ ((uint64_t)rank[j] * 0x9E3779B97F4A7C15ull), (uint64_t)(index0 + h), 20u + (uint32_t)t);
+        const double u1 = nfw_uniform(&g), u2 = nfw_uniform(&g);
+        const double c = hc[h];
+        int br;
+        double ue = 0.0, d = 0.0; /* the uniform of the exponential radius, or the table value */
+        if (nfw_uniform(&g) < exp_frac) {
+            br = 1;
+            ue = nfw_uniform(&g);
+        } else {
+            br = 2;
+            for (int it = 0; it < 256; it++) {
+                int64_t k = (int64_t)(nfw_uniform(&g) * (double)n_draw);
+                if (k > n_draw - 1) k = n_draw - 1;
+                d = draw[k];
+                if (!(d > c)) {
+                    br = 0;
+                    break;
+                }
+            }
+            if (br == 2) ue = nfw_uniform(&g);
+        }
+        const double w0 = nfw_uniform(&g), w1 = nfw_uniform(&g), w2 = nfw_uniform(&g), w3 = nfw_uniform(&g);
+        const double sig = hvrms[h] * 0.577 * f_sigv;
+        branch[j] = (uint8_t)br, sig_out[j] = sig;
+        { /* double */
+            const double ra = u1 * TWO_PI, dec = PI - acos(-1.0 + 2.0 * u2);
+            const double sd = sin(dec), ux = sd * cos(ra), uy = sd * sin(ra), uz = cos(dec);
+            const double eta = br == 1 ? -exp_scale * log(ue) / c : (br == 2 ? c * ue : d) / c * nfw_rescale;
+            const double r = eta * hrvir[h];
+            const double m0 = sqrt(-2.0 * log(w0)), m1 = sqrt(-2.0 * log(w1)), a0 = TWO_PI * w2, a1 = TWO_PI * w3;
+            double z = hpos[3 * h + 2] + uz * r;
+            const double vz = hvel[3 * h + 2] + sig * m1 * cos(a1);
+            if (rsd) {
+                z = z + vz * inv_velz2kms;
+                z = z - floor(z / lbox) * lbox;
+            }
+            r_out[j] = r;
+            out_d[0 * ns + j] = hpos[3 * h] + ux * r, out_d[1 * ns + j] = hpos[3 * h + 1] + uy * r, out_d[2 * ns + j] = z;
+            out_d[3 * ns + j] = hvel[3 * h] + sig * m0 * cos(a0), out_d[4 * ns + j] = hvel[3 * h + 1] + sig * m0 * sin(a0);
+            out_d[5 * ns + j] = vz;
+        }
+        { /* long double: the same expressions of the same double inputs and constants */
+            typedef long double ld;
+            const ld ra = (ld)u1 * TWO_PI, dec = (ld)PI - acosl(-1.0L + 2.0L * u2);
+            const ld sd = sinl(dec), ux = sd * cosl(ra), uy = sd * sinl(ra), uz = cosl(dec);
+            const ld eta = br == 1 ? -(ld)exp_scale * logl((ld)ue) / c : (br == 2 ? (ld)c * ue : (ld)d) / c * nfw_rescale;
+            const ld r = eta * hrvir[h];
+            const ld sg = (ld)hvrms[h] * 0.577 * f_sigv;
+            const ld m0 = sqrtl(-2.0L * logl((ld)w0)), m1 = sqrtl(-2.0L * logl((ld)w1)), a0 = (ld)TWO_PI * w2, a1 = (ld)TWO_PI * w3;
+            ld z = hpos[3 * h + 2] + uz * r;
+            const ld vz = hvel[3 * h + 2] + sg * m1 * cosl(a1);
+            if (rsd) {
+                z = z + vz * inv_velz2kms;
+                z = z - floorl(z / lbox) * lbox;
+            }
+            out_l[0 * ns + j] = hpos[3 * h] + ux * r, out_l[1 * ns + j] = hpos[3 * h + 1] + uy * r, out_l[2 * ns + j] = z;
+            out_l[3 * ns + j] = hvel[3 * h] + sg * m0 * cosl(a0), out_l[4 * ns + j] = hvel[3 * h + 1] + sg * m0 * sinl(a0);
+            out_l[5 * ns + j] = vz;
+        }
     }
 }
 

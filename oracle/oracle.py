@@ -637,6 +637,86 @@ def nfw_expected_counts(halo_data, tracers, params, keep_cent):
     return out
 
 
+# The build draws the NFW satellites from counter-based Philox streams keyed by (seed, global halo index, tracer,
+# satellite rank): everything it emits is a pure function of those and is restated in C (abacus_oracle.c, "NFW
+# satellites") from the stream layout, the published samplers and the reference's formulas.
+NFW_EPS = 2.0 ** -36
+
+
+def nfw_poisson(lam, seed, t=0, index0=0):
+    """the Poisson sampler alone: one deviate per entry of `lam` from the count stream of tracer `t` of halo
+    `index0 + i`.  Returns (numbers int64, fragile bool)."""
+    lam = _f8(lam)
+    out = np.zeros(len(lam), dtype=np.int64)
+    fr = np.zeros(len(lam), dtype=np.uint8)
+    lib().oracle_nfw_poisson(C.c_int64(len(lam)), _ptr(lam), C.c_uint64(int(seed) & (2**64 - 1)), C.c_int64(int(index0)),
+                             int(t), _ptr(out), _ptr(fr))
+    return out, fr.astype(bool)
+
+
+def nfw_counts(halo_data, tracers, params, keep_cent, seed, halo_index0=0):
+    """Numbers of NFW satellites per tracer and halo as the build draws them: (counts int64 [3, nh], lam float64 [3, nh],
+    fragile bool [3, nh]); rows of absent tracers are zero.  `keep_cent`: the centrals' flags of the same populate.
+
+    A (halo, tracer) is FRAGILE when the device may legitimately decide it differently: some comparison of its draw
+    (`prod > exp(-lam)`; in PTRS `us >= 0.07`, `V <= vr`, `us < 0.013`, `V > us`, the log inequality relative to
+    |lhs| + |rhs|, the argument of `floor` against the nearest integer; `M_h - kappa M_cut < 0` of the mean) is closer than
+    2^-36 relative, or lam is within that distance of 0 or of the sampler switch at 10.  The window comes from arithmetic:
+    the device and the glibc math libraries differ by a few ulp (1e-16 .. 1e-15) per call, the worst accumulations are
+    exp(-lam) below 10 and lgamma around 500, about 1e-13; 2^-36 = 1.5e-11 leaves two orders of magnitude."""
+    p = marshal_params(tracers, params, False, True)
+    nh = len(halo_data['hmass'])
+    opt = [(_f8(halo_data[k]) if k in halo_data else None) for k in ('hdeltac', 'hfenv', 'hshear')]
+    m = _f8(halo_data['hmass'])
+    kc = np.ascontiguousarray(keep_cent, dtype=np.int8)
+    assert len(kc) == nh
+    counts = np.zeros((3, nh), dtype=np.int64)
+    lam = np.zeros((3, nh), dtype=np.float64)
+    fr = np.zeros((3, nh), dtype=np.uint8)
+    lib().oracle_nfw_counts(C.c_int64(nh), _ptr(m), *[_ptr(a) for a in opt], _ptr(kc), C.byref(p),
+                            C.c_uint64(int(seed) & (2**64 - 1)), C.c_int64(int(halo_index0)), _ptr(counts), _ptr(lam), _ptr(fr))
+    return counts, lam, fr.astype(bool)
+
+
+def ldbl_mant_dig():
+    """LDBL_MANT_DIG of the compiler that built the oracle (64 on x86-64: the long-double tier is meaningful)"""
+    return int(lib().oracle_ldbl_mant_dig())
+
+
+def nfw_satellites(halo_data, tracers, params, NFW_draw, seed, t, halo, rank, rsd, halo_index0=0):
+    """Satellites `rank[j]` of halos `halo[j]` (local indices) of tracer number `t`, as the build emits them.  Returns a
+    dict: 'double' and 'longdouble' -> the eight columns ('x' .. 'vz' evaluated in that precision; 'mass', 'id' copied
+    from the host), 'r' (eta * Rvir) and 'sig' per satellite, 'branch' (0 table, 1 exponential, 2 fallback c * u).  Every
+    decision (`u < exp_frac`, the table index, `d > c`, the fallback) is taken on IEEE double values and is identical in
+    both evaluations and on the device; a satellite depends on (seed, halo, tracer, rank) alone."""
+    h = halo_data
+    halo = np.ascontiguousarray(halo, dtype=np.int64)
+    rank = np.ascontiguousarray(rank, dtype=np.int64)
+    ns = len(halo)
+    assert len(rank) == ns and (ns == 0 or (halo.min() >= 0 and halo.max() < len(h['hmass'])))
+    draw = _f8(NFW_draw)
+    tr = tracers.get(TRACERS[t], {})
+    elg = tracers.get('ELG', {})   # exp_frac, exp_scale, nfw_rescale: the ELG dict's for every tracer (:603-606)
+    arrs = [_f8(h[k]) for k in ('hpos', 'hvel', 'hsigma3d', 'hc', 'hrvir')]
+    out_d = np.zeros((6, ns), dtype=np.float64)
+    out_l = np.zeros((6, ns), dtype=np.longdouble)
+    r = np.zeros(ns, dtype=np.float64)
+    sig = np.zeros(ns, dtype=np.float64)
+    br = np.zeros(ns, dtype=np.uint8)
+    lib().oracle_nfw_satellites(C.c_int64(ns), _ptr(halo), _ptr(rank), int(t), *[_ptr(a) for a in arrs], _ptr(draw),
+                                C.c_int64(len(draw)), _D(float(tr.get('f_sigv', 0.0))), _D(float(elg.get('exp_frac', 0.0))),
+                                _D(float(elg.get('exp_scale', 1.0))), _D(float(elg.get('nfw_rescale', 1.0))), int(bool(rsd)),
+                                _D(1 / params['velz2kms']), _D(params['Lbox']), C.c_uint64(int(seed) & (2**64 - 1)),
+                                C.c_int64(int(halo_index0)), _ptr(out_d), _ptr(out_l), _ptr(r), _ptr(sig), _ptr(br))
+    res = {'r': r, 'sig': sig, 'branch': br}
+    mass, hid = _f8(h['hmass'])[halo], np.asarray(h['hid'], dtype=np.int64)[halo]
+    for name, o in (('double', out_d), ('longdouble', out_l)):
+        d = {c: o[q] for q, c in enumerate(COLS[:6])}
+        d['mass'], d['id'] = mass, hid
+        res[name] = d
+    return res
+
+
 def compute_ngal_numpy(ball, tracers=None):
     """AbacusHOD.compute_ngal (hod/abacus_hod.py:861-1179) restated in NumPy: the reference's triple / quadruple sums over
     the weighted halo histograms `ball.halo_mass_func` (100^3) and `ball.halo_mass_func_wshear` (100^4), cell centres

@@ -1,7 +1,10 @@
-"""NFW satellites (`gen_gal_cat(nfw=True)`, reference gen_sats_nfw hod/GRAND_HOD.py:417-822).  The reference draws
-from unseeded per-thread generators, so parity is STATISTICAL: satellite numbers against the Poisson means of the
-oracle's restatement, radii against the NFW_draw table, directions, velocities; the deterministic parts (centrals,
-host mass / id, the RSD relation) are checked exactly."""
+"""NFW satellites (`gen_gal_cat(nfw=True)`, reference gen_sats_nfw hod/GRAND_HOD.py:417-822): the end-to-end
+STATISTICAL guard.  The reference draws from unseeded per-thread generators, so the link from the reference to this port
+can only be one of distributions; it is made at high power on the CPU, oracle against the reference's laws
+(tests/test_oracle_nfw.py).  The link from the oracle to the device is EXACT - numbers of satellites per halo, ids, masses,
+order, and every coordinate within a few ulp of a long-double evaluation (tests/test_nfw_exact_gpu.py).  What stays here is
+loose on purpose: satellite numbers against the Poisson means, radii against the NFW_draw table, directions, velocities
+of the device's catalogue itself, plus determinism, the RSD relation, the seed from NumPy's generator and the error paths."""
 import warnings
 
 import numpy as np
