@@ -1,8 +1,14 @@
-"""MI355X drop-in for the heavy half of `abacusnbody.hod.zcv` (Zel'dovich control variates): the Lagrangian operator fields
-(`ic_fields`), their advection and the 15 field spectra (`advect_fields`) and the tracer x field spectra of one HOD evaluation
-(`tracer_power`).  The combination with the Zel'dovich model (`tools_cv.run_zcv`, needs ZeNBu and classy) stays with the reference:
-it takes the dictionaries `field_power` and `tracer_power` return."""
-from . import advect_fields, ic_fields, tracer_power  # noqa: F401
+"""MI355X drop-in for the heavy half of `abacusnbody.hod.zcv` (control variates).  Zel'dovich (ZCV): the Lagrangian operator
+fields (`ic_fields`), their advection and the 15 field spectra (`advect_fields`) and the tracer x field spectra of one HOD
+evaluation (`tracer_power.tracer_power`).  Linear (LCV, for reconstructed catalogues): the linear density spectrum and that times
+mu^2 with their three spectra (`linear_fields`), the tracer-minus-randoms spectra of one HOD evaluation
+(`tracer_power.recon_power`) and the field-level combination `combine_field_spectra_k3D_lcv`.  The combination with the models
+(`tools_cv.run_zcv`, `run_lcv`, `run_lcv_field`; ZeNBu and classy) stays with the reference: it takes the dictionaries and grids
+produced here."""
+from . import advect_fields, ic_fields, linear_fields, tracer_power  # noqa: F401
 from .advect_fields import AdvectedFields, advect, field_power, lattice_positions  # noqa: F401
+from .linear_fields import LinearFields, combine_field_spectra_k3D_lcv, linear_power, linear_power3d  # noqa: F401
+from .tracer_power import recon_power  # noqa: F401
 
-__all__ = ['ic_fields', 'advect_fields', 'tracer_power', 'AdvectedFields', 'advect', 'field_power', 'lattice_positions']
+__all__ = ['ic_fields', 'advect_fields', 'tracer_power', 'linear_fields', 'AdvectedFields', 'advect', 'field_power', 'lattice_positions',
+           'LinearFields', 'linear_power', 'linear_power3d', 'combine_field_spectra_k3D_lcv', 'recon_power']

@@ -702,6 +702,32 @@ int abacus_zcv_spectrum_fetch(const void *padded, int n, void *out_c64_host);
 /* releases the cached hipFFT plans of this section (abacus_scratch_release does so too) */
 int abacus_zcv_release(void);
 
+/* ---------------------------------------------------------------- linear control variates --------------- */
+/*
+ * The linear half (LCV) of abacusnbody/hod/zcv, the one reconstructed catalogues use, on DEVICE pointers (csrc/zcv.hip, beside
+ * the section above whose transform, deposit and binning it shares); every call enqueues on the library stream.  Spectra are
+ * padded (n * n rows of abacus_slab_pitch(n) / 2 complex, abacus_zcv_spectrum_bytes bytes) and normalised as get_field_fft
+ * normalises (divided by n^3), so abacus_zcv_power_pair bins any pair of them and abacus_zcv_spectrum_fetch copies one out.
+ * Mode numbers and mu^2 as get_delta_mu2 forms them: float32, index i -> i below n/2, i - n from n/2 on (x, y), 0 .. n/2 on z;
+ * the zero vector has mu^2 = 0.  Calls that need device memory beyond their arguments fail up front, naming the largest mesh
+ * that fits.
+ */
+/* replaces: linear_fields.py:108-124 (and tracer_power.py:440-456): delta (n, n, n) float32, not modified -> padded copy, R2C in
+ * place, ONE pass that writes rfftn(delta) / f32(n^3) and that times mu^2 (get_delta_mu2 fused with the normalisation).  n even. */
+int abacus_lcv_linear_dev(const float *delta, int n, void *out_delta_padded, void *out_deltamu2_padded);
+/* replaces: tr_field_fft -= rn_field_fft (tracer_power.py:410-414): a -= b over two padded spectra */
+int abacus_lcv_spectrum_sub_dev(void *a_padded, const void *b_padded, int n);
+/* replaces: the P_k3D_* products of save_3D_power (linear_fields.py:138-141, tracer_power.py:464, :501-503): Re(a conj b), or
+ * |a|^2 when b_padded is NULL, unpadded on the device and copied out once as the float32 (n, n, n/2+1) HOST array */
+int abacus_lcv_power3d(const void *a_padded, const void *b_padded, int n, float *out_host);
+/* replaces: combine_field_spectra_k3D_lcv (tools_cv.py:313-335) and the six materialised 3-D products it reads: one pass over
+ * the three padded spectra writes pk_ll = D^2 (2 b f_eff P_md + f_eff^2 P_mm + b^2 P_dd), pk_lt = D (b P_dt + f_eff P_mt) and
+ * pk_tt = |tr|^2 in NumPy's float32 order of evaluation; float32 (n, n, n/2+1) HOST arrays.  reciso = 0: f_eff = f_growth;
+ * reciso = 1: f_eff = f_growth (1 - exp(-k^2 R^2 / 2)) per mode with get_smoothing's float32 wavenumbers, on the (n, n, n/2+1)
+ * grid (the reference reshapes that kernel to (n, n, n) and raises: this branch has no reference output). */
+int abacus_lcv_combine_k3d(const void *delta_padded, const void *deltamu2_padded, const void *tr_padded, int n, double Lbox, double bias,
+                           double f_growth, double D, double R, int reciso, float *pk_tt, float *pk_ll, float *pk_lt);
+
 #ifdef __cplusplus
 }
 #endif
