@@ -14,6 +14,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <cmath>
+#include <initializer_list>
+
 #include "../../include/abacus_hip.h"
 
 #if defined(__HIPCC__)
@@ -163,6 +166,29 @@ static inline void make_cls_const(const abacus_hod_params &p, const SatPre &pre,
     c.E_M1_EL = (float)pre.E_M1_EL, c.E_M1_EE = (float)pre.E_M1_EE;
     c.E_alpha_EL_is_one = p.E_alpha_EL == 1.0, c.E_alpha_EE_is_one = p.E_alpha_EE == 1.0;
     c.want_LRG = p.want_LRG, c.want_ELG = p.want_ELG, c.want_QSO = p.want_QSO, c.enable_ranks = p.enable_ranks;
+}
+
+// The enclosures assume finite parameters: fminf / fmaxf return the other operand for a NaN one and the lower ends are clamped
+// at zero, so a NaN factor (a NaN sigma) can drop out of a product and the marker be decided from the finite factors, where
+// the reference's marker is NaN and keeps nothing.  With a non-finite parameter of a wanted tracer (or sigma = 0: an
+// infinite 1 / sigma) the caller leaves the classifier off and every candidate takes the float64 chain.
+static inline int cls_params_finite(const abacus_hod_params &p) {
+    auto fin = [](std::initializer_list<double> v) {
+        for (double x : v)
+            if (!std::isfinite(x)) return false;
+        return true;
+    };
+    if (p.want_LRG && !(fin({p.L_logM_cut, p.L_logM1, p.L_sigma, p.L_alpha, p.L_kappa, p.L_ic, p.L_Acent, p.L_Asat, p.L_Bcent,
+                             p.L_Bsat, p.L_s, p.L_s_v, p.L_s_p, p.L_s_r}) && p.L_sigma != 0))
+        return 0;
+    if (p.want_ELG && !(fin({p.E_logM_cut, p.E_logM1, p.E_sigma, p.E_alpha, p.E_kappa, p.E_ic, p.E_Acent, p.E_Asat, p.E_Bcent,
+                             p.E_Bsat, p.E_Ccent, p.E_Csat, p.E_s, p.E_s_v, p.E_s_p, p.E_s_r, p.E_p_max, p.E_Q, p.E_gamma,
+                             p.E_A_s, p.E_logM1_EE, p.E_logM1_EL, p.E_alpha_EE, p.E_alpha_EL}) && p.E_sigma != 0))
+        return 0;
+    if (p.want_QSO && !(fin({p.Q_logM_cut, p.Q_logM1, p.Q_sigma, p.Q_alpha, p.Q_kappa, p.Q_ic, p.Q_Acent, p.Q_Asat, p.Q_Bcent,
+                             p.Q_Bsat, p.Q_s, p.Q_s_v, p.Q_s_p, p.Q_s_r}) && p.Q_sigma != 0))
+        return 0;
+    return 1;
 }
 
 // decision of the chain `r <= m1 -> 1; r <= m2 -> 2; r <= m3 -> 3; else 0` from enclosures; -1 = inside a band

@@ -40,7 +40,7 @@ What is captured
   Mini_N64_L32/ref_hod/       the reference's prepare_sim HDF5 files of Mini_N64_L32 (its test data), for
         tests/test_staging.py.
 
-usage: python oracle/make_golden.py [hod] [tsc] [power] [helpers] [catalog] [sweep] [ngal] [pairs] [prepare] [staging]
+usage: python oracle/make_golden.py [hod] [tsc] [power] [helpers] [catalog] [sweep] [corners] [ngal] [pairs] [prepare] [staging]
 """
 import ctypes
 import os
@@ -558,6 +558,49 @@ def gen_sweep(G):
     print('hod_sweep written')
 
 
+def _corner_digest(args):
+    name, nthread = args
+    G = _corner_digest.G   # set before the workers fork
+    from corners import corner_case, corner_checksum
+    hd, pd, params, tracers, ranks, rsd = corner_case(name)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')   # divisions by a zero sigma, NaN comparisons: the reference's own arithmetic
+        with np.errstate(all='ignore'):
+            try:
+                mock = G.gen_gal_cat({k: v.copy() for k, v in hd.items()}, {k: v.copy() for k, v in pd.items()}, tracers,
+                                     params, Nthread=nthread, enable_ranks=ranks, rsd=rsd, write_to_disk=False)
+            except Exception as e:   # reported for every case at once by gen_corners
+                return name, repr(e), None
+    return name, corner_checksum(hd, pd), mock_digest(mock)
+
+
+def gen_corners(G):
+    """the corner cases of tests/corners.py (parameters outside the priors, catalogues outside the key window) through the
+    shimmed reference with Nthread=1, kept as digests like the sweep.  Every case is also run with Nthread=4 and must give
+    the same catalogue - a case the reference itself does not pin is not a test case.  The cases are independent: they are
+    spread over worker processes, the file is written in list order."""
+    from concurrent.futures import ProcessPoolExecutor
+    import multiprocessing
+    sys.path.insert(0, str(REPO / 'tests'))
+    from corners import CORNERS
+    _corner_digest.G = G
+    jobs = [(name, nt) for name in CORNERS for nt in (1, 4)]
+    with ProcessPoolExecutor(max_workers=min(8, os.cpu_count() or 1), mp_context=multiprocessing.get_context('fork')) as ex:
+        res = list(ex.map(_corner_digest, jobs))
+    failed = {name: cks for name, cks, dig in res if dig is None}
+    assert not failed, f'the reference does not run: {failed}'
+    out = {}
+    for (name, cks, dig), (_, _, dig4) in zip(res[0::2], res[1::2]):
+        for tr in dig:
+            assert dig[tr][:2] == dig4[tr][:2] and np.array_equal(dig[tr][2], dig4[tr][2]), f'{name}: Nthread 1 and 4 differ'
+        out[f'{name}.checksum'] = np.float64(cks)
+        for tr, (n, nc, sha) in dig.items():
+            out[f'{name}.{tr}.n'], out[f'{name}.{tr}.ncent'], out[f'{name}.{tr}.sha'] = np.int64(n), np.int64(nc), sha
+        print('corner', name, {tr: d[:2] for tr, d in dig.items()})
+    np.savez_compressed(GOLD / 'hod_corners.npz', **out)
+    print('hod_corners written')
+
+
 def gen_catalog():
     """Catalogue side: the reference's unpack_rvint / unpack_pids on the Mini_N64_L32 subsample
     files (tests/Mini_N64_L32/halos/z0.000/{halo,field}_{rv,pid}_A) and do_Menv_from_tree on the Mini halos and on
@@ -1047,7 +1090,7 @@ def gen_staging_inputs():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['hod', 'tsc', 'power', 'helpers', 'exports', 'catalog', 'sweep', 'ngal', 'pairs', 'prepare', 'mini', 'power64', 'staging']
+    which = sys.argv[1:] or ['hod', 'tsc', 'power', 'helpers', 'exports', 'catalog', 'sweep', 'corners', 'ngal', 'pairs', 'prepare', 'mini', 'power64', 'staging']
     G, T, P, C = import_reference()
     GOLD.mkdir(parents=True, exist_ok=True)
     if 'hod' in which:
@@ -1068,6 +1111,8 @@ if __name__ == '__main__':
         gen_catalog()
     if 'sweep' in which:
         gen_sweep(G)
+    if 'corners' in which:
+        gen_corners(G)
     if 'ngal' in which:
         gen_ngal()
     if 'pairs' in which:

@@ -22,6 +22,8 @@ static SatPre make_pre(const abacus_hod_params *p) {   // as abacus_hod_populate
 
 extern "C" {
 
+int cls_usable(const abacus_hod_params *p) { return cls_params_finite(*p); }
+
 void cls_cent(const abacus_hod_params *p, int64_t n, const double *mass, const double *multis, const double *randoms,
               const double *deltac, const double *fenv, const double *shear, int8_t *out) {
     ClsConst c;

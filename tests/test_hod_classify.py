@@ -8,6 +8,7 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+from corners import CORNERS, corner_case
 from sweep import sweep_case
 
 from abacusutils_amd import synth
@@ -44,8 +45,13 @@ def _classify(cls, hd, pd, p, keep_c):
     return oc, os_
 
 
-def _check(cls, hd, pd, params, tracers, enable_ranks, max_undecided=2e-3):
+def _check(cls, hd, pd, params, tracers, enable_ranks, max_undecided=2e-3, usable=True):
+    """`usable`: what cls_params_finite must report - with a non-finite parameter (or sigma = 0) the populate leaves the
+    classifier off and every candidate takes the float64 chain; there is then nothing to compare"""
     from oracle import oracle
+    assert bool(cls.cls_usable(C.byref(marshal_params(tracers, params, enable_ranks, True)))) == usable
+    if not usable:
+        return 1.0, 1.0
     _, kc, ks = oracle.gen_gal_cat(hd, pd, tracers, params, Nthread=4, enable_ranks=enable_ranks, rsd=True, return_keep=True)
     p = marshal_params(tracers, params, enable_ranks, True)
     oc, os_ = _classify(cls, hd, pd, p, kc)
@@ -64,6 +70,16 @@ def test_classifier_never_contradicts_the_oracle_sweep(cls, seed):
     _check(cls, hd, pd, params, tracers, enable_ranks)
 
 
+@pytest.mark.parametrize('name', CORNERS)
+def test_classifier_never_contradicts_the_oracle_corners(cls, name):
+    """the parameter and catalogue corners of tests/corners.py: NaN / zero / negative sigma, alpha < 0, rank factors changing
+    sign, masses, weights and environments the bands were not tuned for.  Undecided objects only cost time (they take the
+    float64 chain), so their fraction is not bounded here.  A NaN parameter or sigma = 0 must switch the classifier off."""
+    hd, pd, params, tracers, enable_ranks, _ = corner_case(name)
+    _check(cls, hd, pd, params, tracers, enable_ranks, max_undecided=1.0,
+           usable=not name.startswith(('nan_sigma', 'nan_cut', 'sigma_zero')))
+
+
 def test_classifier_production_mix_and_lrg(cls):
     hd, pd, params = synth.synth_hod_inputs(400000, 400000, seed=600, with_ranks=True)
     u1 = _check(cls, hd, pd, params, synth.PRODUCTION_TRACERS, True)
@@ -71,15 +87,16 @@ def test_classifier_production_mix_and_lrg(cls):
     assert max(u1 + u2) < 5e-4
 
 
-@pytest.mark.parametrize('case', ['narrow_sigma', 'negative_elg', 'neg_weights', 'float32_randoms', 'tiny_markers', 'alpha_zero'])
+@pytest.mark.parametrize('case', ['narrow_sigma', 'negative_elg', 'neg_weights', 'float32_randoms', 'tiny_markers', 'alpha_zero',
+                                  'nan_sigma_zero_randoms'])
 def test_classifier_edge_cases(cls, case):
     """parameter corners: very narrow erfc transitions, a negative ELG amplitude (p_max < 1/Q: the chain is not monotone),
     negative / zero multiplicities and weights, float32-quantised randoms including exact zeros (what `reseed` draws),
-    occupations deep in the erfc tail, alpha = 0"""
+    occupations deep in the erfc tail, alpha = 0, a NaN LRG marker in front of finite ELG / QSO terms with randoms of exactly 0"""
     rng = np.random.default_rng(5)
     hd, pd, params = synth.synth_hod_inputs(200000, 200000, seed=77, with_ranks=True)
     tracers = {k: dict(v) for k, v in synth.PRODUCTION_TRACERS.items()}
-    lim = 2e-3
+    lim, usable = 2e-3, True
     if case == 'narrow_sigma':
         tracers['LRG']['sigma'] = 0.004
         tracers['QSO']['sigma'] = 0.01
@@ -106,8 +123,13 @@ def test_classifier_edge_cases(cls, case):
         hd['hrandoms'] = hd['hrandoms'] * 10.0 ** rng.uniform(-40, 0, len(hd['hrandoms']))
         pd['prandoms'] = pd['prandoms'] * 10.0 ** rng.uniform(-40, 0, len(pd['prandoms']))
         lim = 0.9      # randoms spread over 40 decades sit inside the absolute floor of the bands by construction
+    elif case == 'nan_sigma_zero_randoms':
+        tracers['LRG']['sigma'] = float('nan')
+        hd['hrandoms'][::14] = 0.0
+        pd['prandoms'][::10] = 0.0
+        usable = False   # the classifier would decide from the finite factors of the LRG term: it must be off
     elif case == 'alpha_zero':
         tracers['QSO']['alpha'] = 0.0
         tracers['ELG']['alpha_EE'] = 0.0
         tracers['ELG']['kappa'] = 0.0
-    _check(cls, hd, pd, params, tracers, True, max_undecided=lim)
+    _check(cls, hd, pd, params, tracers, True, max_undecided=lim, usable=usable)
