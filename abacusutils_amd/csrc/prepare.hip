@@ -123,6 +123,10 @@ __global__ void prep_part_randoms(int64_t n, const long long *__restrict__ index
     }
 }
 
+// a halo's slice [a, a + n) of the particle array: every kernel that walks one tests it first (a slice that fails is reported by
+// prep_fill_host and walked by nobody - the kernels behind it run before the flag is read back)
+__device__ __forceinline__ bool slice_inside(long long a, long long n, int64_t npart) { return a >= 0 && a <= npart && n <= npart - a; }
+
 // one wave per halo: host index of the halo's particles; sort key (candidate rank << 32 | Philox word) of candidates
 __global__ __launch_bounds__(256) void prep_fill_host(const long long *__restrict__ pstart, const long long *__restrict__ pnum,
                                                       const unsigned char *__restrict__ hmask, int64_t nh, int64_t npart,
@@ -130,11 +134,12 @@ __global__ __launch_bounds__(256) void prep_fill_host(const long long *__restric
     const int lane = threadIdx.x & 63;
     for (int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < nh; j += (int64_t)gridDim.x * 4) {
         if (!hmask[j] || pnum[j] <= 0) continue;
-        const long long a = pstart[j], b = a + pnum[j];
-        if (a < 0 || b > npart) {
+        const long long a = pstart[j];
+        if (!slice_inside(a, pnum[j], npart)) {
             if (lane == 0) atomicOr(bad, 1);
             continue;
         }
+        const long long b = a + pnum[j];
         for (long long q = a + lane; q < b; q += 64) host[q] = (int)j;
     }
 }
@@ -178,11 +183,11 @@ __global__ void prep_cand_count(const unsigned char *__restrict__ hmask, const l
 // one wave per halo: kept particles of the halo
 __global__ __launch_bounds__(256) void prep_count(const long long *__restrict__ pstart, const long long *__restrict__ pnum,
                                                   const unsigned char *__restrict__ hmask, const unsigned char *__restrict__ submask,
-                                                  int64_t nh, long long *__restrict__ kept) {
+                                                  int64_t nh, int64_t npart, long long *__restrict__ kept) {
     const int lane = threadIdx.x & 63;
     for (int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < nh; j += (int64_t)gridDim.x * 4) {
         long long c = 0;
-        if (hmask[j] && pnum[j] > 0)
+        if (hmask[j] && pnum[j] > 0 && slice_inside(pstart[j], pnum[j], npart))
             for (long long q = pstart[j] + lane; q < pstart[j] + pnum[j]; q += 64) c += submask[q];
         for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
         if (lane == 0) kept[j] = c;
@@ -220,6 +225,7 @@ struct RankArgs {
     const unsigned int *N;
     const float *r25, *r98;
     const long long *pstart, *pnum, *kept, *kstart;
+    int64_t npart;
     const long long *sel_idx;            // kept particles in output order (ascending input index: halo after halo)
     double Mpart, h;
     double *ranks, *ranksv, *ranksp, *ranksr, *ranksc;   // (n_sel)
@@ -266,7 +272,9 @@ __global__ __launch_bounds__(256) void prep_ranks(RankArgs A, int nwork) {
             const float d2 = (rx * rx + ry * ry) + rz * rz;    // np.sum(r_rel**2, axis=1) in float32
             const float vx = A.vel[3 * q] - hvx, vy = A.vel[3 * q + 1] - hvy, vz = A.vel[3 * q + 2] - hvz;
             const float v2 = (vx * vx + vy * vy) + vz * vz;
-            const float r0 = __fsqrt_rn(d2);
+            // sqrtf, not __fsqrt_rn: the intrinsic compiles to the bare v_sqrt_f32 (1 ulp), np.sqrt rounds correctly - one ulp of r0
+            // is two of vel_rad, and v_tan2 = v2 - vel_rad^2 cancels: the perihelion key of a nearly radial orbit moved by 3e-4
+            const float r0 = sqrtf(d2);
             const float nx = rx / r0, ny = ry / r0, nz = rz / r0;
             const float vrad = (vx * nx + vy * ny) + vz * nz;
             const float vrad2 = vrad * vrad, vtan2 = v2 - vrad2;
@@ -280,7 +288,7 @@ __global__ __launch_bounds__(256) void prep_ranks(RankArgs A, int nwork) {
             float x2f = vtan2 / Af;
             const float Bf = (float)log((double)(1.f + r0k / rs));
             // first iteration: float32 until alpha (float64) enters (:958-965)
-            const float ox = __fsqrt_rn(x2f);
+            const float ox = sqrtf(x2f);
             float lg = ox * r0k;
             lg = lg / rs;
             lg = 1.f + lg;
@@ -303,7 +311,7 @@ __global__ __launch_bounds__(256) void prep_ranks(RankArgs A, int nwork) {
         }
         __syncthreads();
         // nearest other particle among ALL subsample particles of the halo (cKDTree.query(k=2)[0][:, 1], :912-913)
-        const long long a = A.pstart[j], n_in = A.pnum[j];
+        const long long a = A.pstart[j], n_in = slice_inside(A.pstart[j], A.pnum[j], A.npart) ? A.pnum[j] : 0;
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         for (int i = wave; i < k; i += blockDim.x / 64) {
             const long long self = A.sel_idx[o0 + i];
@@ -433,6 +441,11 @@ struct SlabOut {
     void clear();
 };
 SlabOut g_slab;
+// a call of abacus_prepare_slab that fails on any path leaves no prepared slab behind (dismissed on success only)
+struct SlabGuard {
+    bool keep = false;
+    ~SlabGuard();
+};
 // prep_ranks (2.7 of the slab's 4 ms of kernels) runs on a stream of its own, so that the copies of the other columns - the copy
 // engine - go out under it; with the profiler on it stays on the library stream (whose event pairs time it)
 hipStream_t g_slab_side = nullptr;
@@ -441,6 +454,10 @@ void SlabOut::clear() {
     if (ranks_on_side && g_slab_side) (void)hipStreamSynchronize(g_slab_side);   // nothing may still read what goes back to the pool
     delete tmp;
     *this = SlabOut();
+}
+
+SlabGuard::~SlabGuard() {
+    if (!keep) g_slab.clear();
 }
 
 template <int W>
@@ -556,7 +573,7 @@ int abacus_prepare_particles(int64_t nh, const uint8_t *hmask, const int64_t *ps
     ABACUS_TRY(tmp.alloc(&d_kept, (size_t)nh));
     ABACUS_TRY(tmp.alloc(&d_kstart, (size_t)nh));
     ABACUS_LAUNCH("prep_count", prep_count, dim3((unsigned int)std::min<int64_t>(ceil_div(nh, 4), 256 * 32)), dim3(256), 0, d_pstart,
-                  d_pnum, d_hmask, d_sub, nh, d_kept);
+                  d_pnum, d_hmask, d_sub, nh, npart, d_kept);
     ABACUS_TRY(exclusive_sum(d_kept, d_kstart, nh, tmp));
     double *d_psn, *d_pnn;
     ABACUS_TRY(tmp.alloc(&d_psn, (size_t)nh));
@@ -623,7 +640,7 @@ int abacus_prepare_particles(int64_t nh, const uint8_t *hmask, const int64_t *ps
             if (lds > 160 * 1024) return fail("abacus_prepare_particles: %d kept particles in one halo exceed the rank kernel's LDS", cnt[1]);
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(prep_ranks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             A.pos = d_pos, A.vel = d_vel, A.hpos = d_hpos, A.hvel = d_hvel, A.N = d_N, A.r25 = d_r25, A.r98 = d_r98;
-            A.pstart = d_pstart, A.pnum = d_pnum, A.kept = d_kept, A.kstart = d_kstart, A.sel_idx = d_sidx;
+            A.pstart = d_pstart, A.pnum = d_pnum, A.npart = npart, A.kept = d_kept, A.kstart = d_kstart, A.sel_idx = d_sidx;
             A.Mpart = Mpart, A.h = h;
             A.ranks = d_r[0], A.ranksv = d_r[1], A.ranksp = d_r[2], A.ranksr = d_r[3], A.ranksc = d_r[4];
             A.work = d_work, A.kmax = cnt[1];
@@ -678,6 +695,8 @@ int abacus_prepare_randoms(int64_t n, const int64_t *index, int64_t index0, uint
 // both paths produce identical tables (tests/test_prepare_gpu.py).
 int abacus_prepare_slab(const abacus_prepare_slab_args *a, int64_t *n_halo_kept, int64_t *n_part_kept, uint8_t *mask_out) {
     ABACUS_ENTER();
+    g_slab.clear();      // whatever an earlier call left: gone before this one can fail
+    SlabGuard guard;
     if (!a || !n_halo_kept || !n_part_kept) return fail("abacus_prepare_slab: null argument");
     const int64_t nh = a->nh, npart = a->npart;
     if (nh < 0 || npart < 0) return fail("abacus_prepare_slab: negative size");
@@ -688,10 +707,12 @@ int abacus_prepare_slab(const abacus_prepare_slab_args *a, int64_t *n_halo_kept,
     if (a->n_edges != 0 && (a->n_edges < 2 || a->n_edges > 60000 || !a->mbins)) return fail("abacus_prepare_slab: %d mass-bin edges", a->n_edges);
     for (int b = 0; b + 1 < a->n_edges; b++)
         if (!(a->mbins[b + 1] > a->mbins[b])) return fail("abacus_prepare_slab: the mass bin edges must increase");
-    g_slab.clear();
     *n_halo_kept = *n_part_kept = 0;
-    if (nh == 0) return 0;
-    g_slab.tmp = new Tmp();
+    g_slab.tmp = new Tmp();      // (an empty slab leaves an empty table set: the fetch copies nothing)
+    if (nh == 0) {
+        guard.keep = true;
+        return 0;
+    }
     Tmp &t = *g_slab.tmp;
     Tmp &w = t;       // (work arrays too stay until the fetch: the rank kernel reads them on a stream of its own)
     const size_t np1 = (size_t)std::max<int64_t>(npart, 1);
@@ -777,7 +798,7 @@ int abacus_prepare_slab(const abacus_prepare_slab_args *a, int64_t *n_halo_kept,
     ABACUS_TRY(w.alloc(&d_kept, (size_t)nh));
     ABACUS_TRY(w.alloc(&d_kstart, (size_t)nh));
     ABACUS_LAUNCH("prep_count", prep_count, dim3((unsigned int)std::min<int64_t>(ceil_div(nh, 4), 256 * 32)), dim3(256), 0, dps, dpn,
-                  (const unsigned char *)d_hmask, (const unsigned char *)d_sub, nh, d_kept);
+                  (const unsigned char *)d_hmask, (const unsigned char *)d_sub, nh, npart, d_kept);
     ABACUS_TRY(exclusive_sum(d_kept, d_kstart, nh, w));
     double *d_psn, *d_pnn;
     ABACUS_TRY(w.alloc(&d_psn, (size_t)nh));
@@ -809,10 +830,7 @@ int abacus_prepare_slab(const abacus_prepare_slab_args *a, int64_t *n_halo_kept,
     HIP_TRY(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, stream()));
     if (mask_out) HIP_TRY(hipMemcpyAsync(mask_out, d_hmask, (size_t)nh, hipMemcpyDeviceToHost, stream()));
     HIP_TRY(hipStreamSynchronize(stream()));
-    if (bad) {
-        g_slab.clear();
-        return fail("abacus_prepare_slab: a halo's [npstartA, npstartA + npoutA) lies outside the particle array");
-    }
+    if (bad) return fail("abacus_prepare_slab: a halo's [npstartA, npstartA + npoutA) lies outside the particle array");
     const int64_t ns = tail[0] + tail[1], nk = tail[2] + tail[3];
     g_slab.nk = nk, g_slab.ns = ns, g_slab.want_ranks = a->want_ranks;
     *n_halo_kept = nk, *n_part_kept = ns;
@@ -848,13 +866,11 @@ int abacus_prepare_slab(const abacus_prepare_slab_args *a, int64_t *n_halo_kept,
                 d_r[c] = (double *)o;
             }
             const size_t lds = (size_t)((3 * (size_t)cnt[1] * 4 + 15) / 16) * 16 + (size_t)5 * cnt[1] * 8;
-            if (cnt[0] > 0 && lds > 160 * 1024) {
-                g_slab.clear();
+            if (cnt[0] > 0 && lds > 160 * 1024)
                 return fail("abacus_prepare_slab: %d kept particles in one halo exceed the rank kernel's LDS", cnt[1]);
-            }
             RankArgs A;
             A.pos = dpos, A.vel = dvel, A.hpos = dx, A.hvel = dv, A.N = dN, A.r25 = dr25, A.r98 = dr98;
-            A.pstart = dps, A.pnum = dpn, A.kept = d_kept, A.kstart = d_kstart, A.sel_idx = d_sidx;
+            A.pstart = dps, A.pnum = dpn, A.npart = npart, A.kept = d_kept, A.kstart = d_kstart, A.sel_idx = d_sidx;
             A.Mpart = a->Mpart, A.h = a->h;
             A.ranks = d_r[0], A.ranksv = d_r[1], A.ranksp = d_r[2], A.ranksr = d_r[3], A.ranksc = d_r[4];
             A.work = d_work, A.kmax = cnt[1];
@@ -953,6 +969,7 @@ int abacus_prepare_slab(const abacus_prepare_slab_args *a, int64_t *n_halo_kept,
                       (const double *)d_scale, d_rnd, d_rexp, d_rgaus);
     }
     // the work arrays go back to the pool behind the kernels above (one stream); the table columns stay until the fetch
+    guard.keep = true;
     return 0;
 }
 

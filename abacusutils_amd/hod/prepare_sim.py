@@ -297,6 +297,26 @@ _SLAB_PART_OUT = ((('pos', np.float32, (3,)), ('vel', np.float32, (3,))) + tuple
                      ('halo_shear', np.float64, ())))
 
 
+_SLAB_ANY_INT = ('npstartA', 'npoutA')     # the readers hand these over as uint64 / uint32: any integer dtype goes in as int64
+
+
+def _empty_tables(halos, want_ranks):
+    """the two tables of a slab without halos: the keys, dtypes and row shapes of a slab with some"""
+    id_col = halos['id']
+    id_dtype = id_col.dtype if isinstance(id_col, _lib.DeviceArray) else np.asarray(id_col).dtype
+    spec = {name: ((id_dtype if dt is None else dt), tail) for name, dt, tail in _SLAB_HALO_OUT}
+    H = {}
+    for k, v in halos.items():
+        if k in spec:
+            H[k] = np.empty((0,) + spec[k][1], dtype=spec[k][0])
+        else:
+            H[k] = np.empty((0,) + tuple(v.shape[1:]), dtype=v.dtype)
+    for name, _, _ in _SLAB_HALO_OUT[10:]:
+        H[name] = np.empty((0,) + spec[name][1], dtype=spec[name][0])
+    P = {name: np.empty((0,) + tail, dtype=dt) for name, dt, tail in _SLAB_PART_OUT if want_ranks or name not in RANK_COLUMNS}
+    return H, P, np.zeros(0, dtype=bool)
+
+
 def _slab_col(a, dtype, keep):
     """pointer of one input column: a device array is used where it is, anything else as a contiguous NumPy array of `dtype`"""
     if isinstance(a, _lib.DeviceArray):
@@ -323,7 +343,10 @@ def _prepare_slab_device(halos, parts, Mpart, h, MT, want_ranks, want_AB, fenv_r
     a = _SlabArgs()
     a.nh, a.npart = nh, npart
     for field, (name, dt, _) in zip(('N', 'x', 'v', 'r25', 'r90', 'r98', 'npstartA', 'npoutA', 'id', 'sigmav'), _SLAB_HALO_IN):
-        setattr(a, field, _slab_col(halos[name], dt, keep))
+        col = halos[name]
+        if name in _SLAB_ANY_INT and isinstance(col, _lib.DeviceArray) and col.dtype != np.dtype(dt):
+            col = col.get()          # another integer width in HBM: nh values, cast on the host and uploaded with the rest
+        setattr(a, field, _slab_col(col, dt, keep))
     a.pos, a.vel = _slab_col(parts['pos'], np.float32, keep), _slab_col(parts['vel'], np.float32, keep)
     a.fenv_rank = None if fenv_rank is None else _slab_col(fenv_rank, np.float64, keep)
     a.shear_rank = None if shear_rank is None else _slab_col(shear_rank, np.float64, keep)
@@ -394,11 +417,17 @@ def prepare_slab_arrays(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=Tr
     if numpy_mode and rng != 'numpy':
         raise ValueError("rng must be 'numpy' (the reference's global generator) or an integer seed")
     seed = 0 if numpy_mode else int(rng) & (2**64 - 1)
-    def _fits(col, dt):      # the device path returns the library's dtypes: only for inputs that already carry them
+    if not numpy_mode and nh == 0:     # an empty slab or shard: nothing to draw, nothing for the library to do
+        return _empty_tables(halos, want_ranks)
+
+    def _fits(col, dt, any_int=False):      # the device path returns the library's dtypes: only for inputs that already carry them
         d = col.dtype if isinstance(col, _lib.DeviceArray) else np.asarray(col).dtype
+        if any_int:          # cast to int64 on the way in; the outputs are float64 whatever came in
+            return d.kind in 'iu'
         return (d.kind in 'iu' and d.itemsize == 8) if dt is None else d == np.dtype(dt)
 
-    if (not numpy_mode and not _lib.get_option('prep_columnwise') and all(k in halos and _fits(halos[k], dt) for k, dt, _ in _SLAB_HALO_IN)
+    if (not numpy_mode and not _lib.get_option('prep_columnwise')
+            and all(k in halos and _fits(halos[k], dt, k in _SLAB_ANY_INT) for k, dt, _ in _SLAB_HALO_IN)
             and _fits(parts['pos'], np.float32) and _fits(parts['vel'], np.float32)):
         # every draw is made on the device: the slab goes through HBM once (abacus_prepare_slab); the per-halo rank columns that need
         # host-side inputs (light-cone environment, shear) are computed as before and handed over

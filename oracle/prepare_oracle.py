@@ -9,7 +9,10 @@ Pinned by golden vectors of the REFERENCE's own prepare_slab run under the shims
 slabs (tests/golden/prepare_sim.npz, tests/test_oracle_prepare.py).  Random numbers: the reference consumes NumPy's global
 legacy generator in a fixed order (:349-350 seeding, :449 halo mask, :163/:172 one `choice` per kept halo, :984-996 halo
 randoms, :1029 particle randoms); `rng='numpy'` below consumes it in exactly that order, so that a run seeded like the
-reference is comparable value for value.
+reference is comparable value for value.  `rng=<seed>` draws what the DEVICE draws instead (abacusutils_amd.hod.prepare_sim with an
+integer seed: Philox4x32-10 functions of the seed and the global halo / particle index, restated at the end of this file); every
+deterministic line - subsample_halos, particle_target, rank_in_mass_bins, satellite_ranks, the offsets, the assembly of the tables -
+is shared between the two modes, so the reference-held goldens pin the code the seeded mode runs.
 """
 import numpy as np
 from scipy.spatial import cKDTree
@@ -58,12 +61,14 @@ def rank_in_mass_bins(values, masses, mbins, denom='max'):
     return out
 
 
-def satellite_ranks(ppos, pvel, hpos, hvel, allpos, N, Mpart, h, r25, r98):
+def satellite_ranks(ppos, pvel, hpos, hvel, allpos, N, Mpart, h, r25, r98, stable=False, log=np.log):
     """the five rank columns of one halo's selected particles (:899-977): nearest-neighbour distance among ALL subsample
     particles of the halo, distance and speed relative to the halo, radial velocity, NFW perihelion - each as
-    (rank - mean rank) / mean rank"""
+    (rank - mean rank) / mean rank.  stable: equal keys rank by particle index, NaN last (the device's rule, prep_ranks'
+    key_before); the reference's order among equal keys is whatever NumPy's unstable sort leaves.  log: the logarithm of the
+    float32 values of the perihelion iteration (tests compare NumPy's float32 log with a float64 log rounded once)"""
     def norm(key):
-        r = key.argsort().argsort()
+        r = key.argsort(kind='stable' if stable else None).argsort()
         return (r - np.mean(r)) / np.mean(r)
 
     tree = cKDTree(allpos)
@@ -82,30 +87,101 @@ def satellite_ranks(ppos, pvel, hpos, hvel, allpos, N, Mpart, h, r25, r98):
     rs = r25
     c = r98 / rs
     r0_kpc = r0 * 1000
-    alpha = 1.0 / (np.log(1 + c) - c / (1 + c)) * 2 * 6.67e-11 * m * 2e30 / r0_kpc / 3.086e19 / 1e6
+    alpha = 1.0 / (log(1 + c) - c / (1 + c)) * 2 * 6.67e-11 * m * 2e30 / r0_kpc / 3.086e19 / 1e6
     x2 = v_tan2 / (v_tan2 + v_rad2)
     A = v_tan2 + v_rad2
-    B = np.log(1 + r0_kpc / rs)
+    B = log(1 + r0_kpc / rs)
     with np.errstate(all='ignore'):
         for _ in range(20):
             oldx = np.sqrt(x2)
-            x2 = v_tan2 / (A + alpha * (np.log(1 + oldx * r0_kpc / rs) / oldx - B))
+            x2 = v_tan2 / (A + alpha * (log(1 + oldx * r0_kpc / rs) / oldx - B))
     x2[np.isnan(x2)] = 1
     ranksp = norm(r0_kpc ** 2 * x2)
     return ranks, ranksv, ranksp, ranksr, ranksc
 
 
+class NumpyDraws:
+    """the reference's draws: NumPy's global legacy generator, consumed in the reference's order"""
+    stable_ranks = False
+
+    def start(self, npart):
+        pass
+
+    def halo_mask(self, p_halos):
+        return np.random.random(len(p_halos)) < p_halos                                      # (:449)
+
+    def subset(self, a, n_in, ntarget):
+        sub = np.zeros(n_in, dtype=bool)
+        sub[np.random.choice(n_in, ntarget, replace=False)] = True                           # (:163,172)
+        return sub
+
+    def halo_randoms(self, sigmav3d, mask_halos):
+        nh = len(sigmav3d)
+        sig = np.repeat(sigmav3d, 3).reshape((-1, 3)) / np.sqrt(3)
+        rnd = np.random.random(nh)                                                           # (:984)
+        rexp = (np.random.randint(0, 2, size=(nh, 3)) * 2 - 1) * np.random.exponential(scale=sig, size=(nh, 3))
+        return rnd, rexp, np.random.normal(loc=0, scale=sig, size=(nh, 3))
+
+    def part_randoms(self, kept_index):
+        return np.random.random(len(kept_index))                                             # (:1029)
+
+
+class SeededDraws:
+    """the device's draws (csrc/prepare.hip): halo mask from stream 6, the selection from the first word of stream 3 (a halo keeps
+    the `ntarget` particles of its slice with the smallest words, equal words by index - one stable sort on the device), halo
+    randoms from stream 4 for the KEPT halos only, particle randoms from stream 5 - all functions of (seed, global index)"""
+    stable_ranks = True
+
+    def __init__(self, seed, halo_index0=0, part_index0=0):
+        self.seed, self.halo_index0, self.part_index0 = int(seed) & (2**64 - 1), int(halo_index0), int(part_index0)
+
+    def start(self, npart):
+        self.words = philox_words(self.seed, self.part_index0 + np.arange(npart, dtype=np.int64), 3)[:, 0]
+
+    def halo_mask(self, p_halos):
+        return device_uniform_vec(self.seed, self.halo_index0 + np.arange(len(p_halos), dtype=np.int64), 6) < p_halos
+
+    def subset(self, a, n_in, ntarget):
+        sub = np.zeros(n_in, dtype=bool)
+        if ntarget >= n_in:
+            sub[:] = True
+        elif ntarget > 0:
+            sub[np.argsort(self.words[a:a + n_in], kind='stable')[:ntarget]] = True
+        return sub
+
+    def halo_randoms(self, sigmav3d, mask_halos):
+        nh = len(sigmav3d)
+        kept = np.flatnonzero(mask_halos)
+        rnd, rexp, rg = np.zeros(nh), np.zeros((nh, 3)), np.zeros((nh, 3))
+        scale = np.asarray(sigmav3d)[kept].astype(np.float64) / np.sqrt(3)
+        rnd[kept], rexp[kept], rg[kept] = device_halo_randoms(self.seed, kept + self.halo_index0, scale)
+        return rnd, rexp, rg
+
+    def part_randoms(self, kept_index):
+        return device_uniform_vec(self.seed, self.part_index0 + np.asarray(kept_index, dtype=np.int64), 5)
+
+
 def prepare_slab_core(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=True, Menv=None, shearmark=None, Lbox=None,
-                      mcut=1e11, halo_lc=False):
+                      mcut=1e11, halo_lc=False, rng='numpy', halo_index0=0, part_index0=0, draws=None, rank_log=np.log):
     """halos / parts: dicts of columns as CompaSOHaloCatalog hands them over (abacusutils_amd.synth.synth_compaso_slabs).
     Menv: the raw environment masses of the slab's halos (do_Menv_from_tree; the reference writes them to the env file for the
     global ranking later, :748-756) - unused here except for light cones, where fenv_rank is ranked per slab (:618).
     Returns (halo table of the KEPT halos, particle table of the kept particles) as dicts with the field names of the
-    reference's HDF5 datasets (:1001-1045), plus `mask_halos` over the input halos."""
+    reference's HDF5 datasets (:1001-1045), plus `mask_halos` over the input halos.
+    rng: 'numpy' (the reference's draws from NumPy's global generator) or an integer seed (the device's Philox draws of the halos
+    and particles with global indices halo_index0 + row / part_index0 + row); `draws` (tests) replaces the object that draws, `rank_log` the logarithm of
+    satellite_ranks."""
+    if draws is None:
+        if isinstance(rng, str):
+            if rng != 'numpy':
+                raise ValueError("rng must be 'numpy' or an integer seed")
+            draws = NumpyDraws()
+        else:
+            draws = SeededDraws(rng, halo_index0, part_index0)
     nh = len(halos['N'])
     masses = halos['N'] * Mpart
     p_halos = subsample_halos(masses, MT)
-    mask_halos = np.random.random(nh) < p_halos                                              # (:449)
+    mask_halos = draws.halo_mask(p_halos)
     H = {k: v for k, v in halos.items()}
     H['mask_subsample'] = mask_halos
     H['multi_halos'] = 1.0 / p_halos
@@ -131,6 +207,7 @@ def prepare_slab_core(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=True
 
     pstart, pnum = halos['npstartA'], halos['npoutA']
     npart = len(parts['pos'])
+    draws.start(npart)
     mask_parts = np.zeros(npart, dtype=bool)
     host = np.full(npart, -1, dtype=np.int64)
     Np = np.full(npart, -1.0)
@@ -146,7 +223,7 @@ def prepare_slab_core(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=True
         ntarget = particle_target(masses[j], n_in, MT)
         sub = np.zeros(n_in, dtype=bool)
         if ntarget > 0 or (MT and masses[j] >= 1e11) or (not MT and 10 ** np.log10(masses[j]) >= 1e12):
-            sub[np.random.choice(n_in, ntarget, replace=False)] = True                        # (:163,172)
+            sub = draws.subset(a, n_in, ntarget)
         k = int(sub.sum())
         mask_parts[a:a + n_in] = sub
         host[a:a + n_in] = j
@@ -160,14 +237,12 @@ def prepare_slab_core(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=True
                     arr[idx] = 0
                 continue
             r = satellite_ranks(parts['pos'][idx], parts['vel'][idx], halos['x_L2com'][j], halos['v_L2com'][j],
-                                parts['pos'][a:a + n_in], halos['N'][j], Mpart, h, halos['r25_L2com'][j], halos['r98_L2com'][j])
+                                parts['pos'][a:a + n_in], halos['N'][j], Mpart, h, halos['r25_L2com'][j], halos['r98_L2com'][j],
+                                stable=draws.stable_ranks, log=rank_log)
             for name, val in zip(('ranks', 'ranksv', 'ranksp', 'ranksr', 'ranksc'), r):
                 rk[name][idx] = val
     H['npstartA'], H['npoutA'] = pstart_new, pnum_new
-    sig = np.repeat(halos['sigmav3d_L2com'], 3).reshape((-1, 3)) / np.sqrt(3)
-    H['randoms'] = np.random.random(nh)                                                       # (:984)
-    H['randoms_exp'] = (np.random.randint(0, 2, size=(nh, 3)) * 2 - 1) * np.random.exponential(scale=sig, size=(nh, 3))
-    H['randoms_gaus_vrms'] = np.random.normal(loc=0, scale=sig, size=(nh, 3))
+    H['randoms'], H['randoms_exp'], H['randoms_gaus_vrms'] = draws.halo_randoms(halos['sigmav3d_L2com'], mask_halos)   # (:984-996)
     Hk = {k: np.asarray(v)[mask_halos] for k, v in H.items()}
 
     hp = host[mask_parts]
@@ -180,7 +255,7 @@ def prepare_slab_core(halos, parts, Mpart, h, MT, want_ranks=False, want_AB=True
     P['halo_mass'] = masses[hp].astype(np.float64)
     P['Np'] = Np[mask_parts]
     P['halo_id'] = halos['id'][hp].astype(np.int64)
-    P['randoms'] = np.random.random(int(mask_parts.sum()))                                     # (:1029)
+    P['randoms'] = draws.part_randoms(np.flatnonzero(mask_parts))
     P['halo_deltac'] = H['deltac_rank'][hp]
     P['halo_fenv'] = H['fenv_rank'][hp]
     P['halo_shear'] = H['shear_rank'][hp]
@@ -286,6 +361,38 @@ def device_uniform(seed, index, stream):
         w = oracle.philox4x32_10((int(g) & 0xFFFFFFFF, (int(g) >> 32) & 0xFFFFFFFF, stream, 0), key)
         out[r] = _u53(w[0], w[1])
     return out
+
+
+def philox4x32_10_vec(ctr, key):
+    """Philox4x32-10 blocks of many counters at once: ctr (n, 4), key (2,) or (n, 2) of 32-bit words -> (n, 4) uint32.  uint64
+    arithmetic (a 32 x 32 bit product fits); held word for word to the C restatement and the published vectors by
+    tests/test_oracle_prepare.py"""
+    ctr = np.asarray(ctr).astype(np.uint64)
+    key = np.asarray(key).astype(np.uint64)
+    M = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (ctr[..., i] & M for i in range(4))
+    k0, k1 = key[..., 0] & M, key[..., 1] & M
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def philox_words(seed, index, stream, block=0):
+    """the four words of block `block` of `stream` for the objects of global indices `index` (counter = (index low, index high,
+    stream, block), key = the two halves of the seed)"""
+    g = np.asarray(index, dtype=np.int64).view(np.uint64)
+    ctr = np.empty((len(g), 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1], ctr[:, 2], ctr[:, 3] = g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), stream, block
+    seed = int(seed) & (2**64 - 1)
+    return philox4x32_10_vec(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+
+
+def device_uniform_vec(seed, index, stream):
+    """device_uniform for whole slabs"""
+    w = philox_words(seed, index, stream).astype(np.uint64)
+    return (((w[:, 0] >> np.uint64(5)) << np.uint64(26)) | (w[:, 1] >> np.uint64(6))).astype(np.float64) * 1.1102230246251565e-16
 
 
 def device_halo_randoms(seed, index, scale):

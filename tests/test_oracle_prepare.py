@@ -138,3 +138,180 @@ def test_device_stream_restatement_is_sane():
     np.testing.assert_array_equal(g2[::-1], g)
     u = po.device_uniform(9, idx, 5)
     assert 0 <= u.min() and u.max() < 1 and abs(u.mean() - 0.5) < 0.03 and not np.array_equal(u, po.device_uniform(9, idx, 6))
+
+
+# ---- the seeded mode of the restatement (`rng=<seed>`: the device's Philox draws) -------------------------------------------------
+def test_vectorised_philox_is_the_c_restatement():
+    """philox4x32_10_vec on the published known-answer vectors (tests/test_oracle_reseed.py) and word for word against the C
+    restatement on random (counter, key) pairs, counters above 2^32 and a seed with a non-zero upper half included"""
+    from test_oracle_reseed import KAT
+
+    from oracle import oracle
+    for ctr, key, want in KAT:
+        np.testing.assert_array_equal(po.philox4x32_10_vec(np.array([ctr]), np.array(key))[0], np.array(want, dtype=np.uint32))
+    rng = np.random.default_rng(12)
+    ctr = rng.integers(0, 2**32, (400, 4), dtype=np.uint64)
+    key = rng.integers(0, 2**32, (400, 2), dtype=np.uint64)
+    got = po.philox4x32_10_vec(ctr, key)
+    assert got.dtype == np.uint32 and got.shape == (400, 4)
+    for i in range(400):
+        np.testing.assert_array_equal(got[i], oracle.philox4x32_10(ctr[i], key[i]))
+    np.testing.assert_array_equal(po.philox4x32_10_vec(ctr, key[7]), [oracle.philox4x32_10(c, key[7]) for c in ctr])
+    index = np.concatenate([2**32 - 3 + np.arange(6), 2**40 + np.arange(4), [0, 2**63 - 1]]).astype(np.int64)
+    for seed in (5, 2**63 + 5, -1):
+        for stream in (3, 5, 6):
+            w = po.philox_words(seed, index, stream)
+            s = seed & (2**64 - 1)
+            for g, row in zip(index, w):
+                np.testing.assert_array_equal(row, oracle.philox4x32_10((int(g) & 0xFFFFFFFF, int(g) >> 32, stream, 0), (s & 0xFFFFFFFF, s >> 32)))
+            if stream != 3:
+                np.testing.assert_array_equal(po.device_uniform_vec(seed, index, stream), po.device_uniform(s, index, stream))
+
+
+@pytest.mark.parametrize('MT', [True, False])
+def test_seeded_core_shares_the_reference_pinned_code(MT):
+    """the seeded mode with its draws forced to what the 'numpy' mode drew (mask and subsets injected) gives the 'numpy' mode's
+    tables, the random columns aside: everything but the draws is one code, the code the goldens above pin.  Equal rank keys are
+    the one difference - by index in the seeded mode, NumPy's unstable order in the reference's - so a column may differ
+    inside a halo with tied keys, as a permutation"""
+    slabs, header = synth.synth_compaso_slabs(numslabs=1, n_halo=2500, seed=17, lbox=300.0)
+    halos, parts = slabs[0]['halos'], slabs[0]['parts']
+    record = []
+
+    class Recording(po.NumpyDraws):
+        def halo_mask(self, p_halos):
+            record.append(super().halo_mask(p_halos))
+            return record[-1]
+
+        def subset(self, a, n_in, ntarget):
+            record.append(super().subset(a, n_in, ntarget))
+            return record[-1]
+
+    class Replaying(po.SeededDraws):
+        def halo_mask(self, p_halos):
+            return record.pop(0)
+
+        def subset(self, a, n_in, ntarget):
+            return record.pop(0)
+
+    kw = dict(want_ranks=True, want_AB=True, shearmark=shearmark(), Lbox=header['BoxSizeHMpc'])
+    reference_seed(600, 3)
+    with np.errstate(all='ignore'):
+        H0, P0, m0 = po.prepare_slab_core(halos, parts, header['ParticleMassHMsun'], 0.6736, MT, draws=Recording(), **kw)
+        n_draws = len(record)
+        H1, P1, m1 = po.prepare_slab_core(halos, parts, header['ParticleMassHMsun'], 0.6736, MT, draws=Replaying(77, 5, 9), **kw)
+    assert n_draws > 200 and not record
+    np.testing.assert_array_equal(m0, m1)
+    assert list(H0) == list(H1) and list(P0) == list(P1)
+    for got, want in ((H1, H0), (P1, P0)):
+        for k in want:
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+            if k.startswith('randoms'):
+                assert not np.array_equal(got[k], want[k])
+            elif k in ('ranks', 'ranksv', 'ranksp', 'ranksr', 'ranksc'):
+                same = got[k] == want[k]
+                assert same.mean() > 0.99, (k, same.mean())
+                for hid in np.unique(P0['halo_id'][~same]):
+                    sel = P0['halo_id'] == hid
+                    np.testing.assert_array_equal(np.sort(got[k][sel]), np.sort(want[k][sel]))
+            else:
+                np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    # the seeded draws of the random columns: the kept halos' and kept particles' global indices
+    kept = np.flatnonzero(m1)
+    np.testing.assert_array_equal(H1['randoms'][:40], po.device_halo_randoms(77, kept[:40] + 5, halos['sigmav3d_L2com'][kept[:40]] / np.sqrt(3))[0])
+
+
+@pytest.mark.parametrize('MT', [True, False])
+def test_seeded_core_is_invariant_under_sharding(MT):
+    """a slab cut in two, the second half with the halo and particle offsets of its first row: the two masks, selections and
+    random columns concatenated are the whole slab's"""
+    import prepare_corners as pc
+    c = pc.corner('mixed')
+    h0, p0 = 2**32 - 50, 2**33 - 3000
+    kw = dict(want_ranks=True, want_AB=False, rng=2**63 + 5)
+    cut = c.nh // 3
+    pcut = int(c.halos['npstartA'][cut])
+    with np.errstate(all='ignore'):
+        H, P, m = po.prepare_slab_core(c.halos, c.parts, c.Mpart, c.h, MT, halo_index0=h0, part_index0=p0, **kw)
+        first = po.prepare_slab_core({k: v[:cut] for k, v in c.halos.items()}, {k: v[:pcut] for k, v in c.parts.items()}, c.Mpart, c.h,
+                                     MT, halo_index0=h0, part_index0=p0, **kw)
+        second = {k: v[cut:] for k, v in c.halos.items()}
+        second['npstartA'] = second['npstartA'] - pcut
+        second = po.prepare_slab_core(second, {k: v[pcut:] for k, v in c.parts.items()}, c.Mpart, c.h, MT, halo_index0=h0 + cut,
+                                      part_index0=p0 + pcut, **kw)
+    assert 0 < len(first[1]['pos']) < len(P['pos']) and 0 < first[2].sum() < m.sum()
+    np.testing.assert_array_equal(np.concatenate([first[2], second[2]]), m)
+    for k in P:
+        np.testing.assert_array_equal(np.concatenate([first[1][k], second[1][k]]), P[k], err_msg=k)
+    live = second[0]['npstartA'] >= 0
+    second[0]['npstartA'][live] += len(first[1]['pos'])
+    for k in H:
+        np.testing.assert_array_equal(np.concatenate([first[0][k], second[0][k]]), H[k], err_msg=k)
+    # and it is the seed that decides
+    with np.errstate(all='ignore'):
+        other = po.prepare_slab_core(c.halos, c.parts, c.Mpart, c.h, MT, halo_index0=h0, part_index0=p0, want_ranks=False, want_AB=False, rng=6)
+    assert not np.array_equal(other[2], m)
+
+
+def _corner_cases():
+    import prepare_corners as pc
+    return [(name, MT) for name in pc.CORNERS + ['lds_over'] for MT in pc.corner(name).MT]
+
+
+@pytest.mark.parametrize('name,MT', _corner_cases())
+def test_corner_slabs_rank_alike_under_both_float32_logarithms(name, MT):
+    """the perihelion key starts from float32 logarithms: NumPy's float32 log in the reference, a float64 log rounded once on the
+    device.  On the hand-made slabs (a swap in a halo of five cannot hide behind a 1 % rule) the restatement's tables are the same
+    under both, so the device is compared with them exactly (tests/test_prepare_seeded_gpu.py); also what every corner is for"""
+    import prepare_corners as pc
+    c = pc.corner(name)
+    H, P, m = pc.oracle_tables(name, MT)
+    H2, P2, m2 = pc.oracle_tables(name, MT, rank_log=pc.log_rounded_once)
+    for k in P:
+        np.testing.assert_array_equal(P[k], P2[k], err_msg=k)
+    # the tables hang together: offsets, counts, rank columns a permutation of (r - mean) / mean per halo
+    live = H['npoutA'] >= 0
+    np.testing.assert_array_equal(H['npstartA'][live], np.cumsum(H['npoutA'][live]) - H['npoutA'][live])
+    assert int(H['npoutA'][live].sum()) == len(P['pos']) and int(m.sum()) == len(H['N'])
+    for s0, k in list(zip(H['npstartA'][live].astype(int), H['npoutA'][live].astype(int)))[:300]:
+        if k == 0:
+            continue
+        for col in ('ranks', 'ranksv', 'ranksp', 'ranksr', 'ranksc'):
+            want = np.zeros(1) if k == 1 else (np.arange(k) - 0.5 * (k - 1)) / (0.5 * (k - 1))
+            np.testing.assert_allclose(np.sort(P[col][s0:s0 + k]), want, rtol=0, atol=1e-12)
+
+
+def test_corner_slabs_are_the_corners_they_claim():
+    import prepare_corners as pc
+    assert pc.oracle_tables('none_kept', True)[2].sum() == 0 and pc.oracle_tables('none_kept', False)[2].sum() == 0
+    H, P, m = pc.oracle_tables('kept_without_particles', False)
+    assert m.sum() > 60 and len(P['pos']) == 0 and set(H['npoutA']) == {0.0, -1.0}
+    H, P, m = pc.oracle_tables('single_2', False)
+    for col in ('ranks', 'ranksv', 'ranksp', 'ranksr', 'ranksc'):
+        assert sorted(P[col]) == [-1.0, 1.0]
+    H, P, m = pc.oracle_tables('single_1', True)
+    assert all(P[col][0] == 0 for col in ('ranks', 'ranksv', 'ranksp', 'ranksr', 'ranksc'))
+    H, P, m = pc.oracle_tables('many_halos', False)
+    assert m.all() and (H['npoutA'] == 2).sum() > 2048 and (H['npoutA'] == 1).sum() > 4096
+    H, P, m = pc.oracle_tables('mt_cap', True)
+    np.testing.assert_array_equal(H['npoutA'], [100, 100, 100])
+    H, P, m = pc.oracle_tables('lrg_floor', False)
+    np.testing.assert_array_equal(H['npoutA'], [0, 1, 1, 0, 1, 1])
+    H, P, m = pc.oracle_tables('wave_edges', False)
+    kept_in = pc.corner('wave_edges').halos['npoutA'][m]
+    for s in pc.WAVE_SLICES:       # every slice width is there as a partly and as a wholly kept slice
+        out = H['npoutA'][kept_in == s]
+        assert (out == s).any() and ((out > 0) & (out < s)).any() or s <= 2, (s, out)
+    H, P, m = pc.oracle_tables('rank_keys', False)
+    assert m.all() and list(H['npoutA']) == [6, 7, 5, 9, 2]
+    # equal keys rank by index: the two identical particles of the second halo hold neighbouring ranks in every column, the
+    # earlier one first; the nearest neighbour of both lies at distance 0, so they are the first two of ranksc
+    a = int(H['npstartA'][1])
+    for col in ('ranks', 'ranksv', 'ranksp', 'ranksr', 'ranksc'):
+        lo, hi = P[col][a + 1], P[col][a + 4]
+        assert abs((hi - lo) - 1 / 3.0) < 1e-12, (col, lo, hi)
+    assert P['ranksc'][a + 1] == -1.0
+    # the particle on the centre: NaN radial velocity, ranked last
+    assert P['ranksr'][int(H['npstartA'][0]) + 2] == 1.0 and P['ranks'][int(H['npstartA'][0]) + 2] == -1.0
+    sh = pc.shear_field()
+    assert pc.shear_has_no_ties(pc.corner('mixed'), sh)
