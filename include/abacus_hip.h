@@ -728,6 +728,19 @@ int abacus_lcv_power3d(const void *a_padded, const void *b_padded, int n, float 
 int abacus_lcv_combine_k3d(const void *delta_padded, const void *deltamu2_padded, const void *tr_padded, int n, double Lbox, double bias,
                            double f_growth, double D, double R, int reciso, float *pk_tt, float *pk_ll, float *pk_lt);
 
+/* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
+ * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
+ * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
+ * + kvals[i]^2) and mu = kvals[i] / knorm (0 at the origin) in float32, L2 = (3 mu^2 - 1) / 2, L4 = (35 mu^4 - 30 mu^2 + 3) / 8 with
+ * mu^4 = (mu^2)^2, the bin o with kout[o] <= knorm < kout[o + 1] (float32 against the float64 edges), multiplicity m = 1 on the
+ * plane k = 0 and 2 elsewhere.  Per bin, in float64: nmodes += m, ksum += m knorm, S[o][l][l'] += m fl32(fl32(pref_l L_l) L_l')
+ * with pref = 1, 5, 9.  Modes below kout[0] or at and beyond kout[nkout] are left out.  kvals_host: the n float32 wavenumbers of
+ * the mesh as the caller's NumPy forms them (its first n/2 are the half axis); kout_host: nkout + 1 finite, strictly increasing
+ * edges, nkout <= 4096; n even, 2 .. 32766.  One pass, no mesh in memory, O(nkout) device memory.  Host arrays out:
+ * S_host [nkout][3][3], nmodes_host [nkout], ksum_host [nkout]. */
+int abacus_window_moments(int nmesh, const float *kvals_host, const double *kout_host, int nkout, double *S_host /*[nkout][3][3]*/,
+                          double *nmodes_host, double *ksum_host);
+
 #ifdef __cplusplus
 }
 #endif
