@@ -95,7 +95,8 @@ def recon_power(tracer_pos, random_pos, lin, k_bin_edges, mu_bin_edges, poles, p
     `combine_field_spectra_k3D_lcv`.
 
     Positions are (N, 3) in box coordinates and are NOT shifted by `Lbox / 2` (unlike `tracer_power`); reconstruction may leave
-    them a few cells outside [0, Lbox), the deposit wraps them.  NumPy inputs (float32 or float64, deposited as float32) are not
+    them a few cells outside [0, Lbox), the deposit wraps them.  `reconstruction.reconstruct` produces both sets in HBM (it wraps them
+    into the box); an external reconstruction's output is taken as well.  NumPy inputs (float32 or float64, deposited as float32) are not
     modified.  `DeviceArray` inputs must be float32 and may be wrapped into the box IN PLACE by the TSC deposit, as the
     reference's `tsc_parallel` wraps its argument.
 

@@ -728,6 +728,45 @@ int abacus_lcv_power3d(const void *a_padded, const void *b_padded, int n, float 
 int abacus_lcv_combine_k3d(const void *delta_padded, const void *deltamu2_padded, const void *tr_padded, int n, double Lbox, double bias,
                            double f_growth, double D, double R, int reciso, float *pk_tt, float *pk_ll, float *pk_lt);
 
+/* ---------------------------------------------------------------- BAO reconstruction --------------------- */
+/*
+ * Standard plane-parallel reconstruction of a periodic box (line of sight = z) on DEVICE pointers (csrc/zcv.hip, beside the LCV
+ * section whose inputs it produces); every call enqueues on the library stream.  replaces: nothing in the reference - its
+ * get_recon_power takes reconstructed tracers and shifted randoms that an external CPU code made between run_hod and get_recon_power;
+ * this is that step.  Conventions of Chen et al. 2019 (RecSym, RecIso), the ones tools_cv.combine_kaiser_spectra assumes:
+ *   psi_i(k) = i k_i S(k) delta(k) / (k^2 b (1 + beta mu^2)),  S = exp(-k^2 R^2 / 2),  beta = f / b (rsd) or 0,  mu^2 = k_z^2 / k^2,
+ * 0 for the zero vector; float32 arithmetic, wavenumbers as above (dk = float32(2 pi / Lbox), i -> i below n/2, i - n from n/2 on for
+ * x and y, 0 .. n/2 on z).  In the factor i k_i ONLY the wavenumber of axis i is 0 at index n/2 of that axis (k^2, mu^2 and S keep
+ * it), which makes the three spectra Hermitian as written.  "Padded meshes" are the real side of the padded spectra above: n * n
+ * rows of abacus_slab_pitch(n) floats, the first n of a row used.  n even, 2 .. 32767.
+ */
+/* fails, naming the largest mesh that fits, when the three displacement meshes + the work mesh of one deposit + transform + the
+ * copies of np particles do not fit the free device memory */
+int abacus_recon_check_memory(int n, int64_t np);
+/* three float64 device columns (what MockDict.device_xyz returns) -> out (np, 3) float32 = f32(column + f64(f32(offset))): for
+ * float32-valued columns the same bits as the float32 sum */
+int abacus_recon_pack_soa64_dev(const double *x, const double *y, const double *z, int64_t np, double offset, float *out);
+/* out (np, 3) float32 = (pos + f32(offset)) % f32(Lbox), NumPy's float32 remainder: the copy a deposit may work on.  out may be pos. */
+int abacus_recon_wrap_dev(const float *pos, int64_t np, double offset, double Lbox, float *out);
+/* mesh (n, n, n) float32 -> padded mesh (the layout abacus_recon_shift_dev reads) */
+int abacus_recon_pad_dev(const float *mesh, int n, float *out_padded);
+/* a given density mesh delta (n, n, n) float32, not modified -> padded copy, R2C in place: the BARE spectrum (not divided by n^3;
+ * pass normalised = 0 below, which folds 1 / n^3 into the multiplier).  The transform may take one padded work mesh from the scratch pool. */
+int abacus_recon_delta_dev(const float *delta, int n, void *out_padded);
+/* delta_padded (a padded spectrum; normalised = 1: divided by n^3 as abacus_zcv_spectrum_dev leaves it, 0: a bare R2C) -> ONE pass
+ * that writes the three displacement spectra (8 B read, 24 B written per mode) -> three in-place C2R: psi_x, psi_y, psi_z are
+ * padded meshes of abacus_zcv_spectrum_bytes(n) bytes each, in the units of Lbox.  delta_padded may be psi_z (and nothing else):
+ * three meshes then hold everything.  bias > 0, f_growth >= 0, R >= 0 (0: no smoothing), all finite.  hipFFT may take a work area. */
+int abacus_recon_displacement_dev(const void *delta_padded, int normalised, int n, double Lbox, double bias, double f_growth, double R, int rsd,
+                                  float *psi_x, float *psi_y, float *psi_z);
+/* one lane per particle: s = (pos + f32(offset)) % f32(Lbox); psi read at s from the three padded meshes with the cloud of `paste`
+ * (0: the 27 cells of analysis/tsc.py _tsc_scatter, 1: the 8 cells of analysis/cic.py; cell i centred at i Lbox / n, nearest cell by
+ * rounding, periodic indices); out (np, 3) float32 = (s - psi - f32(los_factor) psi_z z^) % f32(Lbox), the z component as
+ * ((s_z - psi_z) - los psi_z).  los_factor: f_growth for tracers and RecSym randoms under rsd, 0 for RecIso randoms.  pos is not
+ * modified; out must not be pos.  No scratch memory. */
+int abacus_recon_shift_dev(const float *pos, int64_t np, double offset, const float *psi_x, const float *psi_y, const float *psi_z, int n,
+                           double Lbox, int paste, double los_factor, float *out);
+
 /* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
  * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
  * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
