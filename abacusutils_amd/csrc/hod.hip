@@ -5,15 +5,18 @@
 // pos/vel, int64 ids) and stay resident across populate calls (the MCMC use case of staging()).
 //
 // plus what the kernels actually read: a packed 16-bit filter key per object, packed records of whole 128-B memory lines
-// for the sparse phases, and for LRG-only runs a (mass bin, q code)-sorted key index.
+// for the sparse phases, and for LRG-only runs a (mass bin, q code)-sorted key index, global and per superblock.
 //
 // Kernels (no MFMA - there is no contraction on this path); a populate is filter -> exact -> emit, or for LRG alone with
-// unchanged keys (from the second populate on) exact_index -> emit_bm:
+// unchanged keys (from the second populate on) exact_sbidx -> emit (option hod_sbindex = 1: exact_index -> emit_bm):
+//   hod_exact_sbidx LRG alone, from the second populate on: hod_exact with the superblock's candidates read off the
+//        per-superblock key index (cum / sidx: a prefix of every mass bin's run at the populate's threshold code) instead
+//        of the tiles' queues; hod_emit follows.  Profiled as hod_exact.
 //   hod_filter_key  streams the keys (2 B per object): `code > threshold[bin]` proves keep = 0 for the bulk of the objects
 //        (an envelope table bounds the marker chain over the bin's masses and the catalogue's environment ranges); the
 //        rest is queued per 2048-object tile.  hod_filter / hod_filter32 are the comparator and fallback filters
 //        (float64 columns of caller-owned catalogues, float32 shadow columns).
-//   hod_exact_index LRG alone, from the second populate on: the candidates are prefixes of the sorted key index, found on
+//   hod_exact_index its comparator (hod_sbindex = 1): the candidates are prefixes of the sorted key index, found on
 //        the host without reading a key (DealTab).  One candidate per lane: index, record line, the classifier below; a kept
 //        object sets its keep byte and a bit of this populate's per-tracer kept bitmap (non-returning atomics), nothing else.
 //        Profiled as hod_exact.
@@ -779,6 +782,78 @@ __global__ __launch_bounds__(256) void hod_index_last(const unsigned short *__re
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
         if (i == n - 1 || sk[i] != sk[i + 1]) last[sk[i]] = (unsigned int)(i + 1);
 }
+// ---- per-superblock key index (sparse mixes; hod_exact_sbidx) ----------------------------------------------------------
+// The same order, cut per superblock: superblock S of a kind holds, in the range of its own objects, their superblock-local
+// ids sorted by (mass bin, q code, id) - `sidx` - and cum[S][bin][code] = the number of its objects in `bin` with a code
+// <= `code`, plus every bin's start inside the segment.  The candidates of a populate are then, per superblock, a prefix of
+// every bin's run, read off `cum` at the bin's threshold code: the workgroup of a superblock finds its own candidates with
+// one round of loads and one index read each, and nothing has to be dealt, counted or handed over between workgroups.
+// Built from the global index by one more stable sort on the superblock number (hod_index_keys / _sort), the tables from
+// the keys themselves (hod_index_last).  2 + 4 B per object.
+__device__ __forceinline__ int sb_of_tile(int t, int ntile, int nsb) {   // the S with sb_first_tile(S) <= t < sb_first_tile(S + 1)
+    return (int)((((int64_t)t + 1) * nsb + ntile - 1) / ntile) - 1;
+}
+__global__ __launch_bounds__(256) void hod_sbindex_keys(const unsigned int *__restrict__ idx, int64_t n, int ntile, int nsb,
+                                                        unsigned short *__restrict__ sk) {
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256)
+        sk[k] = (unsigned short)sb_of_tile((int)(idx[k] / TILE), ntile, nsb);
+}
+// position k of the sorted order lies inside superblock sk[k]'s own object range (a superblock has as many entries as objects)
+__global__ __launch_bounds__(256) void hod_sbindex_local(const unsigned short *__restrict__ sk, const unsigned int *__restrict__ val,
+                                                         int64_t n, int ntile, int nsb, unsigned short *__restrict__ sidx) {
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256)
+        sidx[k] = (unsigned short)((int64_t)val[k] - (int64_t)((int64_t)sk[k] * ntile / nsb) * TILE);
+}
+constexpr int SBX_BINS = 128, SBX_CODES = 512, SBX_CHUNK = 16;   // bins per LDS histogram pass
+// one workgroup per superblock: histogram of its keys over (bin, code), SBX_CHUNK bins at a time, scanned along the code
+__global__ __launch_bounds__(256) void hod_sbindex_cum(const unsigned short *__restrict__ keys, int64_t n, int ntile, int nsb,
+                                                       unsigned short *__restrict__ cum, unsigned short *__restrict__ bstart) {
+    __shared__ unsigned int h[SBX_CHUNK * SBX_CODES];
+    __shared__ unsigned int seg[256], btot[SBX_CHUNK];
+    static_assert(SBX_CHUNK * 16 == 256 && SBX_CODES == 16 * 32, "thread t scans codes [32 (t & 15), +32) of bin t >> 4");
+    const int tid = threadIdx.x, S = blockIdx.x;
+    const int64_t first = (int64_t)sb_first_tile(S, ntile, nsb) * TILE;
+    const int64_t end = min((int64_t)sb_first_tile(S + 1, ntile, nsb) * TILE, n);
+    unsigned int run = 0;   // start of the chunk's first bin inside the superblock's segment (uniform)
+    for (int chunk = 0; chunk < SBX_BINS / SBX_CHUNK; chunk++) {
+        for (int q = tid; q < SBX_CHUNK * SBX_CODES; q += 256) h[q] = 0u;
+        __syncthreads();
+        for (int64_t i = first + tid; i < end; i += 256) {
+            const unsigned int k = keys[i], bin = k & 127u, code = k >> 7;
+            if ((int)(bin / SBX_CHUNK) == chunk) atomicAdd(&h[(bin % SBX_CHUNK) * SBX_CODES + code], 1u);
+        }
+        __syncthreads();
+        const int lb = tid >> 4, s = tid & 15, base = lb * SBX_CODES + s * 32;
+        unsigned int acc = 0;
+        for (int c = 0; c < 32; c++) {
+            acc += h[base + c];
+            h[base + c] = acc;
+        }
+        seg[tid] = acc;
+        __syncthreads();
+        unsigned int off = 0;
+        for (int q = 0; q < s; q++) off += seg[(lb << 4) + q];
+        unsigned short *dst = cum + ((int64_t)S * SBX_BINS + chunk * SBX_CHUNK + lb) * SBX_CODES + s * 32;
+        for (int c = 0; c < 32; c++) dst[c] = (unsigned short)(h[base + c] + off);   // <= 32768 objects per superblock
+        if (s == 15) btot[lb] = off + acc;
+        __syncthreads();
+        unsigned int before = 0, all = 0;
+        for (int q = 0; q < SBX_CHUNK; q++) {
+            if (q < tid) before += btot[q];
+            all += btot[q];
+        }
+        if (tid < SBX_CHUNK) bstart[(int64_t)S * SBX_BINS + chunk * SBX_CHUNK + tid] = (unsigned short)(run + before);
+        run += all;
+        __syncthreads();
+    }
+}
+// what hod_exact_sbidx reads of it; tc: the populate's threshold codes (KeyTab), two per word, [0]: centrals, [1]: satellites
+struct SbIndex {
+    const unsigned short *cum, *bstart;     // [nsb_c + nsb_s][128][512], [nsb_c + nsb_s][128]
+    const unsigned short *sidx_c, *sidx_s;  // per kind, at the objects' own positions
+    unsigned int tc[2][64];
+};
+
 struct DealTab {   // candidate segments of the sorted index: centrals first; pre = exclusive prefix of the lengths
     int nseg, nseg_c;
     unsigned int start[256], pre[257];
@@ -906,9 +981,26 @@ __device__ __forceinline__ void fetch_cand(const HodPtrs &a, const abacus_hod_pa
     }
 }
 
-template <int XB, bool PIPE, int SBT>
+// lane `lane` of `old` replaced by the wave-uniform `v` (v_writelane_b32)
+template <int lane>
+__device__ __forceinline__ unsigned int writelane_u32(unsigned int v, unsigned int old) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(v), "n"(lane));
+#endif
+    return old;
+}
+
+// SRC: where the superblock's candidates come from - 0: the tiles' queues (filled by a filter or hod_deal); 1: the
+// per-superblock key index `sx` (see hod_sbindex_cum): thread b < 128 reads the length of bin b's candidate prefix at the
+// populate's threshold code and the bin's start in one round of loads, a scan over the bins replaces the one over the tiles,
+// and candidate j is one search over the bins plus one index read.  No queue counter is read or zeroed.  The previous
+// populate's kept count and first kept entries are requested in the same round (the slice is always allocated; what it
+// holds beyond the count is not used).
+template <int XB, bool PIPE, int SBT, int SRC = 0>
 __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, const abacus_hod_params &p, const SatPre &pre,
-                                               const abacus_cls::ClsConst &cc, int use_cls, int clear_prev) {
+                                               const abacus_cls::ClsConst &cc, int use_cls, int clear_prev,
+                                               const SbIndex *sx = nullptr) {
+    static_assert(SRC == 0 || (!PIPE && XB >= 128 && SBT * TILE <= 65536), "the key index feeds the plain form");
     constexpr int SB_TILES = SBT, SB_OBJ = SBT * TILE, SB_WORDS = SB_OBJ / 32;
     constexpr int WORDS_PER_THREAD = SB_WORDS / XB;
     static_assert(SB_WORDS % XB == 0 && XB <= 512 && SB_OBJ <= 65536, "bitmap words must divide over the workgroup");
@@ -928,20 +1020,66 @@ __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, c
     const int tile_first = sb_first_tile(S, ntile, nsb), ntl = sb_first_tile(S + 1, ntile, nsb) - tile_first;   // ntl <= SB_TILES
     const int64_t obj_first = (int64_t)tile_first * TILE;
     const int *q_count = a.q_count + (sat ? a.ntile_c : 0);
-    if (tid < SB_TILES) {
-        const int t = tile_first + tid;
-        L.pre[tid + 1] = tid < ntl ? q_count[t] : 0;
-        if ((clear_prev & 2) && tid < ntl) a.q_count[(sat ? a.ntile_c : 0) + t] = 0;   // the index path counts into zeroed counters
-    }
-    if (tid == 0) L.pre[0] = 0;
+    __shared__ int s_bpre[SRC == 1 ? SBX_BINS + 1 : 1];              // SRC 1: exclusive prefix of the bins' candidate counts
+    __shared__ unsigned short s_bstart[SRC == 1 ? SBX_BINS : 1];     // ... and the bins' starts in the superblock's segment
+    int prev_n = 0;
+    unsigned int prev_k0 = 0;
+    if constexpr (SRC == 1) {
+        // the threshold code of bin `tid`: the codes are kernel arguments (scalar registers), two per word; lane l takes word
+        // l, then every thread fetches the word of its bin from that lane - no memory round trip in front of the loads below
+        unsigned int tw = 0;
+        const unsigned int *tcw = sx->tc[sat ? 1 : 0];
+#define WL4(l) tw = writelane_u32<l>(tcw[l], tw), tw = writelane_u32<l + 1>(tcw[l + 1], tw), tw = writelane_u32<l + 2>(tcw[l + 2], tw), tw = writelane_u32<l + 3>(tcw[l + 3], tw)
+        WL4(0), WL4(4), WL4(8), WL4(12), WL4(16), WL4(20), WL4(24), WL4(28), WL4(32), WL4(36), WL4(40), WL4(44), WL4(48), WL4(52), WL4(56), WL4(60);
+#undef WL4
+        const int bin = tid & (SBX_BINS - 1);
+        const unsigned int w2 = (unsigned int)__shfl((int)tw, bin >> 1, 64);
+        const int code = min((int)((w2 >> ((bin & 1) * 16)) & 0xffffu), SBX_CODES - 1);
+        int cnt = 0, bs = 0;
+        if (tid < SBX_BINS) {
+            cnt = sx->cum[((int64_t)g * SBX_BINS + tid) * SBX_CODES + code];
+            bs = sx->bstart[(int64_t)g * SBX_BINS + tid];
+        }
+        if (clear_prev & 1) {
+            prev_n = a.sb_counts[(int64_t)g * 4] + a.sb_counts[(int64_t)g * 4 + 1] + a.sb_counts[(int64_t)g * 4 + 2];
+            prev_k0 = ((sat ? a.kept_s : a.kept_c) + obj_first)[tid];
+        }
 #pragma unroll
-    for (int w = 0; w < 3 * WORDS_PER_THREAD; w++) (&L.bm[0][0])[w * XB + tid] = 0u;
-    __syncthreads();
-    if (tid == 0)
-        for (int q = 1; q <= SB_TILES; q++) L.pre[q] += L.pre[q - 1];
-    __syncthreads();
-    const int total = L.pre[SB_TILES];
-    if (clear_prev & 1) {
+        for (int w = 0; w < 3 * WORDS_PER_THREAD; w++) (&L.bm[0][0])[w * XB + tid] = 0u;
+        int incl = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(incl, d, 64);
+            if ((tid & 63) >= d) incl += v;
+        }
+        if (tid < SBX_BINS) s_bpre[tid + 1] = incl, s_bstart[tid] = (unsigned short)bs;
+        if (tid == 0) s_bpre[0] = 0;
+        __syncthreads();
+        const int w0 = s_bpre[64];   // the first wave's total; the second wave writes entries 65 .. 128 only
+        if (tid >= 64 && tid < SBX_BINS) s_bpre[tid + 1] = incl + w0;
+        __syncthreads();
+    } else {
+        if (tid < SB_TILES) {
+            const int t = tile_first + tid;
+            L.pre[tid + 1] = tid < ntl ? q_count[t] : 0;
+            if ((clear_prev & 2) && tid < ntl) a.q_count[(sat ? a.ntile_c : 0) + t] = 0;   // the index path counts into zeroed counters
+        }
+        if (tid == 0) L.pre[0] = 0;
+#pragma unroll
+        for (int w = 0; w < 3 * WORDS_PER_THREAD; w++) (&L.bm[0][0])[w * XB + tid] = 0u;
+        __syncthreads();
+        if (tid == 0)
+            for (int q = 1; q <= SB_TILES; q++) L.pre[q] += L.pre[q - 1];
+        __syncthreads();
+    }
+    const int total = SRC == 1 ? s_bpre[SRC == 1 ? SBX_BINS : 0] : L.pre[SB_TILES];
+    if (SRC == 1 && (clear_prev & 1)) {   // the un-keep of the previous kept list (see below), its loads already under way
+        const unsigned short *pk = (sat ? a.kept_s : a.kept_c) + obj_first;
+        int8_t *keep = (sat ? a.keep_s : a.keep_c) + obj_first;
+        if (tid < prev_n) keep[prev_k0] = 0;
+        for (int e = tid + XB; e < prev_n; e += XB) keep[pk[e]] = 0;
+        __syncthreads();
+    } else if (clear_prev & 1) {
         // Lazy keep masks (sparse mixes): the filter did not zero the 1 B per object - 20 MB of the 100 MB it moves at 1e7 +
         // 1e7 (23.8 -> 21.3 us; 83 -> 67 us at 4e7 + 4e7).  The only non-zero bytes are the objects the PREVIOUS populate
         // kept, and this superblock's share of them is still listed in its kept slice (counts in sb_counts, overwritten at
@@ -958,8 +1096,19 @@ __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, c
     const unsigned short *queue = sat ? a.queue_s : a.queue_c;
     // tile and tile-local index of the superblock's j-th candidate
     auto locate = [&](int j, int &q, int &loc) {
-        q = exact_find_tile(L, j);
-        loc = queue[(int64_t)(tile_first + q) * TILE + (j - L.pre[q])];
+        if constexpr (SRC == 1) {
+            int lo = 0, hi = SBX_BINS - 1;   // largest bin with pre <= j
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (s_bpre[mid] <= j) lo = mid;
+                else hi = mid - 1;
+            }
+            const int l = ((sat ? sx->sidx_s : sx->sidx_c) + obj_first)[(int)s_bstart[lo] + (j - s_bpre[lo])];
+            q = l / TILE, loc = l % TILE;
+        } else {
+            q = exact_find_tile(L, j);
+            loc = queue[(int64_t)(tile_first + q) * TILE + (j - L.pre[q])];
+        }
     };
     // the candidate's scalars: one record line, or the staged columns (caller-owned catalogues)
     auto fetch = [&](int q, int loc, ExactCand &c) {
@@ -1145,6 +1294,16 @@ __global__ __launch_bounds__(XB) __attribute__((amdgpu_waves_per_eu(4))) void ho
                                                                                                abacus_cls::ClsConst cc, int use_cls,
                                                                                                int clear_prev) {
     hod_exact_body<XB, false, SBT>(a, first_sb, p, pre, cc, use_cls, clear_prev);
+}
+
+// The plain form fed from the per-superblock key index (SRC = 1 above): with hod_emit behind it the whole populate of a sparse
+// mix on unchanged keys.  A kernel of its own, so that hod_exact_plain keeps its registers; this one runs at its 137, three
+// waves per SIMD and nothing in scratch (held to 128 it spills nine values).
+template <int XB, int SBT>
+__global__ __launch_bounds__(XB) void hod_exact_sbidx(HodPtrs a, abacus_hod_params p, SatPre pre,
+                                                                                               abacus_cls::ClsConst cc, int use_cls,
+                                                                                               int clear_prev, SbIndex sx) {
+    hod_exact_body<XB, false, SBT, 1>(a, 0, p, pre, cc, use_cls, clear_prev, &sx);
 }
 
 // Index path without queues (sparse mixes, unchanged keys; `hod_deal` = 1 restores hod_deal -> hod_exact -> hod_emit): one
@@ -2059,6 +2218,10 @@ struct abacus_hod_state {
     DevBuf index_idx, index_scratch, index_tmp, index_last;
     std::vector<unsigned int> upper_h, upper_p;   // host: number of objects with (bin << 9 | code) <= v
     bool index_ok = false;
+    // per-superblock key index (hod_exact_sbidx): built behind the global one, for the superblock layout it records
+    DevBuf sbx_cum, sbx_bstart, sbx_sidx;
+    bool sbx_ok = false;
+    int sbx_layout[6] = {0, 0, 0, 0, 0, 0};   // ntile_c, ntile_s, nsb_c, nsb_s, tiles per superblock, hod_nobalance
     int key_uses = 0;           // populates since the keys were (re)built
     bool q_zero = false;        // the per-tile candidate counters are known to be zero
     int64_t last_cand[2] = {-1, -1};
@@ -2102,7 +2265,7 @@ namespace {
 // the diagnostic options a populate reads, re-read only when one has been set since (option_version): a lookup takes the API
 // mutex and builds a std::string, about a dozen of them per populate.  Callers hold the API mutex.
 struct HodOpts {
-    int sbtiles, nobalance, norec, one_stage, f64filter, nokeys, nolazy, deal, noindex, nocls, pipe, eblock, dbg;
+    int sbtiles, nobalance, norec, one_stage, f64filter, nokeys, nolazy, deal, noindex, nocls, pipe, eblock, dbg, sbindex;
 };
 const HodOpts &hod_opts() {
     static HodOpts o;
@@ -2114,6 +2277,7 @@ const HodOpts &hod_opts() {
         o.one_stage = option("hod_one_stage"), o.f64filter = option("hod_f64filter"), o.nokeys = option("hod_nokeys");
         o.nolazy = option("hod_nolazy"), o.deal = option("hod_deal"), o.noindex = option("hod_noindex");
         o.nocls = option("hod_nocls"), o.pipe = option("hod_pipe"), o.eblock = option("hod_eblock"), o.dbg = option("dbg");
+        o.sbindex = option("hod_sbindex");
         seen = v, have = true;
     }
     return o;
@@ -2287,7 +2451,7 @@ int build_keys(abacus_hod_state *st) {
     ABACUS_LAUNCH("hod_build_keys", hod_build_keys, dim3((unsigned)std::min<int64_t>(ceil_div(pp, 256), 8192)), dim3(256), 0,
                   (const double *)st->phmass, (const double *)st->pweights, (const double *)st->prandoms, st->np, pp, pk);
     st->keys_ok = true;
-    st->index_ok = false;   // the index sorts these keys
+    st->index_ok = st->sbx_ok = false;   // the indices sort these keys
     st->key_uses = 0;
     return 0;
 }
@@ -2325,6 +2489,43 @@ int build_index(abacus_hod_state *st) {
         }
     }
     st->index_ok = true;
+    return 0;
+}
+
+// the per-superblock key index (see hod_sbindex_cum) for the superblock layout in force, from the global index and the keys.
+// Declines (sbx_ok stays false: the caller keeps the bitmap path) where a superblock number does not fit the 16-bit sort key.
+int build_sbindex(abacus_hod_state *st) {
+    const int layout[6] = {st->ntile_c, st->ntile_s, st->nsb_c, st->nsb_s, st->sb_tiles, hod_opts().nobalance};
+    if (st->sbx_ok && !memcmp(layout, st->sbx_layout, sizeof layout)) return 0;
+    st->sbx_ok = false;
+    if (!st->index_ok || st->sb_tiles * TILE > 65536 || st->nsb_c > 65535 || st->nsb_s > 65535) return 0;
+    const int64_t nh = st->nh, np = st->np, nmax = std::max<int64_t>(std::max(nh, np), 1);
+    const int64_t ph = (int64_t)std::max(st->ntile_c, 1) * TILE, pp = (int64_t)std::max(st->ntile_s, 1) * TILE;
+    const int nsb = st->nsb_c + st->nsb_s;
+    ABACUS_TRY(st->sbx_cum.reserve((size_t)std::max(nsb, 1) * SBX_BINS * SBX_CODES * sizeof(unsigned short)));
+    ABACUS_TRY(st->sbx_bstart.reserve((size_t)std::max(nsb, 1) * SBX_BINS * sizeof(unsigned short)));
+    ABACUS_TRY(st->sbx_sidx.reserve((size_t)(ph + pp) * sizeof(unsigned short)));
+    ABACUS_TRY(st->index_scratch.reserve((size_t)nmax * (2 + 2 + 4)));
+    unsigned short *sk_in = st->index_scratch.as<unsigned short>(), *sk_out = sk_in + nmax;
+    unsigned int *val_out = reinterpret_cast<unsigned int *>(sk_out + nmax);
+    const unsigned short *hk = st->keys.as<unsigned short>(), *pk = hk + ph;
+    for (int kind = 0; kind < 2; kind++) {
+        const int64_t n = kind ? np : nh;
+        const int ntile = kind ? st->ntile_s : st->ntile_c, nsbk = kind ? st->nsb_s : st->nsb_c;
+        if (n == 0 || nsbk == 0) continue;
+        const unsigned int *idx = st->index_idx.as<unsigned int>() + (kind ? nh : 0);
+        unsigned short *sidx = st->sbx_sidx.as<unsigned short>() + (kind ? ph : 0);
+        const int grid = (int)std::min<int64_t>(ceil_div(n, 256), 8192);
+        ABACUS_LAUNCH("hod_index_keys", hod_sbindex_keys, dim3(grid), dim3(256), 0, idx, n, ntile, nsbk, sk_in);
+        ABACUS_TRY(sort_pairs_u16(sk_in, sk_out, idx, val_out, n, st->index_tmp));
+        ABACUS_LAUNCH("hod_index_keys", hod_sbindex_local, dim3(grid), dim3(256), 0, (const unsigned short *)sk_out,
+                      (const unsigned int *)val_out, n, ntile, nsbk, sidx);
+        ABACUS_LAUNCH("hod_index_last", hod_sbindex_cum, dim3(nsbk), dim3(256), 0, kind ? pk : hk, n, ntile, nsbk,
+                      st->sbx_cum.as<unsigned short>() + (int64_t)(kind ? st->nsb_c : 0) * SBX_BINS * SBX_CODES,
+                      st->sbx_bstart.as<unsigned short>() + (int64_t)(kind ? st->nsb_c : 0) * SBX_BINS);
+    }
+    memcpy(st->sbx_layout, layout, sizeof layout);
+    st->sbx_ok = true;
     return 0;
 }
 
@@ -2445,6 +2646,34 @@ int populate_bitmaps(abacus_hod_state *st, const abacus_hod_params *p, const Sat
     st->have_run = true;
     st->counts_valid = false;
     return 0;   // kept_valid stays false: this path writes no kept lists; q_count is untouched (q_zero stays as it was)
+}
+
+// sparse mixes on unchanged keys: hod_exact_sbidx from the per-superblock key index, then hod_emit over the kept lists it
+// wrote.  `lazy`: the kept lists of the previous populate name the non-zero keep bytes (the kernel un-keeps them); otherwise
+// (the first such populate, after the bitmap path, the NFW path, another superblock size) the masks are cleared here once.
+int populate_sbindex(abacus_hod_state *st, const abacus_hod_params *p, const SatPre &pre, const HodPtrs &a, const KeyTab &kt,
+                     bool lazy) {
+    if (!lazy) {
+        if (st->nh) HIP_TRY(hipMemsetAsync(st->keep_c, 0, (size_t)st->nh, stream()));
+        if (st->np) HIP_TRY(hipMemsetAsync(st->keep_s, 0, (size_t)st->np, stream()));
+    }
+    abacus_cls::ClsConst cc;
+    abacus_cls::make_cls_const(*p, pre, cc);
+    const int use_cls = (hod_opts().nocls || !abacus_cls::cls_params_finite(*p)) ? 0 : 1;
+    SbIndex sx;
+    sx.cum = st->sbx_cum.as<unsigned short>(), sx.bstart = st->sbx_bstart.as<unsigned short>();
+    sx.sidx_c = st->sbx_sidx.as<unsigned short>(), sx.sidx_s = sx.sidx_c + (int64_t)std::max(st->ntile_c, 1) * TILE;
+    for (int l = 0; l < 64; l++)
+        sx.tc[0][l] = kt.c[2 * l] | ((unsigned int)kt.c[2 * l + 1] << 16), sx.tc[1][l] = kt.s[2 * l] | ((unsigned int)kt.s[2 * l + 1] << 16);
+    const int nsb = st->nsb_c + st->nsb_s;
+    if (nsb > 0)
+        ABACUS_LAUNCH("hod_exact", (hod_exact_sbidx<256, SB_TILES_SPARSE>), dim3(nsb), dim3(256), 0, a, *p, pre, cc, use_cls,
+                      lazy ? 1 : 0, sx);
+    ABACUS_TRY(launch_emit(st));   // emit_bm is off: hod_emit over the kept lists
+    st->have_run = true;
+    st->counts_valid = false;
+    st->kept_valid = true, st->kept_sb_tiles = st->sb_tiles;   // every mask byte that is set is in a kept list
+    return 0;   // q_count is untouched (q_zero stays as it was); bm_valid is off: the bitmap path clears its state on entry
 }
 
 }  // namespace
@@ -2778,6 +3007,11 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
     const bool lazy_ok = use32 && !hod_opts().nokeys && !hod_opts().nolazy && cheap.c_ok && cheap.s_ok && st->ntile_c > 0 &&
                          st->ntile_s > 0 && (!conf || filter_first_) && st->sb_tiles == SB_TILES_SPARSE;
     const bool lazy_masks = lazy_ok && st->kept_valid && st->kept_sb_tiles == st->sb_tiles;
+    // the per-superblock index path (hod_exact_sbidx -> hod_emit; `hod_sbindex` = 1 keeps the bitmap path): no filter launch,
+    // so a kind may be empty
+    const bool sbx_mix = !hod_opts().sbindex && !hod_opts().deal && !conf && use32 && !hod_opts().nokeys && !hod_opts().nolazy &&
+                         cheap.c_ok && cheap.s_ok && st->sb_tiles == SB_TILES_SPARSE;
+    const bool sbx_lazy = st->kept_valid && st->kept_sb_tiles == st->sb_tiles;
     st->kept_valid = false;   // until this populate's launches are all enqueued
     // the index path without queues (hod_exact_index -> hod_emit_bm) - except where the satellites read keep_cent[pinds], which
     // holds the previous populate's bytes until hod_emit_bm: then, and with `hod_deal` = 1 (the A/B comparator), the index
@@ -2792,7 +3026,9 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
     if (use32 && st->sb_tiles == SB_TILES_SPARSE && !hod_opts().noindex && !hod_opts().nokeys) {
         st->key_uses++;
         if (!st->index_ok && st->key_uses >= 2) ABACUS_TRY(build_index(st));
-        if (st->index_ok && (bm_path ? lazy_ok : lazy_masks)) {
+        if (st->index_ok && sbx_mix) ABACUS_TRY(build_sbindex(st));
+        const bool sbx = sbx_mix && st->sbx_ok;
+        if (st->index_ok && (sbx || (bm_path ? lazy_ok : lazy_masks))) {
             unsigned int pre = 0;
             deal.nseg = 0;
             int64_t cand[2] = {0, 0};
@@ -2817,6 +3053,7 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
         }
     }
     if (!index_mode) st->last_cand[0] = st->last_cand[1] = -1;
+    if (index_mode && sbx_mix && st->sbx_ok) return populate_sbindex(st, p, pre, a, keytab, sbx_lazy);
     if (index_mode && bm_path) return populate_bitmaps(st, p, pre, a, deal, bm_was_valid);
     const int exact_flags = (lazy_masks ? 1 : 0) | (index_mode ? 2 : 0);
     // `first`, `count` in global tile ids (centrals first): the shadow path launches the two kinds separately
@@ -3066,6 +3303,7 @@ int abacus_hod_free(abacus_hod_state *st) {
     (void)st->index_idx.release(), (void)st->index_scratch.release(), (void)st->index_tmp.release(), (void)st->index_last.release();
     (void)st->hrec.release(), (void)st->prec.release();
     (void)st->bm.release(), (void)st->lb.release();
+    (void)st->sbx_cum.release(), (void)st->sbx_bstart.release(), (void)st->sbx_sidx.release();
     delete st;
     return 0;
 }
