@@ -9,6 +9,14 @@
 //   r-bin b holds edges[b] <= r < edges[b+1]; DDrppi: pi-bin = int(|dz| / (pimax/npibins)), |dz| < pimax;
 //   DDsmu: mu = |dz|/s, mu-bin = int(mu * nmubins/mu_max), mu < mu_max; autocorrelation counts ordered pairs (i != j).
 //
+// Weighted counts (abacus_paircount_weighted, Corrfunc's weight_type='pair_product' and output_ravg / _rpavg / _savg): the pairs
+// of a bin are those above - npairs is bit-equal to the unweighted count - and per bin
+//   wsum = sum of w_i w_j: float32 weights, the product formed in float64 (24 + 24 bits: exact), accumulated in float64;
+//   rsum = sum of the separation (r | rp = sqrt(dx^2 + dy^2) | s): sqrtf - correctly rounded - of the very r^2 that chose the
+//          bin, accumulated in float64;
+// a missing weight array is unit weights; the weight is sorted into cells WITH its point (both sort paths); float64 atomics
+// make the sums reproducible to n 2^-52 sum|term| per bin, not bit for bit.  Kernel: pair_count_w below.
+//
 // Algorithm: both point sets are counting-sorted into a cell grid with cell size >= the largest separation
 // (SoA x|y|z per set, cell_start offsets).  One workgroup per non-empty cell of set 1 walks the 27 neighbour cells
 // of set 2, staging 256 neighbours at a time in LDS; every thread owns one point of set 1 and scans the staged
@@ -64,10 +72,10 @@ __device__ __forceinline__ float funkey(unsigned int k) {
 }
 
 // COUNT: per-cell counters by global atomics (counting sort, small inputs); else the cell ids become the keys of a radix sort
-// and idx the values
-template <bool COUNT>
+// and idx the values.  W (weighted counts): the point's weight rides in the free lane of the packed record
+template <bool COUNT, bool W>
 __global__ void cell_count(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                           int64_t n, CellGrid g, unsigned int *__restrict__ counts, unsigned int *__restrict__ cellid,
+                           const float *__restrict__ w, int64_t n, CellGrid g, unsigned int *__restrict__ counts, unsigned int *__restrict__ cellid,
                            unsigned int *__restrict__ idx, float4 *__restrict__ packed, int *__restrict__ outside,
                            Frame *__restrict__ frame) {
     bool out = false;
@@ -78,7 +86,7 @@ __global__ void cell_count(const float *__restrict__ x, const float *__restrict_
                       cell_coord(v[2], g.ncz, g.inv_box);
         cellid[i] = (unsigned int)c;
         if (COUNT) atomicAdd(&counts[c], 1u);
-        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], 0.f);   // one 16-B piece per point for the gather
+        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], W ? w[i] : 0.f);   // one 16-B piece per point for the gather
         out = out || !(v[0] >= 0.f && v[0] < g.box && v[1] >= 0.f && v[1] < g.box && v[2] >= 0.f && v[2] < g.box);
 #pragma unroll
         for (int d = 0; d < 3; d++) {
@@ -104,26 +112,31 @@ __global__ void cell_count(const float *__restrict__ x, const float *__restrict_
         atomicMin(&frame->mn[threadIdx.x], s_mn[threadIdx.x]), atomicMax(&frame->mx[threadIdx.x], s_mx[threadIdx.x]);
 }
 
+// W: the weight takes the slot its point drew (the order inside a cell differs from run to run, point and weight stay together)
+template <bool W>
 __global__ void cell_fill(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                          int64_t n, const unsigned int *__restrict__ cellid, const int64_t *__restrict__ start,
-                          unsigned int *__restrict__ cursor, float *__restrict__ sx, float *__restrict__ sy,
-                          float *__restrict__ sz) {
+                          const float *__restrict__ w, int64_t n, const unsigned int *__restrict__ cellid,
+                          const int64_t *__restrict__ start, unsigned int *__restrict__ cursor, float *__restrict__ sx,
+                          float *__restrict__ sy, float *__restrict__ sz, float *__restrict__ sw) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const unsigned int c = cellid[i];
         const int64_t s = start[c] + atomicAdd(&cursor[c], 1u);
         sx[s] = x[i];
         sy[s] = y[i];
         sz[s] = z[i];
+        if (W) sw[s] = w[i];
     }
 }
 
 // behind the radix sort of (cell id, point index): the points in cell order (ties in input order: the sort is stable, so
 // the sorted arrays do not depend on the run) ...
+template <bool W>
 __global__ void cell_gather(const float4 *__restrict__ packed, int64_t n, const unsigned int *__restrict__ idx,
-                            float *__restrict__ sx, float *__restrict__ sy, float *__restrict__ sz) {
+                            float *__restrict__ sx, float *__restrict__ sy, float *__restrict__ sz, float *__restrict__ sw) {
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         const float4 p = packed[idx[s]];   // one memory sector per point instead of three (x, y, z live in separate arrays)
         sx[s] = p.x, sy[s] = p.y, sz[s] = p.z;
+        if (W) sw[s] = p.w;
     }
 }
 // ... and the first point of every cell: start[c] = number of keys below c (c = 0 .. ncell)
@@ -788,9 +801,153 @@ __global__ __launch_bounds__(P3_WAVES * 64) void pair_count3(PairArgs a, const F
         if (hist[q]) atomicAdd(&a.npairs[q], mult * (unsigned long long)hist[q]);
 }
 
+// Weighted counter: per (bin, sub-bin) the integer count, sum of w_i w_j and sum of the pair separation (r | rp | s).
+// One kernel for every geometry: cells of the full reach (or one cell per dimension when fewer than 3 fit), a persistent
+// workgroup per cell of set 1, the 27 (or fewer) neighbour cells as ONE virtual list of which every thread fetches one point
+// per round into registers and walks the slice of its own cell (LDS broadcast reads), and the per-pair minimum image of the
+// oracle in every case - the expressions that decide membership are those of the unweighted kernels, so npairs is bit-equal.
+//   * w_i w_j is formed in float64 (24 + 24 significant bits: exact) and accumulated in float64 from there on - registers,
+//     LDS (ds_add_f64) and global memory; the separation is sqrtf (correctly rounded) of the r^2 that chose the bin, summed in float64.
+//     The sums depend on the order of the atomics in their last bits: |error| <= n 2^-52 sum|term| whatever the order.
+//   * MODE 0: the last bin takes most pairs of logarithmic bins; every lane keeps that bin's three sums in registers and adds
+//     them to the histogram once, at the end (64 lanes on one LDS address serialise; a ballot cannot carry a float64 sum).
+//   * An entry is 20 bytes: W_MAX_HIST entries per launch, more are counted in runs of separation bins (paircount_impl).
+//   * The autocorrelation walks the full stencil (ordered pairs, nothing is doubled).
+constexpr int W_MAX_HIST = 2048;
+
+struct WeightArgs {
+    const float *w1, *w2;   // weights in cell order; NULL: unit weights
+    double *wsum, *rsum;    // rsum is read only when RSUM
+};
+
+template <int MODE, bool RSUM>
+__global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, int ncell, unsigned long long *__restrict__ evaluated) {
+    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
+    __shared__ float e2[64];
+    __shared__ int64_t nb_j0[27];
+    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
+    extern __shared__ __align__(8) double hw[];   // nh sums of w w | nh sums of the separation | nh counts
+    const int tid = threadIdx.x;
+    const int nh = a.nbins * a.nsub;
+    double *hr = hw + nh;
+    unsigned int *hc = reinterpret_cast<unsigned int *>(hr + nh);
+    for (int q = tid; q < nh; q += PB) hw[q] = 0.0, hr[q] = 0.0, hc[q] = 0u;
+    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
+    __syncthreads();
+    const float lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
+    const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
+    const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
+    double top_w = 0.0, top_r = 0.0;         // MODE 0: the last bin, per lane
+    unsigned long long top_n = 0, n_eval = 0;
+    for (int c1 = blockIdx.x; c1 < ncell; c1 += gridDim.x) {
+        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
+        if (cbeg == cend) continue;
+        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
+        if (tid < 64) {
+            int len = 0;
+            int64_t j0 = 0;
+            if (tid < nnb) {
+                const int cz = c1 % a.g.ncz, cy = (c1 / a.g.ncz) % a.g.ncy, cx = c1 / (a.g.ncz * a.g.ncy);
+                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
+                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
+                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
+                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
+                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
+                j0 = a.start2[c2];
+                len = (int)(a.start2[c2 + 1] - j0);
+            }
+            int incl = len;
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) {
+                const int v = __shfl_up(incl, d, 64);
+                if (tid >= d) incl += v;
+            }
+            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
+            if (tid == nnb - 1) nb_pre[nnb] = incl;
+        }
+        __syncthreads();
+        const int M = nb_pre[nnb];
+        for (int64_t i0 = cbeg; i0 < cend; i0 += PB) {
+            const int ni = (int)min((int64_t)PB, cend - i0);
+            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
+            if (tid < ni) {
+                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
+                iw[tid] = wa.w1 ? wa.w1[i0 + tid] : 1.0f;
+            }
+            __syncthreads();
+            for (int base = 0; base < M; base += PB) {
+                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
+                const int v = base + tid;
+                if (v >= M) continue;
+                int sg = 0;
+                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[nnb]: ends at a non-empty cell
+                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
+                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
+                const double wj = wa.w2 ? (double)wa.w2[jj] : 1.0;
+                for (int i = 0; i < ni; i++) {
+                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
+                    const float dx = min_image(ix[i] - xj, a.half, a.g.box);
+                    const float dy = min_image(iy[i] - yj, a.half, a.g.box);
+                    const float dz = min_image(iz[i] - zj, a.half, a.g.box);
+                    float r2;
+                    int sub = 0;
+                    if (MODE == 1) {
+                        const float adz = fabsf(dz);
+                        if (adz >= a.pimax) continue;
+                        r2 = dx * dx + dy * dy;
+                        if (r2 < lo2 || r2 >= hi2) continue;
+                        sub = (int)(adz / a.dpi);
+                        if (sub >= a.nsub) continue;
+                    } else {
+                        r2 = dx * dx + dy * dy + dz * dz;
+                        if (r2 < lo2 || r2 >= hi2) continue;
+                    }
+                    float sep = 0.f;
+                    if (MODE == 2) {
+                        sep = sqrtf(r2);
+                        const float mu = sep > 0.f ? fabsf(dz) / sep : 0.f;
+                        if (mu >= a.mu_max) continue;
+                        sub = (int)(mu * a.inv_dmu);
+                        if (sub >= a.nsub) continue;
+                    } else if (RSUM) {
+                        sep = sqrtf(r2);
+                    }
+                    const double ww = (double)iw[i] * wj;
+                    if (MODE == 0 && r2 >= top2) {
+                        top_n++, top_w += ww;
+                        if (RSUM) top_r += (double)sep;
+                        continue;
+                    }
+                    int b = a.nbins - 1;
+                    while (r2 < e2[b]) b--;
+                    const int q = b * a.nsub + sub;
+                    atomicAdd(&hc[q], 1u);
+                    atomicAdd(&hw[q], ww);
+                    if (RSUM) atomicAdd(&hr[q], (double)sep);
+                }
+            }
+        }
+    }
+    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
+    if (MODE == 0 && top_n) {
+        // a lane's share of a workgroup's last-bin pairs stays far below 2^32
+        const int q = a.nbins - 1;
+        atomicAdd(&hc[q], (unsigned int)top_n);
+        atomicAdd(&hw[q], top_w);
+        if (RSUM) atomicAdd(&hr[q], top_r);
+    }
+    __syncthreads();
+    for (int q = tid; q < nh; q += PB)
+        if (hc[q]) {
+            atomicAdd(&a.npairs[q], (unsigned long long)hc[q]);
+            atomicAdd(&wa.wsum[q], hw[q]);
+            if (RSUM) atomicAdd(&wa.rsum[q], hr[q]);
+        }
+}
+
 struct SortedSet {
-    DevBuf raw, sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed;
-    float *sx, *sy, *sz;
+    DevBuf raw, sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wraw, wsorted;
+    float *sx, *sy, *sz, *sw;   // sw: the weights in cell order (weighted counts with weights for this set), else NULL
     int64_t n;
 };
 
@@ -800,9 +957,10 @@ __global__ void cast_f64_f32(const double *__restrict__ src, float *__restrict__
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)src[i];
 }
 
-// where = 0: host float32 arrays; 1: device float32; 2: device float64
-int sort_into_cells(const void *hx, const void *hy, const void *hz, int where, int64_t n, const CellGrid &g, SortedSet &s,
-                    DevBuf &scratch, int *d_outside, Frame *d_frame) {
+// where = 0: host float32 arrays; 1: device float32; 2: device float64.  hw: float32 weights of the points (host memory when
+// where = 0, else device memory) or NULL; they are sorted along with the points into s.sw
+int sort_into_cells(const void *hx, const void *hy, const void *hz, const float *hw, int where, int64_t n, const CellGrid &g,
+                    SortedSet &s, DevBuf &scratch, int *d_outside, Frame *d_frame) {
     const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
     const size_t n1 = (size_t)std::max<int64_t>(n, 1);
     s.n = n;
@@ -828,6 +986,17 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, int where, i
         }
         rx = bx, ry = by, rz = bz;
     }
+    const float *rw = hw;
+    s.sw = nullptr;
+    if (hw) {
+        ABACUS_TRY(s.wsorted.reserve(n1 * 4));
+        s.sw = s.wsorted.as<float>();
+        if (where == 0) {
+            ABACUS_TRY(s.wraw.reserve(n1 * 4));
+            if (n > 0) HIP_TRY(hipMemcpyAsync(s.wraw.p, hw, n * 4, hipMemcpyHostToDevice, stream()));
+            rw = s.wraw.as<float>();
+        }
+    }
     // large inputs: stable radix sort of (cell id, index) + gather + a search per cell (10^7 points: 0.6 ms against 2.2 ms of
     // the counting sort below, whose two passes are a global atomic per point each)
     if (n >= 200000 && n < ((int64_t)1 << 31) && !option("pairs_countsort")) {
@@ -835,8 +1004,12 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, int where, i
         ABACUS_TRY(s.idx.reserve(n1 * 4));
         ABACUS_TRY(s.idx2.reserve(n1 * 4));
         ABACUS_TRY(s.packed.reserve(n1 * 16));
-        ABACUS_LAUNCH("pair_cell_count", cell_count<false>, dim3(nblk), dim3(256), 0, rx, ry, rz, n, g, (unsigned int *)nullptr,
-                      s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>(), d_outside, d_frame);
+        if (hw)
+            ABACUS_LAUNCH("pair_cell_count", (cell_count<false, true>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, g, (unsigned int *)nullptr,
+                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>(), d_outside, d_frame);
+        else
+            ABACUS_LAUNCH("pair_cell_count", (cell_count<false, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, g, (unsigned int *)nullptr,
+                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>(), d_outside, d_frame);
         int end_bit = 1;
         while (((int64_t)1 << end_bit) < ncell) end_bit++;
         size_t tmp_bytes = 0;
@@ -848,21 +1021,28 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, int where, i
                                                                      s.idx.as<unsigned int>(), s.idx2.as<unsigned int>(), (int)n, 0, end_bit, stream());
         prof_end("pair_cell_sort");
         if (sorted != hipSuccess) return fail("abacus_paircount: radix sort failed");
-        ABACUS_LAUNCH("pair_cell_fill", cell_gather, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(), s.sx,
-                      s.sy, s.sz);
+        if (hw)
+            ABACUS_LAUNCH("pair_cell_fill", cell_gather<true>, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(),
+                          s.sx, s.sy, s.sz, s.sw);
+        else
+            ABACUS_LAUNCH("pair_cell_fill", cell_gather<false>, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(),
+                          s.sx, s.sy, s.sz, s.sw);
         const int cblk = (int)std::min<int64_t>(ceil_div(ncell + 1, 256), 8192);
         ABACUS_LAUNCH("pair_cell_starts", cell_starts, dim3(cblk), dim3(256), 0, s.keys2.as<unsigned int>(), n, ncell, s.start.as<int64_t>());
         return 0;
     }
     HIP_TRY(hipMemsetAsync(s.counts.p, 0, (size_t)(ncell + 1) * 4, stream()));
     if (n > 0)
-        ABACUS_LAUNCH("pair_cell_count", cell_count<true>, dim3(nblk), dim3(256), 0, rx, ry, rz, n, g,
+        ABACUS_LAUNCH("pair_cell_count", (cell_count<true, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, (const float *)nullptr, n, g,
                       s.counts.as<unsigned int>(), s.cellid.as<unsigned int>(), (unsigned int *)nullptr, (float4 *)nullptr, d_outside,
                       d_frame);
     ABACUS_TRY(exclusive_scan_u32(s.counts.as<unsigned int>(), ncell, s.start.as<int64_t>(), scratch, 1));
-    if (n > 0)
-        ABACUS_LAUNCH("pair_cell_fill", cell_fill, dim3(nblk), dim3(256), 0, rx, ry, rz, n,
-                      s.cellid.as<unsigned int>(), s.start.as<int64_t>(), s.counts.as<unsigned int>(), s.sx, s.sy, s.sz);
+    if (n > 0 && hw)
+        ABACUS_LAUNCH("pair_cell_fill", cell_fill<true>, dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n,
+                      s.cellid.as<unsigned int>(), s.start.as<int64_t>(), s.counts.as<unsigned int>(), s.sx, s.sy, s.sz, s.sw);
+    else if (n > 0)
+        ABACUS_LAUNCH("pair_cell_fill", cell_fill<false>, dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n,
+                      s.cellid.as<unsigned int>(), s.start.as<int64_t>(), s.counts.as<unsigned int>(), s.sx, s.sy, s.sz, s.sw);
     return 0;
 }
 
@@ -871,9 +1051,12 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, int where, i
 static unsigned long long g_last_evaluated = 0;   // candidate pairs of the last call (wave-per-cell kernel only)
 static int g_last_cells[3] = {0, 0, 0};
 
+// weighted: also wsum (and rsum unless NULL) per bin, by pair_count_w; w1 / w2 (host memory when where = 0, else device memory)
+// may be NULL: unit weights
 static int paircount_impl(int mode, const void *x1, const void *y1, const void *z1, int64_t n1, const void *x2, const void *y2,
                           const void *z2, int64_t n2, int where, float boxsize, const float *bins, int nbins, float pimax,
-                          int npibins, float mu_max, int nmubins, uint64_t *npairs) {
+                          int npibins, float mu_max, int nmubins, uint64_t *npairs, int weighted = 0, const float *w1 = nullptr,
+                          const float *w2 = nullptr, double *wsum = nullptr, double *rsum = nullptr) {
     ABACUS_ENTER();
     if (mode < 0 || mode > 2) return fail("abacus_paircount: unknown mode %d", mode);
     if (!x1 || !y1 || !z1 || !bins || !npairs || nbins < 1) return fail("abacus_paircount: null/empty argument");
@@ -881,16 +1064,21 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
     const int autocorr = x2 == nullptr;
     const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
     if (nsub < 1) return fail("abacus_paircount: need at least one pi / mu bin");
-    if (nsub > MAX_HIST) return fail("abacus_paircount: %d pi / mu bins exceed the LDS histogram", nsub);
-    // One launch bins into at most 63 separation bins (the kernels' edge tables) and MAX_HIST counters in LDS.  More bins -
+    const int max_hist = weighted ? W_MAX_HIST : MAX_HIST;
+    if (nsub > max_hist) return fail("abacus_paircount: %d pi / mu bins exceed the LDS histogram", nsub);
+    if (weighted && !wsum) return fail("abacus_paircount_weighted: wsum is NULL");
+    if (weighted && autocorr && w2) return fail("abacus_paircount_weighted: w2 given for an autocorrelation (x2 is NULL)");
+    // One launch bins into at most 63 separation bins (the kernels' edge tables) and MAX_HIST counters (weighted: W_MAX_HIST
+    // entries of 20 bytes) in LDS.  More bins -
     // Corrfunc takes any number - are counted in runs of consecutive separation bins, each a call of its own with its own,
     // smaller reach; a pair ON an edge shared by two runs belongs to the upper bin in both ([lo, hi) bins)
-    const int run = std::min(63, MAX_HIST / nsub);
+    const int run = std::min(63, max_hist / nsub);
     if (nbins > run) {
         for (int a = 0; a < nbins; a += run) {
             const int n = std::min(run, nbins - a);
+            const size_t o = (size_t)a * nsub;
             ABACUS_TRY(paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, where, boxsize, bins + a, n, pimax, npibins, mu_max,
-                                      nmubins, npairs + (size_t)a * nsub));
+                                      nmubins, npairs + o, weighted, w1, w2, wsum ? wsum + o : nullptr, rsum ? rsum + o : nullptr));
         }
         return 0;
     }
@@ -903,6 +1091,8 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
         return fail("abacus_paircount: maximum separation exceeds half the box (minimum image not unique)");
     const size_t ntot = (size_t)nbins * nsub;
     memset(npairs, 0, ntot * sizeof(uint64_t));
+    if (wsum) memset(wsum, 0, ntot * sizeof(double));
+    if (rsum) memset(rsum, 0, ntot * sizeof(double));
     if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
 
     CellGrid g;
@@ -916,9 +1106,9 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
         nc = std::min(nc, cap);
         return nc < 3 ? 1 : nc;
     };
-    const bool v1 = gen == 1;   // first-generation kernel (comparator of the tests)
+    const bool v1 = gen == 1 && !weighted;   // first-generation kernel (comparator of the tests)
     int R = 1;
-    if (!v1) {
+    if (!v1 && !weighted) {   // the weighted kernel walks 27 cells of the full reach
         const double nmax = (double)std::max(n1, autocorr ? n1 : n2);
         const double per_cell = nmax * ((double)reach_xy / boxsize) * ((double)reach_xy / boxsize) * ((double)reach_z / boxsize);
         if (gen >= 3 && per_cell > 12.0 && ncells(reach_xy, 2, 192) >= 5 && ncells(reach_z, 2, 192) >= 5) R = 2;
@@ -927,10 +1117,10 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
     g.ncz = ncells(reach_z, R, R == 2 ? 192 : 128);
     // the cap may leave cells larger than reach / R: still correct (a cell >= reach / R is all the stencil needs)
     const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-    const bool use3 = !v1 && gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1;
+    const bool use3 = !v1 && !weighted && gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1;
 
     static SortedSet S1, S2;
-    static DevBuf scratch, d_edges, d_npairs, d_work, d_flag;
+    static DevBuf scratch, d_edges, d_npairs, d_work, d_flag, d_sums;
     ABACUS_TRY(d_flag.reserve(64));
     HIP_TRY(hipMemsetAsync(d_flag.p, 0, 64, stream()));
     Frame *d_frame = reinterpret_cast<Frame *>(d_flag.as<int>() + 4);
@@ -941,8 +1131,8 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
         HIP_TRY(hipMemcpyAsync(d_frame, &f0, sizeof f0, hipMemcpyHostToDevice, stream()));
         HIP_TRY(hipStreamSynchronize(stream()));   // f0 is a stack object
     }
-    ABACUS_TRY(sort_into_cells(x1, y1, z1, where, n1, g, S1, scratch, d_flag.as<int>(), d_frame));
-    if (!autocorr) ABACUS_TRY(sort_into_cells(x2, y2, z2, where, n2, g, S2, scratch, d_flag.as<int>(), d_frame));
+    ABACUS_TRY(sort_into_cells(x1, y1, z1, w1, where, n1, g, S1, scratch, d_flag.as<int>(), d_frame));
+    if (!autocorr) ABACUS_TRY(sort_into_cells(x2, y2, z2, w2, where, n2, g, S2, scratch, d_flag.as<int>(), d_frame));
     SortedSet &T = autocorr ? S1 : S2;
 
     int nwork = 0, *d_wc = nullptr, *d_wo = nullptr;
@@ -1006,7 +1196,34 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
     a.start1 = S1.start.as<int64_t>();
     a.start2 = T.start.as<int64_t>();
     a.npairs = d_npairs.as<unsigned long long>();
-    if (v1) {
+    if (weighted) {
+        ABACUS_TRY(d_sums.reserve(2 * ntot * 8));
+        HIP_TRY(hipMemsetAsync(d_sums.p, 0, 2 * ntot * 8, stream()));
+        WeightArgs wa;
+        wa.w1 = S1.sw, wa.w2 = T.sw;
+        wa.wsum = d_sums.as<double>(), wa.rsum = wa.wsum + ntot;
+        int dev = 0, ncu = 256, per_cu = 2;
+        HIP_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        const size_t hist_bytes = ntot * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
+        const bool rs = rsum != nullptr;
+#define PW_FN(M) (rs ? (const void *)pair_count_w<M, true> : (const void *)pair_count_w<M, false>)
+        const void *fn = mode == 0 ? PW_FN(0) : (mode == 1 ? PW_FN(1) : PW_FN(2));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, PB, hist_bytes));
+        const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * std::max(per_cu, 1)));
+#define PW_RUN(M)                                                                                                               \
+    do {                                                                                                                        \
+        if (rs) ABACUS_LAUNCH("pair_count_w", (pair_count_w<M, true>), grid, dim3(PB), hist_bytes, a, wa, (int)ncell, d_eval);   \
+        else ABACUS_LAUNCH("pair_count_w", (pair_count_w<M, false>), grid, dim3(PB), hist_bytes, a, wa, (int)ncell, d_eval);     \
+    } while (0)
+        if (mode == 0) PW_RUN(0);
+        else if (mode == 1) PW_RUN(1);
+        else PW_RUN(2);
+#undef PW_RUN
+#undef PW_FN
+        HIP_TRY(hipMemcpyAsync(wsum, d_sums.p, ntot * 8, hipMemcpyDeviceToHost, stream()));
+        if (rsum) HIP_TRY(hipMemcpyAsync(rsum, d_sums.as<double>() + ntot, ntot * 8, hipMemcpyDeviceToHost, stream()));
+    } else if (v1) {
         if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
     } else if (use3) {
         int dev = 0, ncu = 256;
@@ -1070,6 +1287,24 @@ extern "C" int abacus_paircount_dev(int mode, const void *x1, const void *y1, co
     if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
     return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, pos_dtype == ABACUS_F32 ? 1 : 2, boxsize, bins, nbins, pimax,
                           npibins, mu_max, nmubins, npairs);
+}
+
+extern "C" int abacus_paircount_weighted(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
+                                         const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,
+                                         float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                                         int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, 0, boxsize, bins, nbins, pimax, npibins, mu_max, nmubins, npairs, 1,
+                          w1, w2, wsum, rsum);
+}
+
+extern "C" int abacus_paircount_weighted_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                                             const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2,
+                                             int pos_dtype, float boxsize, const float *bins, int nbins, float pimax, int npibins,
+                                             float mu_max, int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64)
+        return fail("abacus_paircount_weighted_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
+    return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, pos_dtype == ABACUS_F32 ? 1 : 2, boxsize, bins, nbins, pimax,
+                          npibins, mu_max, nmubins, npairs, 1, w1, w2, wsum, rsum);
 }
 
 extern "C" int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z, int *stencil_R) {

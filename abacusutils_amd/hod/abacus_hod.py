@@ -536,43 +536,49 @@ class AbacusHOD:
             return dev
         return mock_dict[tracer]['x'], mock_dict[tracer]['y'], mock_dict[tracer]['z']
 
-    def _pairs(self, mock_dict, fn):
+    def _pairs(self, mock_dict, fn, weights=None):
+        """`fn` over every tracer pair.  weights: None (the reference: a 'w' column is ignored), or the name of a column of
+        per-galaxy weights - tracers without it count with unit weights - handed to `fn` as w1= / w2=; the coordinates
+        stay in HBM either way, only the weights are uploaded"""
         clustering = {}
+        wcol = lambda tr: None if weights is None else mock_dict[tr].get(weights)   # noqa: E731
+        wkw = lambda tr1, tr2: {} if weights is None else dict(w1=wcol(tr1), w2=None if tr2 is None else wcol(tr2))   # noqa: E731
         for i1, tr1 in enumerate(mock_dict.keys()):
             x1, y1, z1 = self._xyz(mock_dict, tr1)
             for i2, tr2 in enumerate(mock_dict.keys()):
                 if i1 > i2:
                     continue  # cross-correlations are symmetric
                 if i1 == i2:
-                    clustering[tr1 + '_' + tr2] = fn(x1, y1, z1, None, None, None)
+                    clustering[tr1 + '_' + tr2] = fn(x1, y1, z1, None, None, None, **wkw(tr1, None))
                 else:
                     x2, y2, z2 = self._xyz(mock_dict, tr2)
                     if isinstance(x1, np.ndarray) != isinstance(x2, np.ndarray):   # one side only in HBM: both from the host
                         x1, y1, z1 = (mock_dict[tr1][c] for c in 'xyz')
                         x2, y2, z2 = (mock_dict[tr2][c] for c in 'xyz')
-                    clustering[tr1 + '_' + tr2] = fn(x1, y1, z1, x2, y2, z2)
+                    clustering[tr1 + '_' + tr2] = fn(x1, y1, z1, x2, y2, z2, **wkw(tr1, tr2))
                     clustering[tr2 + '_' + tr1] = clustering[tr1 + '_' + tr2]
         return clustering
 
-    def compute_xirppi(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8):
-        """xi(rp, pi) for every tracer pair (:1221-1279)"""
-        return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2: calc_xirppi_fast(
-            x1, y1, z1, rpbins, pimax, pi_bin_size, self.lbox, Nthread, x2=x2, y2=y2, z2=z2))
+    def compute_xirppi(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8, weights=None):
+        """xi(rp, pi) for every tracer pair (:1221-1279); weights: see `_pairs`"""
+        return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2, **w: calc_xirppi_fast(
+            x1, y1, z1, rpbins, pimax, pi_bin_size, self.lbox, Nthread, x2=x2, y2=y2, z2=z2, **w), weights)
 
-    def compute_wp(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8):
-        """wp(rp) for every tracer pair (:1826-1885)"""
-        return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2: calc_wp_fast(
-            x1, y1, z1, rpbins, pimax, self.lbox, Nthread, x2=x2, y2=y2, z2=z2))
+    def compute_wp(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8, weights=None):
+        """wp(rp) for every tracer pair (:1826-1885); weights: see `_pairs`"""
+        return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2, **w: calc_wp_fast(
+            x1, y1, z1, rpbins, pimax, self.lbox, Nthread, x2=x2, y2=y2, z2=z2, **w), weights)
 
-    def compute_multipole(self, mock_dict, rpbins, pimax, sbins, nbins_mu, orders=[0, 2], Nthread=8):
-        """wp concatenated with xi_l(s) (:1281-1336; like the reference, cross pairs use `rpbins` as s bins, :1313)"""
-        def fn(x1, y1, z1, x2, y2, z2):
+    def compute_multipole(self, mock_dict, rpbins, pimax, sbins, nbins_mu, orders=[0, 2], Nthread=8, weights=None):
+        """wp concatenated with xi_l(s) (:1281-1336; like the reference, cross pairs use `rpbins` as s bins, :1313);
+        weights: see `_pairs`"""
+        def fn(x1, y1, z1, x2, y2, z2, **w):
             sb = sbins if x2 is None else rpbins
             new_multi = calc_multipole_fast(x1, y1, z1, sb, self.lbox, Nthread, nbins_mu=nbins_mu, orders=orders,
-                                            x2=x2, y2=y2, z2=z2)
-            new_wp = calc_wp_fast(x1, y1, z1, rpbins, pimax, self.lbox, Nthread, x2=x2, y2=y2, z2=z2)
+                                            x2=x2, y2=y2, z2=z2, **w)
+            new_wp = calc_wp_fast(x1, y1, z1, rpbins, pimax, self.lbox, Nthread, x2=x2, y2=y2, z2=z2, **w)
             return np.concatenate((new_wp, new_multi))
-        return self._pairs(mock_dict, fn)
+        return self._pairs(mock_dict, fn, weights)
 
     def compute_power(self, mock_dict, nbins_k, nbins_mu, k_hMpc_max, logk, poles=[], paste='TSC', num_cells=550,
                       compensated=False, interlaced=False):

@@ -496,6 +496,27 @@ int abacus_paircount_dev(int mode, const void *x1, const void *y1, const void *z
                          const void *y2, const void *z2, int64_t n2, int pos_dtype, float boxsize, const float *bins,
                          int nbins, float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs);
 
+/*
+ * Weighted counts (Corrfunc's weights1 / weights2 with weight_type='pair_product', and its output_ravg / _rpavg / _savg).
+ * Beside npairs - bit-equal to what abacus_paircount returns for the same arguments - and laid out like it:
+ *   wsum  sum over the bin's pairs of w_i * w_j: float32 weights, the product formed in float64 (exact) and
+ *         accumulated in float64;
+ *   rsum  sum of the pair's separation - r (mode 0), rp = sqrt(dx^2 + dy^2) (mode 1), s (mode 2): the correctly rounded
+ *         float32 square root of the r^2 that chose the bin, accumulated in float64.  NULL: not computed.
+ * w1 / w2 NULL: unit weights.  x2 == NULL is the autocorrelation (ordered pairs) and w2 must then be NULL.
+ * The sums are accumulated by float64 atomics: their last bits depend on the run, |error| <= n * 2^-52 * sum|term| of a bin
+ * with n pairs.  abacus_paircount_stats reports the candidate pairs of a weighted call too (stencil_R = 0).
+ * _dev: coordinates as in abacus_paircount_dev, w1 / w2 float32 DEVICE pointers.
+ */
+int abacus_paircount_weighted(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
+                              const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2, float boxsize,
+                              const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
+                              uint64_t *npairs, double *wsum, double *rsum);
+int abacus_paircount_weighted_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                                  const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int pos_dtype,
+                                  float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                                  int nmubins, uint64_t *npairs, double *wsum, double *rsum);
+
 /* bookkeeping of the last pair-count call (bench.py's roofline): candidate pair separations the kernel evaluated (0 when an
  * older-generation kernel ran), cells per dimension in xy / z, stencil half-width in cells (1 or 2; 0: older kernel) */
 int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z, int *stencil_R);
