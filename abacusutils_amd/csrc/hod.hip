@@ -11,7 +11,9 @@
 // unchanged keys (from the second populate on) exact_sbidx -> emit (option hod_sbindex = 1: exact_index -> emit_bm):
 //   hod_exact_sbidx LRG alone, from the second populate on: hod_exact with the superblock's candidates read off the
 //        per-superblock key index (cum / sidx: a prefix of every mass bin's run at the populate's threshold code) instead
-//        of the tiles' queues; hod_emit follows.  Profiled as hod_exact.
+//        of the tiles' queues; hod_emit follows.  Profiled as hod_exact.  It writes the kept lists and counts only: the
+//        keep masks are deferred (hod_keep_masks writes them from the lists when abacus_hod_fetch_keep or a populate of
+//        another path asks; option hod_keepmasks = 1: maintained per populate as in hod_exact).
 //   hod_filter_key  streams the keys (2 B per object): `code > threshold[bin]` proves keep = 0 for the bulk of the objects
 //        (an envelope table bounds the marker chain over the bin's masses and the catalogue's environment ranges); the
 //        rest is queued per 2048-object tile.  hod_filter / hod_filter32 are the comparator and fallback filters
@@ -993,14 +995,17 @@ __device__ __forceinline__ unsigned int writelane_u32(unsigned int v, unsigned i
 // SRC: where the superblock's candidates come from - 0: the tiles' queues (filled by a filter or hod_deal); 1: the
 // per-superblock key index `sx` (see hod_sbindex_cum): thread b < 128 reads the length of bin b's candidate prefix at the
 // populate's threshold code and the bin's start in one round of loads, a scan over the bins replaces the one over the tiles,
-// and candidate j is one search over the bins plus one index read.  No queue counter is read or zeroed.  The previous
-// populate's kept count and first kept entries are requested in the same round (the slice is always allocated; what it
-// holds beyond the count is not used).
-template <int XB, bool PIPE, int SBT, int SRC = 0>
+// and candidate j is one search over the bins plus one index read.  No queue counter is read or zeroed.
+// MASKS (SRC 1 only; the queue forms always keep them): the keep bytes are maintained here - the previous populate's kept
+// count and first kept entries are requested in the round of the bin loads (the slice is always allocated; what it holds
+// beyond the count is not used), un-kept, and every kept object sets its byte.  Without it the kernel neither reads nor
+// writes a keep byte: the kept lists it leaves are the record, and hod_keep_masks writes the bytes when somebody asks.
+template <int XB, bool PIPE, int SBT, int SRC = 0, bool MASKS = true>
 __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, const abacus_hod_params &p, const SatPre &pre,
                                                const abacus_cls::ClsConst &cc, int use_cls, int clear_prev,
                                                const SbIndex *sx = nullptr) {
     static_assert(SRC == 0 || (!PIPE && XB >= 128 && SBT * TILE <= 65536), "the key index feeds the plain form");
+    static_assert(SRC == 1 || MASKS, "only the key index form may leave the keep masks alone");
     constexpr int SB_TILES = SBT, SB_OBJ = SBT * TILE, SB_WORDS = SB_OBJ / 32;
     constexpr int WORDS_PER_THREAD = SB_WORDS / XB;
     static_assert(SB_WORDS % XB == 0 && XB <= 512 && SB_OBJ <= 65536, "bitmap words must divide over the workgroup");
@@ -1040,7 +1045,7 @@ __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, c
             cnt = sx->cum[((int64_t)g * SBX_BINS + tid) * SBX_CODES + code];
             bs = sx->bstart[(int64_t)g * SBX_BINS + tid];
         }
-        if (clear_prev & 1) {
+        if (MASKS && (clear_prev & 1)) {
             prev_n = a.sb_counts[(int64_t)g * 4] + a.sb_counts[(int64_t)g * 4 + 1] + a.sb_counts[(int64_t)g * 4 + 2];
             prev_k0 = ((sat ? a.kept_s : a.kept_c) + obj_first)[tid];
         }
@@ -1073,13 +1078,13 @@ __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, c
         __syncthreads();
     }
     const int total = SRC == 1 ? s_bpre[SRC == 1 ? SBX_BINS : 0] : L.pre[SB_TILES];
-    if (SRC == 1 && (clear_prev & 1)) {   // the un-keep of the previous kept list (see below), its loads already under way
+    if (MASKS && SRC == 1 && (clear_prev & 1)) {   // the un-keep of the previous kept list (see below), its loads already under way
         const unsigned short *pk = (sat ? a.kept_s : a.kept_c) + obj_first;
         int8_t *keep = (sat ? a.keep_s : a.keep_c) + obj_first;
         if (tid < prev_n) keep[prev_k0] = 0;
         for (int e = tid + XB; e < prev_n; e += XB) keep[pk[e]] = 0;
         __syncthreads();
-    } else if (clear_prev & 1) {
+    } else if (MASKS && (clear_prev & 1)) {
         // Lazy keep masks (sparse mixes): the filter did not zero the 1 B per object - 20 MB of the 100 MB it moves at 1e7 +
         // 1e7 (23.8 -> 21.3 us; 83 -> 67 us at 4e7 + 4e7).  The only non-zero bytes are the objects the PREVIOUS populate
         // kept, and this superblock's share of them is still listed in its kept slice (counts in sb_counts, overwritten at
@@ -1126,7 +1131,7 @@ __device__ __forceinline__ void hod_exact_body(const HodPtrs &a, int first_sb, c
     };
     auto record = [&](const ExactCand &c, int kk) {
         if (kk) {
-            (sat ? a.keep_s : a.keep_c)[(int64_t)(tile_first + c.q) * TILE + c.loc] = (int8_t)kk;
+            if constexpr (MASKS) (sat ? a.keep_s : a.keep_c)[(int64_t)(tile_first + c.q) * TILE + c.loc] = (int8_t)kk;
             const int ls = c.q * TILE + c.loc;
             atomicOr(&L.bm[kk - 1][ls >> 5], 1u << (ls & 31));
         }
@@ -1297,13 +1302,36 @@ __global__ __launch_bounds__(XB) __attribute__((amdgpu_waves_per_eu(4))) void ho
 }
 
 // The plain form fed from the per-superblock key index (SRC = 1 above): with hod_emit behind it the whole populate of a sparse
-// mix on unchanged keys.  A kernel of its own, so that hod_exact_plain keeps its registers; this one runs at its 137, three
-// waves per SIMD and nothing in scratch (held to 128 it spills nine values).
+// mix on unchanged keys.  A kernel of its own, so that hod_exact_plain keeps its registers; nothing in scratch (held to 128
+// registers it spills).  It leaves the keep masks alone (see MASKS; the host marks them deferred).
 template <int XB, int SBT>
-__global__ __launch_bounds__(XB) void hod_exact_sbidx(HodPtrs a, abacus_hod_params p, SatPre pre,
-                                                                                               abacus_cls::ClsConst cc, int use_cls,
-                                                                                               int clear_prev, SbIndex sx) {
-    hod_exact_body<XB, false, SBT, 1>(a, 0, p, pre, cc, use_cls, clear_prev, &sx);
+__global__ __launch_bounds__(XB) void hod_exact_sbidx(HodPtrs a, abacus_hod_params p, SatPre pre, abacus_cls::ClsConst cc,
+                                                      int use_cls, SbIndex sx) {
+    hod_exact_body<XB, false, SBT, 1, false>(a, 0, p, pre, cc, use_cls, 0, &sx);
+}
+// ... and the form that keeps the masks exact populate by populate (`hod_keepmasks` = 1, the A/B comparator): 137 registers
+template <int XB, int SBT>
+__global__ __launch_bounds__(XB) void hod_exact_sbidx_masks(HodPtrs a, abacus_hod_params p, SatPre pre, abacus_cls::ClsConst cc,
+                                                            int use_cls, int clear_prev, SbIndex sx) {
+    hod_exact_body<XB, false, SBT, 1, true>(a, 0, p, pre, cc, use_cls, clear_prev, &sx);
+}
+
+// The keep masks of a populate that deferred them, from its kept lists: one workgroup per superblock of that populate's layout, entry e
+// of the slice is a kept object of tracer 0 below m0, 1 below m0 + m1, 2 above; its byte becomes tracer + 1.  The host
+// zeroes both masks in front of it.
+__global__ __launch_bounds__(256) void hod_keep_masks(int nsb_c, int nsb_s, int ntile_c, int ntile_s,
+                                                      const unsigned short *__restrict__ kept_c,
+                                                      const unsigned short *__restrict__ kept_s,
+                                                      const int *__restrict__ sb_counts, int8_t *__restrict__ keep_c,
+                                                      int8_t *__restrict__ keep_s) {
+    const int g = blockIdx.x;
+    const bool sat = g >= nsb_c;
+    const int S = sat ? g - nsb_c : g;
+    const int64_t obj_first = (int64_t)sb_first_tile(S, sat ? ntile_s : ntile_c, sat ? nsb_s : nsb_c) * TILE;
+    const int m0 = sb_counts[(int64_t)g * 4], m1 = sb_counts[(int64_t)g * 4 + 1], m2 = sb_counts[(int64_t)g * 4 + 2];
+    const unsigned short *kept = (sat ? kept_s : kept_c) + obj_first;
+    int8_t *keep = (sat ? keep_s : keep_c) + obj_first;
+    for (int e = threadIdx.x; e < m0 + m1 + m2; e += 256) keep[kept[e]] = (int8_t)(e < m0 ? 1 : (e < m0 + m1 ? 2 : 3));
 }
 
 // Index path without queues (sparse mixes, unchanged keys; `hod_deal` = 1 restores hod_deal -> hod_exact -> hod_emit): one
@@ -1406,35 +1434,45 @@ __device__ __forceinline__ int64_t wave_sum(int64_t v) {
 
 // the output offsets of superblock g: v[0..2] the counts of the superblocks of its kind in front of it, v[3..5] all central
 // counts (the satellites' offset); workgroup 0 also writes the totals Ncent[3], Nsat[3] for the host.  CS: ints per
-// superblock in sb_counts
+// superblock in sb_counts.  Two halves: the thread's share of the counts, from row `first` on (added to v), and the reduction
+// over the workgroup (every thread must reach its barriers).  v[0..2]: the counts of the superblocks of its kind in front of
+// g, v[3..5]: all central counts
 template <int EBLOCK, int CS>
-__device__ __forceinline__ void emit_offsets(int g, bool sat, int S, int nsb_c, int nsb_s, const int *__restrict__ sb_counts,
-                                             int64_t *__restrict__ totals, int64_t (&red)[EBLOCK / 64][6], int64_t (&v)[6]) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int t = 0; t < 6; t++) v[t] = 0;
-    const int *sb_c = sb_counts, *sb_s = sb_counts + (int64_t)nsb_c * CS;
-    const int *sb_mine = sat ? sb_s : sb_c;
+__device__ __forceinline__ void emit_offsets_sum(int g, bool sat, int S, int nsb_c, const int *__restrict__ sb_counts, int first,
+                                                 int64_t (&v)[6]) {
+    const int tid = threadIdx.x;
+    const int *sb_c = sb_counts, *sb_mine = sat ? sb_counts + (int64_t)nsb_c * CS : sb_c;
     // v[0..2]: counts of the superblocks of my kind in front of me; v[3..5]: all central counts (satellite offset,
     // and block 0 reports the totals)
-    for (int s = tid; s < S; s += EBLOCK)
+    for (int s = first + tid; s < S; s += EBLOCK)
 #pragma unroll
         for (int t = 0; t < 3; t++) v[t] += sb_mine[(int64_t)s * CS + t];
     if (sat || g == 0)
-        for (int s = tid; s < nsb_c; s += EBLOCK)
+        for (int s = first + tid; s < nsb_c; s += EBLOCK)
 #pragma unroll
             for (int t = 0; t < 3; t++) v[3 + t] += sb_c[(int64_t)s * CS + t];
+}
+// v (per thread) -> off[3], the output offsets per tracer.  Three sums cross the workgroup, not six: a superblock other than
+// the very first needs only v[t] + (satellites: v[3 + t]), and the very first (offsets 0) only the central totals v[3 + t]
+template <int EBLOCK, int CS>
+__device__ __forceinline__ void emit_offsets_reduce(int g, bool sat, int nsb_c, int nsb_s, const int *__restrict__ sb_counts,
+                                                    int64_t *__restrict__ totals, int64_t (&red)[EBLOCK / 64][3],
+                                                    const int64_t (&v)[6], int64_t (&off)[3]) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int *sb_s = sb_counts + (int64_t)nsb_c * CS;
+    int64_t u[3];
 #pragma unroll
-    for (int t = 0; t < 6; t++) v[t] = wave_sum(v[t]);
+    for (int t = 0; t < 3; t++) u[t] = wave_sum(g == 0 ? v[3 + t] : v[t] + (sat ? v[3 + t] : 0));
     if (lane == 0)
 #pragma unroll
-        for (int t = 0; t < 6; t++) red[wv][t] = v[t];
+        for (int t = 0; t < 3; t++) red[wv][t] = u[t];
     __syncthreads();
 #pragma unroll
-    for (int t = 0; t < 6; t++) {
-        v[t] = 0;
+    for (int t = 0; t < 3; t++) {
+        u[t] = 0;
 #pragma unroll
-        for (int w = 0; w < EBLOCK / 64; w++) v[t] += red[w][t];
+        for (int w = 0; w < EBLOCK / 64; w++) u[t] += red[w][t];
+        off[t] = g == 0 ? 0 : u[t];
     }
     if (g == 0) {   // totals for the host: Ncent[3], Nsat[3]
         int64_t s3[3] = {0, 0, 0};
@@ -1452,9 +1490,16 @@ __device__ __forceinline__ void emit_offsets(int g, bool sat, int S, int nsb_c, 
             int64_t tot = 0;
             for (int w = 0; w < EBLOCK / 64; w++) tot += red[w][tid];
             totals[3 + tid] = tot;
-            totals[tid] = tid == 0 ? v[3] : (tid == 1 ? v[4] : v[5]);
+            totals[tid] = tid == 0 ? u[0] : (tid == 1 ? u[1] : u[2]);
         }
     }
+}
+template <int EBLOCK, int CS>
+__device__ __forceinline__ void emit_offsets(int g, bool sat, int S, int nsb_c, int nsb_s, const int *__restrict__ sb_counts,
+                                             int64_t *__restrict__ totals, int64_t (&red)[EBLOCK / 64][3], int64_t (&off)[3]) {
+    int64_t v[6] = {0, 0, 0, 0, 0, 0};
+    emit_offsets_sum<EBLOCK, CS>(g, sat, S, nsb_c, sb_counts, 0, v);
+    emit_offsets_reduce<EBLOCK, CS>(g, sat, nsb_c, nsb_s, sb_counts, totals, red, v, off);
 }
 
 struct EmitPtrs {
@@ -1504,7 +1549,7 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
                                                    const unsigned short *__restrict__ kept_s,
                                                    const int *__restrict__ sb_counts, int64_t *__restrict__ totals,
                                                    EmitPtrs in, abacus_hod_params p, OutCols o_arg, int dbg) {
-    __shared__ int64_t red[EBLOCK / 64][6];
+    __shared__ int64_t red[EBLOCK / 64][3];
     // the column pointers and capacities are indexed by the galaxy's tracer: from a copy in LDS (an LDS read per use, counted
     // by lgkmcnt) - indexing the kernel arguments at run time made every galaxy load them from the argument segment with
     // vector memory loads, whose waits sat in front of the column stores
@@ -1517,16 +1562,40 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
     const bool sat = g >= nsb_c;
     const int S = sat ? g - nsb_c : g;
     const int64_t obj_first = (int64_t)sb_first_tile(S, sat ? ntile_s : ntile_c, sat ? nsb_s : nsb_c) * TILE;
-    int64_t v[6];
-    emit_offsets<EBLOCK, 4>(g, sat, S, nsb_c, nsb_s, sb_counts, totals, red, v);
-    const int m0 = sb_counts[(int64_t)g * 4], m1 = sb_counts[(int64_t)g * 4 + 1], m2 = sb_counts[(int64_t)g * 4 + 2];
-    const int total = m0 + m1 + m2;
-    if (total == 0) return;
-    const int64_t off0 = v[0] + (sat ? v[3] : 0), off1 = v[1] + (sat ? v[4] : 0), off2 = v[2] + (sat ? v[5] : 0);
+    int64_t off[3];
     const unsigned short *kept = (sat ? kept_s : kept_c) + obj_first;
     const double a0 = sat ? p.L_alpha_s : p.L_alpha_c, a1 = sat ? p.E_alpha_s : p.E_alpha_c,
                  a2 = sat ? p.Q_alpha_s : p.Q_alpha_c;
-    if (in.hrec && in.prec && !(dbg & 3)) {
+    // (the generic form comes first: behind it in the control flow, the waits the compiler places for ITS loads and stores would
+    // land between the untracked loads of the records form and serialise them)
+    if (!(in.hrec && in.prec) || (dbg & 3)) {   // caller-owned columns, ablations
+        emit_offsets<EBLOCK, 4>(g, sat, S, nsb_c, nsb_s, sb_counts, totals, red, off);
+        const int m0 = sb_counts[(int64_t)g * 4], m1 = sb_counts[(int64_t)g * 4 + 1], m2 = sb_counts[(int64_t)g * 4 + 2];
+        const int total = m0 + m1 + m2;
+        const int64_t off0 = off[0], off1 = off[1], off2 = off[2];
+        for (int e = tid; e < total; e += EBLOCK) {
+            const int t = e < m0 ? 0 : (e < m0 + m1 ? 1 : 2);
+            const int64_t j = t == 0 ? off0 + e : (t == 1 ? off1 + (e - m0) : off2 + (e - m0 - m1));
+            const int64_t i = obj_first + kept[e];
+            const double al = t == 0 ? a0 : (t == 1 ? a1 : a2);
+            double x, y, z, vx, vy, vz, m;
+            int64_t id;
+            if (dbg & 2) {   // ablation: no gather
+                x = y = z = vx = vy = vz = m = (double)i;
+                id = i;
+            } else {
+                emit_gather(in, sat, i, al, x, y, z, vx, vy, vz, m, id);
+            }
+            if (dbg & 1) {   // ablation: no column stores (one conditional store keeps the gather alive)
+                if (x + y + z + vx + vy + vz + m == 1.2345e300 && id == 77) o.c[t][0][j] = x;
+                continue;
+            }
+            emit_one(p, o, t, j, x, y, z, vx, vy, vz, m, id);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), known to the compiler: nothing of this form is pending behind it
+        return;
+    }
+    {
         // Records: software pipeline with untracked loads (see hod_exact).  Written plainly, an iteration was three dependent
         // waits - the kept index, the record line, and (vmcnt counts in order) the eight column stores of the iteration
         // before, which the wait for the kept index drained.  Here the stores of galaxy k are issued, then the record of
@@ -1544,16 +1613,50 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
                 aload16(r[5], q + o5);
         };
         auto dbl = [](unsigned int lo, unsigned int hi) { return __hiloint2double((int)hi, (int)lo); };
-        int e = tid;
-        if (e >= total) return;
+        // The head of the chain: only the store addresses need the offsets, so their loads go out TOGETHER with what the
+        // first record needs - this superblock's own counts and the thread's first two kept entries (the slice has
+        // SB_TILES_MAX tiles of slack behind the last superblock: in bounds; entries past `total` are stale and never become
+        // an address) - and the offsets are reduced while the record line is in flight.  Every lane issues every load (a
+        // lane without a galaxy reads the superblock's first object, a row past S row 0 of its kind), so each wave has the
+        // same loads outstanding and the counted waits below are exact; vmcnt counts in order.
+        // count rows per thread and prefix requested up front (superblocks beyond: the tracked loop, whose wait also drains the
+        // record): two cover LRG alone at 1e7 + 1e7; the larger workgroups of the dense mixes, whose time is the galaxy loop,
+        // take one and stay under the 96 registers at which three workgroups of 384 threads fit a CU
+        constexpr int OROWS = EBLOCK == 256 ? 2 : 1;
+        v4u cm, row[2 * OROWS];
         unsigned int k0, k1, k2 = 0;
         v4u r[6];
-        aload_u16(k0, kept + e);
-        aload_u16(k1, kept + min(e + EBLOCK, total - 1));
+        const int *sb_mine = sat ? sb_counts + (int64_t)nsb_c * 4 : sb_counts;
+        aload16(cm, sb_counts + (int64_t)g * 4);
+        aload_u16(k0, kept + tid);
+        aload_u16(k1, kept + tid + EBLOCK);
+#pragma unroll
+        for (int i = 0; i < OROWS; i++) {
+            const int s = tid + i * EBLOCK;
+            aload16(row[i], sb_mine + (int64_t)min(s, max(S - 1, 0)) * 4);
+            aload16(row[OROWS + i], sb_counts + (int64_t)min(s, max(nsb_c - 1, 0)) * 4);
+        }
+        await_vm<2 * OROWS>();   // the counts and the kept entries have landed
+        touch4(cm), touch1(k0), touch1(k1);
+        const int m0 = (int)cm.x, m1 = (int)cm.y, m2 = (int)cm.z;
+        const int total = m0 + m1 + m2;
+        int e = tid;
+        issue(e < total ? k0 : 0u, r);
+        await_vm<6>();   // the count rows have landed; the record is in flight
+        int64_t v[6] = {0, 0, 0, 0, 0, 0};
+        const bool need_c = sat || g == 0;
+#pragma unroll
+        for (int i = 0; i < OROWS; i++) {
+            touch4(row[i]), touch4(row[OROWS + i]);
+            const int s = tid + i * EBLOCK;
+            if (s < S) v[0] += (int)row[i].x, v[1] += (int)row[i].y, v[2] += (int)row[i].z;
+            if (need_c && s < nsb_c) v[3] += (int)row[OROWS + i].x, v[4] += (int)row[OROWS + i].y, v[5] += (int)row[OROWS + i].z;
+        }
+        emit_offsets_sum<EBLOCK, 4>(g, sat, S, nsb_c, sb_counts, OROWS * EBLOCK, v);
+        emit_offsets_reduce<EBLOCK, 4>(g, sat, nsb_c, nsb_s, sb_counts, totals, red, v, off);
+        const int64_t off0 = off[0], off1 = off[1], off2 = off[2];
         await_vm<0>();
-        touch1(k0), touch1(k1);
-        issue(k0, r);
-        await_vm<0>();
+        if (e >= total) return;
 #pragma unroll 1
         for (;;) {
 #pragma unroll
@@ -1596,25 +1699,6 @@ __global__ __launch_bounds__(EBLOCK) void hod_emit(int nsb_c, int nsb_s, int nti
             k1 = k2;
         }
         return;
-    }
-    for (int e = tid; e < total; e += EBLOCK) {
-        const int t = e < m0 ? 0 : (e < m0 + m1 ? 1 : 2);
-        const int64_t j = t == 0 ? off0 + e : (t == 1 ? off1 + (e - m0) : off2 + (e - m0 - m1));
-        const int64_t i = obj_first + kept[e];
-        const double al = t == 0 ? a0 : (t == 1 ? a1 : a2);
-        double x, y, z, vx, vy, vz, m;
-        int64_t id;
-        if (dbg & 2) {   // ablation: no gather
-            x = y = z = vx = vy = vz = m = (double)i;
-            id = i;
-        } else {
-            emit_gather(in, sat, i, al, x, y, z, vx, vy, vz, m, id);
-        }
-        if (dbg & 1) {   // ablation: no column stores (one conditional store keeps the gather alive)
-            if (x + y + z + vx + vy + vz + m == 1.2345e300 && id == 77) o.c[t][0][j] = x;
-            continue;
-        }
-        emit_one(p, o, t, j, x, y, z, vx, vy, vz, m, id);
     }
 }
 
@@ -2227,6 +2311,9 @@ struct abacus_hod_state {
     int64_t last_cand[2] = {-1, -1};
     bool kept_valid = false;    // the kept lists (superblocks of kept_sb_tiles tiles) name exactly the non-zero mask bytes
     int kept_sb_tiles = 0;
+    // ... once written: the per-superblock index path leaves the keep bytes stale and sets this flag; its kept lists are the
+    // truth until materialise_masks has run (kept_valid then says what the masks WILL hold)
+    bool masks_deferred = false;
     // queue-free index path (hod_exact_index / hod_emit_bm): per-tracer kept bitmaps over all objects, two sets alternating by
     // populate parity, and the look-back words of the emission
     DevBuf bm;
@@ -2265,7 +2352,7 @@ namespace {
 // the diagnostic options a populate reads, re-read only when one has been set since (option_version): a lookup takes the API
 // mutex and builds a std::string, about a dozen of them per populate.  Callers hold the API mutex.
 struct HodOpts {
-    int sbtiles, nobalance, norec, one_stage, f64filter, nokeys, nolazy, deal, noindex, nocls, pipe, eblock, dbg, sbindex;
+    int sbtiles, nobalance, norec, one_stage, f64filter, nokeys, nolazy, deal, noindex, nocls, pipe, eblock, dbg, sbindex, keepmasks;
 };
 const HodOpts &hod_opts() {
     static HodOpts o;
@@ -2277,7 +2364,7 @@ const HodOpts &hod_opts() {
         o.one_stage = option("hod_one_stage"), o.f64filter = option("hod_f64filter"), o.nokeys = option("hod_nokeys");
         o.nolazy = option("hod_nolazy"), o.deal = option("hod_deal"), o.noindex = option("hod_noindex");
         o.nocls = option("hod_nocls"), o.pipe = option("hod_pipe"), o.eblock = option("hod_eblock"), o.dbg = option("dbg");
-        o.sbindex = option("hod_sbindex");
+        o.sbindex = option("hod_sbindex"), o.keepmasks = option("hod_keepmasks");
         seen = v, have = true;
     }
     return o;
@@ -2648,14 +2735,37 @@ int populate_bitmaps(abacus_hod_state *st, const abacus_hod_params *p, const Sat
     return 0;   // kept_valid stays false: this path writes no kept lists; q_count is untouched (q_zero stays as it was)
 }
 
+// the keep masks a populate of the per-superblock index path left to its kept lists (masks_deferred): both masks zeroed, then
+// byte tracer + 1 for every entry of the lists.  That populate's layout is the sparse one over all tiles (set_superblocks may
+// already have chosen another for the populate that asks).  Afterwards kept_valid holds as it stands.
+int materialise_masks(abacus_hod_state *st) {
+    if (!st->masks_deferred) return 0;
+    if (st->nh) HIP_TRY(hipMemsetAsync(st->keep_c, 0, (size_t)st->nh, stream()));
+    if (st->np) HIP_TRY(hipMemsetAsync(st->keep_s, 0, (size_t)st->np, stream()));
+    const int nsb_c = (int)ceil_div(st->ntile_c, SB_TILES_SPARSE), nsb_s = (int)ceil_div(st->ntile_s, SB_TILES_SPARSE);
+    if (nsb_c + nsb_s > 0)
+        ABACUS_LAUNCH("hod_keep_masks", hod_keep_masks, dim3(nsb_c + nsb_s), dim3(256), 0, nsb_c, nsb_s, st->ntile_c, st->ntile_s,
+                      (const unsigned short *)st->kept_c, (const unsigned short *)st->kept_s, (const int *)st->sb_counts, st->keep_c,
+                      st->keep_s);
+    st->masks_deferred = false;
+    return 0;
+}
+
 // sparse mixes on unchanged keys: hod_exact_sbidx from the per-superblock key index, then hod_emit over the kept lists it
-// wrote.  `lazy`: the kept lists of the previous populate name the non-zero keep bytes (the kernel un-keeps them); otherwise
-// (the first such populate, after the bitmap path, the NFW path, another superblock size) the masks are cleared here once.
+// wrote.  The keep masks are not touched: the populate leaves them deferred (materialise_masks).  `hod_keepmasks` = 1 (the A/B
+// comparator) keeps them exact populate by populate instead: the kernel un-keeps the previous kept lists where they name the
+// non-zero bytes; otherwise (the first such populate, after the bitmap path, the NFW path, another superblock size) the masks
+// are cleared here once (`lists_valid`: the previous populate's lists are of this layout and name the masks' bytes).
 int populate_sbindex(abacus_hod_state *st, const abacus_hod_params *p, const SatPre &pre, const HodPtrs &a, const KeyTab &kt,
-                     bool lazy) {
-    if (!lazy) {
-        if (st->nh) HIP_TRY(hipMemsetAsync(st->keep_c, 0, (size_t)st->nh, stream()));
-        if (st->np) HIP_TRY(hipMemsetAsync(st->keep_s, 0, (size_t)st->np, stream()));
+                     bool lists_valid) {
+    const bool keepmasks = hod_opts().keepmasks != 0;
+    const bool lazy = keepmasks && lists_valid;
+    if (keepmasks) {
+        ABACUS_TRY(materialise_masks(st));
+        if (!lazy) {
+            if (st->nh) HIP_TRY(hipMemsetAsync(st->keep_c, 0, (size_t)st->nh, stream()));
+            if (st->np) HIP_TRY(hipMemsetAsync(st->keep_s, 0, (size_t)st->np, stream()));
+        }
     }
     abacus_cls::ClsConst cc;
     abacus_cls::make_cls_const(*p, pre, cc);
@@ -2666,13 +2776,16 @@ int populate_sbindex(abacus_hod_state *st, const abacus_hod_params *p, const Sat
     for (int l = 0; l < 64; l++)
         sx.tc[0][l] = kt.c[2 * l] | ((unsigned int)kt.c[2 * l + 1] << 16), sx.tc[1][l] = kt.s[2 * l] | ((unsigned int)kt.s[2 * l + 1] << 16);
     const int nsb = st->nsb_c + st->nsb_s;
-    if (nsb > 0)
-        ABACUS_LAUNCH("hod_exact", (hod_exact_sbidx<256, SB_TILES_SPARSE>), dim3(nsb), dim3(256), 0, a, *p, pre, cc, use_cls,
+    if (nsb > 0 && keepmasks)
+        ABACUS_LAUNCH("hod_exact", (hod_exact_sbidx_masks<256, SB_TILES_SPARSE>), dim3(nsb), dim3(256), 0, a, *p, pre, cc, use_cls,
                       lazy ? 1 : 0, sx);
+    else if (nsb > 0)
+        ABACUS_LAUNCH("hod_exact", (hod_exact_sbidx<256, SB_TILES_SPARSE>), dim3(nsb), dim3(256), 0, a, *p, pre, cc, use_cls, sx);
     ABACUS_TRY(launch_emit(st));   // emit_bm is off: hod_emit over the kept lists
     st->have_run = true;
     st->counts_valid = false;
-    st->kept_valid = true, st->kept_sb_tiles = st->sb_tiles;   // every mask byte that is set is in a kept list
+    st->masks_deferred = !keepmasks;
+    st->kept_valid = true, st->kept_sb_tiles = st->sb_tiles;   // every mask byte that is set (or will be) is in a kept list
     return 0;   // q_count is untouched (q_zero stays as it was); bm_valid is off: the bitmap path clears its state on entry
 }
 
@@ -2859,6 +2972,7 @@ int abacus_hod_populate_nfw(abacus_hod_state *st, const abacus_hod_params *p, co
     HodPtrs a;
     memset(&a, 0, sizeof a);
     set_superblocks(st, p);
+    ABACUS_TRY(materialise_masks(st));   // the particles' masks are kept as the previous populate decided them
     st->kept_valid = false;   // the particles' masks and kept lists are left as they are: no lazy masks after this path
     st->bm_valid = st->emit_bm = false;
     st->q_zero = false, st->last_cand[0] = st->last_cand[1] = -1;
@@ -3054,6 +3168,8 @@ int abacus_hod_populate_async(abacus_hod_state *st, const abacus_hod_params *p) 
     }
     if (!index_mode) st->last_cand[0] = st->last_cand[1] = -1;
     if (index_mode && sbx_mix && st->sbx_ok) return populate_sbindex(st, p, pre, a, keytab, sbx_lazy);
+    // every other path reads or rewrites the keep bytes: they must be what the previous populate's kept lists say
+    ABACUS_TRY(materialise_masks(st));
     if (index_mode && bm_path) return populate_bitmaps(st, p, pre, a, deal, bm_was_valid);
     const int exact_flags = (lazy_masks ? 1 : 0) | (index_mode ? 2 : 0);
     // `first`, `count` in global tile ids (centrals first): the shadow path launches the two kinds separately
@@ -3270,6 +3386,7 @@ int abacus_hod_device_columns(abacus_hod_state *st, int tracer, void *cols[8]) {
 int abacus_hod_fetch_keep(abacus_hod_state *st, int8_t *keep_cent, int8_t *keep_sat) {
     ABACUS_ENTER();
     if (!st || !st->have_run) return fail("abacus_hod_fetch_keep: populate has not been called");
+    ABACUS_TRY(materialise_masks(st));
     if (keep_cent && st->nh) HIP_TRY(hipMemcpyAsync(keep_cent, st->keep_c, st->nh, hipMemcpyDeviceToHost, stream()));
     if (keep_sat && st->np) HIP_TRY(hipMemcpyAsync(keep_sat, st->keep_s, st->np, hipMemcpyDeviceToHost, stream()));
     HIP_TRY(hipStreamSynchronize(stream()));

@@ -70,7 +70,9 @@ int abacus_profile_get(const char **names, double *total_ms, int64_t *launches, 
  * hod_f64filter, hod_norec, hod_nokeys, hod_pipe (1 / 2: pipelined hod_exact off / on), hod_eblock (256 / 512 threads per
  * hod_emit workgroup), hod_sbtiles (8 / 16 tiles per superblock), hod_nolazy / hod_noindex (no lazy
  * keep masks / no mass-sorted key index), hod_deal (the index path through hod_deal and the tile queues),
- * hod_sbindex (1: the index path through the global index, hod_exact_index and hod_emit_bm, instead of the per-superblock index), dbg / dbg_fft / dbg_tsc (ablation bit masks).  Default 0 = the production path. */
+ * hod_sbindex (1: the index path through the global index, hod_exact_index and hod_emit_bm, instead of the per-superblock index),
+ * hod_keepmasks (1: the per-superblock index path keeps the keep masks exact populate by populate instead of writing them on
+ * demand), dbg / dbg_fft / dbg_tsc (ablation bit masks).  Default 0 = the production path. */
 int abacus_set_option(const char *name, int value);
 int abacus_get_option(const char *name);
 
