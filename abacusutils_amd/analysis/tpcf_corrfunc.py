@@ -292,3 +292,290 @@ def calc_wp_fast(x1, y1, z1, rpbins, pimax, lbox, Nthread, num_cells=30, x2=None
     dd, rr = _natural_estimator(DDrppi, (x1, y1, z1), (x2, y2, z2), edges, lbox, annulus, pimax, nthreads=Nthread,
                                 binfile=edges, pimax=np.float32(pimax), max_cells_per_dim=num_cells, w1=w1, w2=w2)
     return 2 * np.sum(dd / rr[:, None] - 1, axis=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Light cones: pair counts with a pairwise line of sight on an open grid (csrc/pairs.hip: pair_count_los, C ABI
+# abacus_paircount_los[_dev]) and the Landy-Szalay estimators on top.  The reference leaves this to Corrfunc.mocks; no
+# Corrfunc run stands behind the code here - the conventions are those of include/abacus_hip.h, pinned against the NumPy
+# statement tests/pairs_los_statement.py only.
+
+def _paircount_los(mode, X1, Y1, Z1, bins, X2=None, Y2=None, Z2=None, W1=None, W2=None, origin=(0.0, 0.0, 0.0), pimax=0.0,
+                   npibins=0, mu_max=1.0, nmubins=0, want_sums=True, want_rsum=True):
+    """(npairs, wsum, rsum) per (bin, sub-bin) of the light-cone counter; wsum and rsum are None when `want_sums` is false
+    (integer counts only), rsum when `want_rsum` is false.  Columns: host arrays (float64 columns are centred on `origin` in
+    float64 here, float32 ones on the device in float32) or - all of them - DeviceArray columns of one dtype; weights as in
+    `_paircount_weighted`"""
+    bins = _f4(bins)
+    nb = len(bins) - 1
+    nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
+    if nb < 1 or nsub < 1:
+        raise ValueError('need at least one separation bin and one pi / mu bin')
+    origin = np.ascontiguousarray(origin, dtype=np.float64)
+    if origin.shape != (3,):
+        raise ValueError(f'origin has shape {origin.shape}, expected (3,)')
+    out = np.zeros(nb * nsub, dtype=np.uint64)
+    wsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums else None
+    rsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums and want_rsum else None
+    if X2 is None and W2 is not None:
+        raise ValueError('weights2 given for an autocorrelation')
+    n1, n2 = len(X1), (0 if X2 is None else len(X2))
+    for name, w, n in (('weights1', W1, n1), ('weights2', W2, n2)):
+        if w is not None and (len(w.shape) != 1 or w.shape[0] != n):
+            raise ValueError(f'{name} has shape {tuple(w.shape)}, expected ({n},)')
+    cols = [c for c in (X1, Y1, Z1, X2, Y2, Z2) if c is not None]
+    tail = lambda org: (ptr(org), ptr(bins), int(nb), C.c_float(pimax), int(npibins), C.c_float(mu_max), int(nmubins),   # noqa: E731
+                        ptr(out), ptr(wsum), ptr(rsum))
+    if any(isinstance(c, _lib.DeviceArray) for c in cols):
+        if not all(isinstance(c, _lib.DeviceArray) and c.dtype == cols[0].dtype for c in cols):
+            raise TypeError('device-resident coordinates: every column must be a DeviceArray of one dtype')
+        dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[cols[0].dtype]
+        dp = lambda c: None if c is None else c.ptr     # noqa: E731
+        own = []
+
+        def dev_w(w):
+            if w is None:
+                return None
+            if isinstance(w, _lib.DeviceArray):
+                if w.dtype != np.float32:
+                    raise TypeError('device-resident weights must be float32')
+                return w
+            own.append(_lib.DeviceArray(_f4(w)))
+            return own[-1]
+        try:
+            d1, d2 = dev_w(W1), dev_w(W2)
+            check(_lib.lib().abacus_paircount_los_dev(
+                int(mode), dp(X1), dp(Y1), dp(Z1), dp(d1), C.c_int64(n1), dp(X2), dp(Y2), dp(Z2), dp(d2), C.c_int64(n2), dt,
+                *tail(origin)))
+        finally:
+            for a in own:
+                a.free()
+        return out, wsum, rsum
+    if isinstance(W1, _lib.DeviceArray) or isinstance(W2, _lib.DeviceArray):
+        raise TypeError('device-resident weights need device-resident coordinates')
+    host = [None if c is None else np.asarray(c) for c in (X1, Y1, Z1, X2, Y2, Z2)]
+    if any(c is not None and c.dtype == np.float64 for c in host):
+        # float64 columns: the subtraction in float64, one rounding to float32 - on the host, the C ABI takes float32 arrays
+        host = [None if c is None else (c - c.dtype.type(origin[i % 3])).astype(np.float32) if c.dtype == np.float64
+                else _f4(c) - np.float32(origin[i % 3]) for i, c in enumerate(host)]
+        origin = np.zeros(3)
+    X1, Y1, Z1, X2, Y2, Z2 = map(_f4, host)
+    W1, W2 = _f4(W1), _f4(W2)
+    check(_lib.lib().abacus_paircount_los(
+        int(mode), ptr(X1), ptr(Y1), ptr(Z1), ptr(W1), C.c_int64(n1), ptr(X2), ptr(Y2), ptr(Z2), ptr(W2), C.c_int64(n2),
+        *tail(origin)))
+    return out, wsum, rsum
+
+
+def _count_los(mode, autocorr, bins, nsub, extra, X1, Y1, Z1, X2, Y2, Z2, origin, kw, avg_kw, **geom):
+    """the body shared by DD_los / DDrppi_los / DDsmu_los: `_count` without a box"""
+    second = (None, None, None) if autocorr else (X2, Y2, Z2)
+    if not autocorr and any(c is None for c in second):
+        raise ValueError('a cross count needs X2, Y2 and Z2')
+    wk = _weight_kw(kw, avg_kw, autocorr)
+    if wk is None:
+        n, _, _ = _paircount_los(mode, X1, Y1, Z1, bins, *second, origin=origin, want_sums=False, **geom)
+        return _result(n, bins, nsub, extra)
+    n, ws, rs = _paircount_los(mode, X1, Y1, Z1, bins, *second, W1=_w_arr(wk[0]), W2=_w_arr(wk[1]), origin=origin,
+                               want_rsum=wk[2], **geom)
+    return _result(n, bins, nsub, extra, sums=(ws, rs), avg_name=avg_kw[len('output_'):])
+
+
+def DD_los(autocorr, nthreads, binfile, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0), **kw):
+    """pair counts in s bins of a non-periodic catalogue in Cartesian columns seen from `origin` (no box, no wrapping);
+    weights1 / weights2 / weight_type / output_ravg as `DD`"""
+    bins = np.asarray(binfile, dtype=np.float64)
+    return _count_los(0, autocorr, bins, 1, {}, X1, Y1, Z1, X2, Y2, Z2, origin, kw, 'output_ravg')
+
+
+def DDrppi_los(autocorr, nthreads, binfile, pimax, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0), **kw):
+    """pair counts in (rp, pi) with the line of sight of each PAIR, l = p_i + p_j seen from `origin`: pi = |d.l| / |l|,
+    rp^2 = s^2 - pi^2, unit pi bins up to pimax; weight keywords as `DDrppi`"""
+    if not pimax > 0:
+        raise ValueError('pimax must be positive')
+    bins = np.asarray(binfile, dtype=np.float64)
+    npi = int(pimax)
+    if npi < 1:
+        raise ValueError('pimax must be at least 1 (unit pi bins)')
+    return _count_los(1, autocorr, bins, npi, {'pimax': np.arange(1, npi + 1, dtype='f8')}, X1, Y1, Z1, X2, Y2, Z2, origin, kw,
+                      'output_rpavg', pimax=float(pimax), npibins=npi)
+
+
+def DDsmu_los(autocorr, nthreads, binfile, mu_max, nmu_bins, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0),
+              **kw):
+    """pair counts in (s, mu), mu = pi / s with the pairwise line of sight of `DDrppi_los`; weight keywords as `DDsmu`"""
+    if not mu_max > 0 or int(nmu_bins) < 1:
+        raise ValueError('mu_max must be positive, with at least one mu bin')
+    bins = np.asarray(binfile, dtype=np.float64)
+    return _count_los(2, autocorr, bins, int(nmu_bins), {'mumax': (np.arange(1, nmu_bins + 1) * mu_max / nmu_bins)}, X1, Y1, Z1,
+                      X2, Y2, Z2, origin, kw, 'output_savg', mu_max=float(mu_max), nmubins=int(nmu_bins))
+
+
+def radec_to_xyz(ra_deg, dec_deg, dist):
+    """float64 Cartesian columns of (right ascension, declination) in degrees and a comoving distance:
+    x = d cos(dec) cos(ra), y = d cos(dec) sin(ra), z = d sin(dec)"""
+    ra, dec = np.radians(np.asarray(ra_deg, dtype=np.float64)), np.radians(np.asarray(dec_deg, dtype=np.float64))
+    d = np.asarray(dist, dtype=np.float64)
+    return d * np.cos(dec) * np.cos(ra), d * np.cos(dec) * np.sin(ra), d * np.sin(dec)
+
+
+def _mocks_columns(is_comoving_dist, RA1, DEC1, CZ1, RA2, DEC2, CZ2, autocorr):
+    if not is_comoving_dist:
+        raise NotImplementedError('is_comoving_dist=False needs a cosmology to turn cz into distances; none is carried here: '
+                                  'pass comoving distances and is_comoving_dist=True')
+    first = radec_to_xyz(RA1, DEC1, CZ1)
+    if autocorr:
+        return first, (None, None, None)
+    if RA2 is None or DEC2 is None or CZ2 is None:
+        raise ValueError('a cross count needs RA2, DEC2 and CZ2')
+    return first, radec_to_xyz(RA2, DEC2, CZ2)
+
+
+def DDrppi_mocks(autocorr, cosmology, nthreads, pimax, binfile, RA1, DEC1, CZ1, weights1=None, RA2=None, DEC2=None, CZ2=None,
+                 weights2=None, is_comoving_dist=False, **kw):
+    """Corrfunc.mocks.DDrppi_mocks over `DDrppi_los`.  The argument order is Corrfunc's published one as far as it can be
+    recalled without the package at hand - check it against your Corrfunc before relying on positional calls.  `cosmology`
+    is accepted and ignored; the CZ columns must be comoving distances (is_comoving_dist=True), else NotImplementedError."""
+    first, second = _mocks_columns(is_comoving_dist, RA1, DEC1, CZ1, RA2, DEC2, CZ2, autocorr)
+    return DDrppi_los(autocorr, nthreads, binfile, pimax, *first, *second, weights1=weights1, weights2=weights2, **kw)
+
+
+def DDsmu_mocks(autocorr, cosmology, nthreads, mu_max, nmu_bins, binfile, RA1, DEC1, CZ1, weights1=None, RA2=None, DEC2=None,
+                CZ2=None, weights2=None, is_comoving_dist=False, **kw):
+    """Corrfunc.mocks.DDsmu_mocks over `DDsmu_los`; the remarks of `DDrppi_mocks` on argument order, `cosmology` and
+    `is_comoving_dist` apply"""
+    first, second = _mocks_columns(is_comoving_dist, RA1, DEC1, CZ1, RA2, DEC2, CZ2, autocorr)
+    return DDsmu_los(autocorr, nthreads, binfile, mu_max, nmu_bins, *first, *second, weights1=weights1, weights2=weights2, **kw)
+
+
+class _LCSample:
+    """a point set of the Landy-Szalay estimators: observer-centred float32 columns in HBM (centred ONCE, then counted against
+    several other sets with origin 0), float32 weights in HBM or None, W = sum w and sum w^2 in float64"""
+
+    def __init__(self, x, y, z, w=None, origin=(0.0, 0.0, 0.0)):
+        origin = np.asarray(origin, dtype=np.float64)
+        cols = (x, y, z)
+        self.n = len(x)
+        if all(isinstance(c, _lib.DeviceArray) for c in cols):
+            if cols[0].dtype == np.float32 and not origin.any():
+                self.cols = list(cols)
+            else:
+                dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[cols[0].dtype]
+                self.cols = [_lib.DeviceArray(nbytes=4 * self.n, dtype=np.float32, shape=(self.n,)) for _ in cols]
+                for c, o, dst in zip(cols, origin, self.cols):
+                    check(_lib.lib().abacus_paircount_los_centre(c.ptr, dt, C.c_int64(self.n), C.c_double(o), dst.ptr))
+        elif any(isinstance(c, _lib.DeviceArray) for c in cols):
+            raise TypeError('device-resident coordinates: every column must be a DeviceArray')
+        else:
+            host = [np.asarray(c) for c in cols]
+            host = [c if c.dtype == np.float64 else c.astype(np.float32) for c in host]
+            self.cols = [_lib.DeviceArray((c - c.dtype.type(o)).astype(np.float32)) for c, o in zip(host, origin)]
+        if w is None:
+            self.w, self.W, self.W2 = None, float(self.n), float(self.n)
+        else:
+            hw = _host(w).astype(np.float64)
+            if hw.shape != (self.n,):
+                raise ValueError(f'weights have shape {hw.shape}, expected ({self.n},)')
+            self.w = w if isinstance(w, _lib.DeviceArray) else _lib.DeviceArray(hw.astype(np.float32))
+            self.W, self.W2 = float(hw.sum()), float((hw * hw).sum())
+
+    @property
+    def auto_norm(self):
+        """normalisation of the ordered autocorrelation: W^2 - sum w^2 (N (N - 1) for unit weights)"""
+        return self.W * self.W - self.W2
+
+
+def _ls_weightsum(mode, a, b, bins, geom):
+    """sum of w_i w_j per (bin, sub-bin) of sample `a` with itself (b None, ordered pairs) or with sample `b`"""
+    second = (None, None, None) if b is None else b.cols
+    _, ws, _ = _paircount_los(mode, *a.cols, bins, *second, W1=a.w, W2=None if b is None else b.w, want_rsum=False, **geom)
+    return ws
+
+
+class LCRandoms(_LCSample):
+    """The randoms of a light-cone catalogue for `calc_xirppi_lc` / `calc_wp_lc` / `calc_multipole_lc`: uploaded once,
+    and RR - the most expensive term - counted once per (mode, bins, pi / mu binning) and kept."""
+
+    def __init__(self, x, y, z, w=None, origin=(0.0, 0.0, 0.0)):
+        super().__init__(x, y, z, w, origin)
+        self._rr = {}
+        self.rr_counted = 0      # RR runs so far (a cache hit does not count)
+
+    def rr(self, mode, bins, geom):
+        key = (int(mode), _f4(bins).tobytes(), tuple(sorted(geom.items())))
+        if key not in self._rr:
+            self._rr[key] = _ls_weightsum(mode, self, None, bins, geom)
+            self.rr_counted += 1
+        return self._rr[key]
+
+
+def landy_szalay(d1d2, d1r, d2r, rr, n12, n1r, n2r, nrr):
+    """xi = (D1D2 / N12 - D1R / N1r - D2R / N2r + RR / Nrr) / (RR / Nrr), every term a weight sum, float64; a bin without RR
+    pairs comes out as nan or inf"""
+    d1d2, d1r, d2r, rr = (np.asarray(a, dtype=np.float64) for a in (d1d2, d1r, d2r, rr))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return (d1d2 / n12 - d1r / n1r - d2r / n2r + rr / nrr) / (rr / nrr)
+
+
+def _ls_terms(mode, s1, s2, randoms, bins, geom):
+    """the four weight sums and their normalisations.  Cross normalisations are Wa Wb, those of the ordered autocorrelations
+    W^2 - sum w^2; an autocorrelation counts DR once: D2R = D1R"""
+    if not isinstance(randoms, LCRandoms):
+        raise TypeError('randoms must be an LCRandoms')
+    rr = randoms.rr(mode, bins, geom)
+    d1r = _ls_weightsum(mode, s1, randoms, bins, geom)
+    if s2 is None:
+        dd, n12 = _ls_weightsum(mode, s1, None, bins, geom), s1.auto_norm
+        d2r, n2r = d1r, s1.W * randoms.W
+    else:
+        dd, n12 = _ls_weightsum(mode, s1, s2, bins, geom), s1.W * s2.W
+        d2r, n2r = _ls_weightsum(mode, s2, randoms, bins, geom), s2.W * randoms.W
+    return (dd, d1r, d2r, rr), (n12, s1.W * randoms.W, n2r, randoms.auto_norm)
+
+
+def _ls_samples(x1, y1, z1, x2, y2, z2, w1, w2, origin):
+    s1 = _LCSample(x1, y1, z1, w1, origin)
+    if x2 is None:
+        if w2 is not None:
+            raise ValueError('w2 given for an autocorrelation')
+        return s1, None
+    return s1, _LCSample(x2, y2, z2, w2, origin)
+
+
+def calc_xirppi_lc(x1, y1, z1, rpbins, pimax, pi_bin_size, randoms, Nthread=1, x2=None, y2=None, z2=None, w1=None, w2=None,
+                   origin=(0.0, 0.0, 0.0)):
+    """Landy-Szalay xi(rp, pi) of a light-cone catalogue seen from `origin`, in pi bins of `pi_bin_size` built from unit pi
+    bins (every count is grouped before the estimator is formed): the shape of `calc_xirppi_fast`.  randoms: an LCRandoms"""
+    _check_int('pimax', pimax)
+    _check_int('pi_bin_size', pi_bin_size)
+    if pimax % pi_bin_size:
+        raise ValueError('pi_bin_size needs to be an integer divisor of pimax, current values are ', pi_bin_size, pimax)
+    edges = np.asarray(rpbins).astype(np.float32)
+    s1, s2 = _ls_samples(x1, y1, z1, x2, y2, z2, w1, w2, origin)
+    terms, norms = _ls_terms(1, s1, s2, randoms, edges, dict(pimax=float(pimax), npibins=int(pimax)))
+    group = lambda a: a.reshape(len(edges) - 1, pimax // pi_bin_size, pi_bin_size).sum(axis=2)   # noqa: E731
+    return landy_szalay(*map(group, terms), *norms)
+
+
+def calc_wp_lc(x1, y1, z1, rpbins, pimax, randoms, Nthread=1, x2=None, y2=None, z2=None, w1=None, w2=None,
+               origin=(0.0, 0.0, 0.0)):
+    """wp(rp) = 2 * sum over unit pi bins of the Landy-Szalay xi(rp, pi): the shape of `calc_wp_fast`"""
+    _check_int('pimax', pimax)
+    edges = np.asarray(rpbins).astype(np.float32)
+    s1, s2 = _ls_samples(x1, y1, z1, x2, y2, z2, w1, w2, origin)
+    terms, norms = _ls_terms(1, s1, s2, randoms, edges, dict(pimax=float(pimax), npibins=int(pimax)))
+    shape = lambda a: a.reshape(len(edges) - 1, pimax)   # noqa: E731
+    return 2 * np.sum(landy_szalay(*map(shape, terms), *norms), axis=1)
+
+
+def calc_multipole_lc(x1, y1, z1, sbins, randoms, Nthread=1, nbins_mu=50, x2=None, y2=None, z2=None, orders=[0, 2], w1=None,
+                      w2=None, origin=(0.0, 0.0, 0.0)):
+    """xi_l(s), the requested orders concatenated, from the Landy-Szalay xi(s, mu) in `nbins_mu` bins of mu in [0, 1): the
+    shape of `calc_multipole_fast`"""
+    edges = np.asarray(sbins).astype(np.float32)
+    mu_edges = np.linspace(0, 1, nbins_mu + 1)
+    s1, s2 = _ls_samples(x1, y1, z1, x2, y2, z2, w1, w2, origin)
+    terms, norms = _ls_terms(2, s1, s2, randoms, edges, dict(mu_max=1.0, nmubins=int(nbins_mu)))
+    shape = lambda a: a.reshape(len(edges) - 1, nbins_mu)   # noqa: E731
+    xi = landy_szalay(*map(shape, terms), *norms)
+    return np.concatenate([tpcf_multipole(xi, mu_edges, order=ell) for ell in orders])

@@ -945,6 +945,241 @@ __global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, in
         }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Light cones: pair counts with a PAIRWISE line of sight on an OPEN grid (abacus_paircount_los, Corrfunc.mocks' DDrppi_mocks /
+// DDsmu_mocks on Cartesian columns).  No reference code and no Corrfunc run stands behind this; the conventions are restated
+// here and pinned against the NumPy statement tests/pairs_los_statement.py.
+//   points: observer-centred float32, p = float32(column - origin) with the subtraction in the column's own dtype;
+//   per ordered pair (self pairs of an autocorrelation excluded): d = p_i - p_j and l = p_i + p_j componentwise in float32,
+//   then float64, left to right, no FMA: s2 = dx dx + dy dy + dz dz, l2 = lx lx + ly ly + lz lz, t = dx lx + dy ly + dz lz,
+//   pi2 = t t / l2; a pair with l2 == 0 has no line of sight and is not counted in modes 1 and 2;
+//   mode 0: bin s2.   mode 1: pi = sqrt(pi2) < (double)pimax, rp2 = max(s2 - pi2, 0) is binned, sub = int(pi / ((double)pimax
+//   / npibins)).   mode 2: bin s2, mu = s2 > 0 ? sqrt(pi2 / s2) : 0 < (double)mu_max, sub = int(mu * (nmubins / (double)mu_max));
+//   a sub >= the number of sub-bins drops the pair; float32 edges compared as e2[b] = (double)edge (double)edge,
+//   bin b: e2[b] <= q < e2[b + 1]; per (bin, sub-bin) npairs, wsum = sum w_i w_j (float64 product of float32 weights) and
+//   rsum = sum sqrt(q) of the q that chose the bin, float64.
+// float64 because rp^2 = s^2 - pi^2 cancels at light-cone distances: with |p| ~ 4000 and pi ~ 30 float32 leaves ~1e-4 on rp^2,
+// percent-level at rp = 0.1.
+// Grid: the bounding box of both sets (one min/max reduction, 24 bytes to the host), per-dimension cell counts 1 .. 128 with a
+// cell side >= 1.0001 reach; cell = min(int((v - lo) inv_cell), nc - 1) in float32; neighbour cells outside the grid are
+// skipped, nothing wraps.  The three float32 roundings of the cell index move a point by less than 3 2^-24 nc cells, so two
+// points whose indices differ by 2 or more are further apart than (1 - 5e-5) of a cell side > reach: the 27 cells suffice.
+struct OpenGrid {
+    int nc[3];
+    float lo[3], inv[3];
+};
+
+__device__ __forceinline__ int open_cell(float v, float lo, float inv, int nc) {
+    const int c = (int)((v - lo) * inv);
+    return c >= nc ? nc - 1 : (c < 0 ? 0 : c);   // c < 0: only a NaN coordinate, kept inside the arrays
+}
+
+template <bool COUNT, bool W>
+__global__ void cell_count_open(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                                const float *__restrict__ w, int64_t n, OpenGrid g, unsigned int *__restrict__ counts,
+                                unsigned int *__restrict__ cellid, unsigned int *__restrict__ idx, float4 *__restrict__ packed) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v[3] = {x[i], y[i], z[i]};
+        const int c = (open_cell(v[0], g.lo[0], g.inv[0], g.nc[0]) * g.nc[1] + open_cell(v[1], g.lo[1], g.inv[1], g.nc[1])) * g.nc[2] +
+                      open_cell(v[2], g.lo[2], g.inv[2], g.nc[2]);
+        cellid[i] = (unsigned int)c;
+        if (COUNT) atomicAdd(&counts[c], 1u);
+        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], W ? w[i] : 0.f);
+    }
+}
+
+// bounding box of a set as order-preserving keys (fkey): wave reduction, one pair of global atomics per workgroup and dimension
+__global__ void bbox_minmax(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, int64_t n,
+                            Frame *__restrict__ frame) {
+    unsigned int mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v[3] = {x[i], y[i], z[i]};
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            const unsigned int k = fkey(v[d]);
+            mn[d] = min(mn[d], k), mx[d] = max(mx[d], k);
+        }
+    }
+    __shared__ unsigned int s_mn[3], s_mx[3];
+    if (threadIdx.x < 3) s_mn[threadIdx.x] = 0xffffffffu, s_mx[threadIdx.x] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        unsigned int a = mn[d], b = mx[d];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) a = min(a, (unsigned int)__shfl_xor((int)a, off, 64)), b = max(b, (unsigned int)__shfl_xor((int)b, off, 64));
+        if ((threadIdx.x & 63) == 0 && a <= b) atomicMin(&s_mn[d], a), atomicMax(&s_mx[d], b);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_mn[threadIdx.x] <= s_mx[threadIdx.x])
+        atomicMin(&frame->mn[threadIdx.x], s_mn[threadIdx.x]), atomicMax(&frame->mx[threadIdx.x], s_mx[threadIdx.x]);
+}
+
+// observer-centred float32 columns: the subtraction in the column's own dtype, then one rounding (dst may be src)
+template <typename T>
+__global__ void los_centre(const T *src, T origin, float *dst, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)(src[i] - origin);
+}
+
+struct LosArgs {
+    int autocorr, nc[3], nbins, nsub;
+    // float32 pre-test: a candidate with s2f > pre_hi or s2f < pre_lo skips the float64 arithmetic (see the kernel)
+    float pre_lo, pre_hi;
+    double pimax, dpi, mu_max, inv_dmu;
+    const double *edges2;   // (nbins + 1) squared edges
+    const float *x1, *y1, *z1, *w1, *x2, *y2, *z2, *w2;   // cell order; w NULL: unit weights
+    const int64_t *start1, *start2;
+    unsigned long long *npairs;
+    double *wsum, *rsum;
+};
+
+// Modelled on pair_count_w: a persistent workgroup per non-empty cell of set 1, the in-range neighbour cells as ONE virtual
+// list of which every thread fetches one point per round into registers and walks the slice of its own cell (LDS broadcast
+// reads); LDS histogram (counts | WEIGHTED: sums of w w | RSUM: sums of sqrt(q)), flushed once per workgroup; full stencil for
+// the autocorrelation (ordered pairs, nothing doubled); MODE 0 keeps the last bin in registers like pair_count_w.
+//
+// Pre-test (cannot change membership).  s2f = dx dx + dy dy + dz dz in float32 from the SAME float32 d: three products and two
+// sums of non-negative terms, each rounded once, so s2f = s2 (1 + e) with |e| < 3.1 2^-24 < 2^-22 against the exact - and the
+// float64 (error 2^-52) - s2, as long as no product underflows.
+//   upper: a counted pair has s2 < R2 (1 + 2^-50), R2 = e2[nbins] (modes 0, 2) or e2[nbins] + pimax^2 (mode 1: rp2 < e2[nbins]
+//   and pi < pimax give s2 <= rp2 + pi2 up to two float64 roundings).  pre_hi = float32(R2 (1 + 2^-20)) rounded UP: s2f > pre_hi
+//   implies s2 > R2 (1 + 2^-20) (1 - 2^-22) > R2 (1 + 2^-50): never counted.
+//   lower (modes 0, 2 only; rp2 of mode 1 may be small whatever s2 is): a counted pair has s2 >= e2[0].  pre_lo =
+//   float32(e2[0] (1 - 2^-20)) rounded DOWN, and 0 (test off) when that is below 1e-30: above it an underflowing product
+//   (< 1.2e-38 lost) moves s2f by less than 2^-22 relative too.  s2f < pre_lo implies s2 < e2[0] (1 - 2^-20) (1 + 2^-22) < e2[0].
+// NaN fails both comparisons and falls to the float64 path, which counts nothing for it.
+template <int MODE, bool WEIGHTED, bool RSUM>
+__global__ __launch_bounds__(PB) void pair_count_los(LosArgs a, int ncell, unsigned long long *__restrict__ evaluated) {
+    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
+    __shared__ double e2[64];
+    __shared__ int64_t nb_j0[27];
+    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
+    extern __shared__ __align__(8) double hw[];   // [nh sums of w w] [nh sums of sqrt(q)] nh counts
+    const int tid = threadIdx.x;
+    const int nh = a.nbins * a.nsub;
+    double *hr = hw + (WEIGHTED ? nh : 0);
+    unsigned int *hc = reinterpret_cast<unsigned int *>(hr + (RSUM ? nh : 0));
+    for (int q = tid; q < nh; q += PB) {
+        hc[q] = 0u;
+        if (WEIGHTED) hw[q] = 0.0;
+        if (RSUM) hr[q] = 0.0;
+    }
+    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
+    __syncthreads();
+    const double lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
+    const int ncx = a.nc[0], ncy = a.nc[1], ncz = a.nc[2];
+    double top_w = 0.0, top_r = 0.0;         // MODE 0: the last bin, per lane
+    unsigned long long top_n = 0, n_eval = 0;
+    for (int c1 = blockIdx.x; c1 < ncell; c1 += gridDim.x) {
+        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
+        if (cbeg == cend) continue;
+        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
+        if (tid < 64) {
+            int len = 0;
+            int64_t j0 = 0;
+            if (tid < 27) {
+                const int cz = c1 % ncz, cy = (c1 / ncz) % ncy, cx = c1 / (ncz * ncy);
+                const int nx = cx + tid / 9 - 1, ny = cy + (tid / 3) % 3 - 1, nz = cz + tid % 3 - 1;
+                if (nx >= 0 && nx < ncx && ny >= 0 && ny < ncy && nz >= 0 && nz < ncz) {   // open grid: nothing wraps
+                    const int c2 = (nx * ncy + ny) * ncz + nz;
+                    j0 = a.start2[c2];
+                    len = (int)(a.start2[c2 + 1] - j0);
+                }
+            }
+            int incl = len;
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) {
+                const int v = __shfl_up(incl, d, 64);
+                if (tid >= d) incl += v;
+            }
+            if (tid < 27) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
+            if (tid == 26) nb_pre[27] = incl;
+        }
+        __syncthreads();
+        const int M = nb_pre[27];
+        for (int64_t i0 = cbeg; i0 < cend; i0 += PB) {
+            const int ni = (int)min((int64_t)PB, cend - i0);
+            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
+            if (tid < ni) {
+                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
+                iw[tid] = WEIGHTED && a.w1 ? a.w1[i0 + tid] : 1.0f;
+            }
+            __syncthreads();
+            for (int base = 0; base < M; base += PB) {
+                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
+                const int v = base + tid;
+                if (v >= M) continue;
+                int sg = 0;
+                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[27]: ends at a non-empty cell
+                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
+                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
+                const double wj = WEIGHTED && a.w2 ? (double)a.w2[jj] : 1.0;
+                for (int i = 0; i < ni; i++) {
+                    const float dxf = ix[i] - xj, dyf = iy[i] - yj, dzf = iz[i] - zj;
+                    const float s2f = dxf * dxf + dyf * dyf + dzf * dzf;
+                    if (s2f > a.pre_hi || s2f < a.pre_lo) continue;
+                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
+                    const double dx = (double)dxf, dy = (double)dyf, dz = (double)dzf;
+                    const double s2 = dx * dx + dy * dy + dz * dz;
+                    double q = s2, pi2 = 0.0;
+                    int sub = 0;
+                    if (MODE == 0) {
+                        if (!(q >= lo2 && q < hi2)) continue;
+                    } else {
+                        if (MODE == 2 && !(q >= lo2 && q < hi2)) continue;
+                        const double lx = (double)(ix[i] + xj), ly = (double)(iy[i] + yj), lz = (double)(iz[i] + zj);
+                        const double l2 = lx * lx + ly * ly + lz * lz;
+                        if (l2 == 0.0) continue;                // no line of sight
+                        const double t = dx * lx + dy * ly + dz * lz;
+                        pi2 = t * t / l2;
+                        if (MODE == 1) {
+                            const double pi = sqrt(pi2);
+                            if (!(pi < a.pimax)) continue;
+                            const double rp2 = s2 - pi2;
+                            q = rp2 > 0.0 ? rp2 : 0.0;
+                            if (!(q >= lo2 && q < hi2)) continue;
+                            sub = (int)(pi / a.dpi);
+                        } else {
+                            const double mu = s2 > 0.0 ? sqrt(pi2 / s2) : 0.0;
+                            if (!(mu < a.mu_max)) continue;
+                            sub = (int)(mu * a.inv_dmu);
+                        }
+                        if (sub >= a.nsub) continue;
+                    }
+                    const double ww = WEIGHTED ? (double)iw[i] * wj : 0.0;
+                    if (MODE == 0 && q >= top2) {
+                        top_n++;
+                        if (WEIGHTED) top_w += ww;
+                        if (RSUM) top_r += sqrt(q);
+                        continue;
+                    }
+                    int b = a.nbins - 1;
+                    while (q < e2[b]) b--;
+                    const int h = b * a.nsub + sub;
+                    atomicAdd(&hc[h], 1u);
+                    if (WEIGHTED) atomicAdd(&hw[h], ww);
+                    if (RSUM) atomicAdd(&hr[h], sqrt(q));
+                }
+            }
+        }
+    }
+    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
+    if (MODE == 0 && top_n) {
+        // a lane's share of a workgroup's last-bin pairs stays far below 2^32
+        const int h = a.nbins - 1;
+        atomicAdd(&hc[h], (unsigned int)top_n);
+        if (WEIGHTED) atomicAdd(&hw[h], top_w);
+        if (RSUM) atomicAdd(&hr[h], top_r);
+    }
+    __syncthreads();
+    for (int q = tid; q < nh; q += PB)
+        if (hc[q]) {
+            atomicAdd(&a.npairs[q], (unsigned long long)hc[q]);
+            if (WEIGHTED) atomicAdd(&a.wsum[q], hw[q]);
+            if (RSUM) atomicAdd(&a.rsum[q], hr[q]);
+        }
+}
+
 struct SortedSet {
     DevBuf raw, sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wraw, wsorted;
     float *sx, *sy, *sz, *sw;   // sw: the weights in cell order (weighted counts with weights for this set), else NULL
@@ -960,7 +1195,7 @@ __global__ void cast_f64_f32(const double *__restrict__ src, float *__restrict__
 // where = 0: host float32 arrays; 1: device float32; 2: device float64.  hw: float32 weights of the points (host memory when
 // where = 0, else device memory) or NULL; they are sorted along with the points into s.sw
 int sort_into_cells(const void *hx, const void *hy, const void *hz, const float *hw, int where, int64_t n, const CellGrid &g,
-                    SortedSet &s, DevBuf &scratch, int *d_outside, Frame *d_frame) {
+                    SortedSet &s, DevBuf &scratch, int *d_outside, Frame *d_frame, const OpenGrid *og = nullptr) {
     const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
     const size_t n1 = (size_t)std::max<int64_t>(n, 1);
     s.n = n;
@@ -1004,7 +1239,13 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, const float 
         ABACUS_TRY(s.idx.reserve(n1 * 4));
         ABACUS_TRY(s.idx2.reserve(n1 * 4));
         ABACUS_TRY(s.packed.reserve(n1 * 16));
-        if (hw)
+        if (og && hw)
+            ABACUS_LAUNCH("pair_cell_count", (cell_count_open<false, true>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, *og, (unsigned int *)nullptr,
+                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>());
+        else if (og)
+            ABACUS_LAUNCH("pair_cell_count", (cell_count_open<false, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, *og, (unsigned int *)nullptr,
+                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>());
+        else if (hw)
             ABACUS_LAUNCH("pair_cell_count", (cell_count<false, true>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, g, (unsigned int *)nullptr,
                           s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>(), d_outside, d_frame);
         else
@@ -1032,7 +1273,10 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, const float 
         return 0;
     }
     HIP_TRY(hipMemsetAsync(s.counts.p, 0, (size_t)(ncell + 1) * 4, stream()));
-    if (n > 0)
+    if (n > 0 && og)
+        ABACUS_LAUNCH("pair_cell_count", (cell_count_open<true, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, (const float *)nullptr, n, *og,
+                      s.counts.as<unsigned int>(), s.cellid.as<unsigned int>(), (unsigned int *)nullptr, (float4 *)nullptr);
+    else if (n > 0)
         ABACUS_LAUNCH("pair_cell_count", (cell_count<true, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, (const float *)nullptr, n, g,
                       s.counts.as<unsigned int>(), s.cellid.as<unsigned int>(), (unsigned int *)nullptr, (float4 *)nullptr, d_outside,
                       d_frame);
@@ -1313,5 +1557,233 @@ extern "C" int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *
     if (ncell_xy) *ncell_xy = g_last_cells[0];
     if (ncell_z) *ncell_z = g_last_cells[1];
     if (stencil_R) *stencil_R = g_last_cells[2];
+    return 0;
+}
+
+// ---------------------------------------------------------------- light cones: abacus_paircount_los ----
+static int g_los_cells[3] = {0, 0, 0};
+
+static float funkey_host(unsigned int k) {
+    const unsigned int u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+
+template <int MODE, bool W, bool R>
+static int los_launch(const LosArgs &a, int64_t ncell, size_t hist_bytes, unsigned long long *d_eval) {
+    int dev = 0, ncu = 256, per_cu = 2;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)pair_count_los<MODE, W, R>, PB, hist_bytes));
+    const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * std::max(per_cu, 1)));
+    ABACUS_LAUNCH("pair_count_los", (pair_count_los<MODE, W, R>), grid, dim3(PB), hist_bytes, a, (int)ncell, d_eval);
+    return 0;
+}
+
+// where = 0: host float32 arrays (and host weights); 1: device float32; 2: device float64 (device weights)
+static int paircount_los_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                              const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int where,
+                              const double *origin, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                              int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    // every argument is checked before the device is touched
+    if (mode < 0 || mode > 2) return fail("%s: unknown mode %d", who, mode);
+    if (!x1 || !y1 || !z1 || !origin || !bins || !npairs) return fail("%s: null argument", who);
+    if (nbins < 1) return fail("%s: nbins must be at least 1", who);
+    const int autocorr = x2 == nullptr;
+    if (!autocorr && (!y2 || !z2)) return fail("%s: null argument (y2 / z2)", who);
+    if (autocorr && w2) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
+    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
+    if (!(bins[0] >= 0.f)) return fail("%s: bin edges must not be negative", who);
+    for (int b = 0; b < nbins; b++)
+        if (!(bins[b + 1] > bins[b])) return fail("%s: bin edges must increase", who);
+    if (mode == 1 && (!(pimax > 0.f) || npibins < 1)) return fail("%s: pimax must be positive, with at least one pi bin", who);
+    if (mode == 2 && (!(mu_max > 0.f) || nmubins < 1)) return fail("%s: mu_max must be positive, with at least one mu bin", who);
+    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
+    if (nsub > W_MAX_HIST) return fail("%s: %d pi / mu bins exceed the LDS histogram", who, nsub);
+    for (int d = 0; d < 3; d++)
+        if (!std::isfinite(origin[d])) return fail("%s: origin must be finite", who);
+    ABACUS_ENTER();
+    const bool weighted = wsum != nullptr, rs = weighted && rsum != nullptr;   // wsum == NULL: integer counts only
+    const size_t nall = (size_t)nbins * nsub;
+    memset(npairs, 0, nall * sizeof(uint64_t));
+    if (wsum) memset(wsum, 0, nall * sizeof(double));
+    if (rs) memset(rsum, 0, nall * sizeof(double));
+    g_last_evaluated = 0;
+    g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
+    g_los_cells[0] = g_los_cells[1] = g_los_cells[2] = 0;
+    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
+
+    // observer-centred float32 columns of both sets in HBM
+    static SortedSet S1, S2;
+    static DevBuf cols[2], wts[2], scratch, d_edges, d_out, d_flag;
+    const float *px[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}, *pw[2] = {nullptr, nullptr};
+    const void *src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
+    const float *srcw[2] = {weighted ? w1 : nullptr, weighted ? w2 : nullptr};
+    const int64_t ns[2] = {n1, autocorr ? 0 : n2};
+    const bool shifted = origin[0] != 0.0 || origin[1] != 0.0 || origin[2] != 0.0;
+    for (int k = 0; k < (autocorr ? 1 : 2); k++) {
+        const int64_t n = ns[k];
+        const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 2048);
+        if (where == 1 && !shifted) {   // caller's device arrays, read in place
+            for (int d = 0; d < 3; d++) px[k][d] = (const float *)src[k][d];
+        } else {
+            ABACUS_TRY(cols[k].reserve(3 * (size_t)n * 4));
+            for (int d = 0; d < 3; d++) {
+                float *dst = cols[k].as<float>() + (size_t)d * n;
+                px[k][d] = dst;
+                if (where == 2) {
+                    ABACUS_LAUNCH("pair_los_centre", los_centre<double>, dim3(nblk), dim3(256), 0, (const double *)src[k][d], origin[d], dst, n);
+                    continue;
+                }
+                const float *from = (const float *)src[k][d];
+                if (where == 0) {
+                    HIP_TRY(hipMemcpyAsync(dst, from, (size_t)n * 4, hipMemcpyHostToDevice, stream()));
+                    from = dst;
+                }
+                if (shifted) ABACUS_LAUNCH("pair_los_centre", los_centre<float>, dim3(nblk), dim3(256), 0, from, (float)origin[d], dst, n);
+            }
+        }
+        pw[k] = srcw[k];
+        if (srcw[k] && where == 0) {
+            ABACUS_TRY(wts[k].reserve((size_t)n * 4));
+            HIP_TRY(hipMemcpyAsync(wts[k].p, srcw[k], (size_t)n * 4, hipMemcpyHostToDevice, stream()));
+            pw[k] = wts[k].as<float>();
+        }
+    }
+    // bounding box of both sets: one reduction, 24 bytes to the host
+    ABACUS_TRY(d_flag.reserve(64));
+    Frame *d_frame = d_flag.as<Frame>();
+    unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_flag.as<char>() + 32);
+    Frame fr;
+    for (int d = 0; d < 3; d++) fr.mn[d] = 0xffffffffu, fr.mx[d] = 0u;
+    HIP_TRY(hipMemsetAsync(d_flag.p, 0, 64, stream()));
+    HIP_TRY(hipMemcpyAsync(d_frame, &fr, sizeof fr, hipMemcpyHostToDevice, stream()));
+    for (int k = 0; k < (autocorr ? 1 : 2); k++)
+        ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
+                      px[k][0], px[k][1], px[k][2], ns[k], d_frame);
+    HIP_TRY(hipMemcpyAsync(&fr, d_frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    double lo[3], extent[3];
+    for (int d = 0; d < 3; d++) {
+        lo[d] = (double)funkey_host(fr.mn[d]);
+        extent[d] = (double)funkey_host(fr.mx[d]) - lo[d];
+        if (!(extent[d] >= 0.0) || !std::isfinite(extent[d]) || !std::isfinite(lo[d])) return fail("%s: coordinates are not finite", who);
+    }
+
+    // One launch bins into at most 63 separation bins and W_MAX_HIST LDS entries; more are counted in runs of consecutive
+    // separation bins, each on a grid of its own, smaller reach (a pair ON an edge shared by two runs belongs to the upper bin
+    // in both).  The columns above and the bounding box serve every run.
+    const int run = std::min(63, W_MAX_HIST / nsub);
+    unsigned long long evaluated = 0;
+    for (int b0 = 0; b0 < nbins; b0 += run) {
+        const int nb = std::min(run, nbins - b0);
+        const float *edges = bins + b0;
+        const size_t ntot = (size_t)nb * nsub, o = (size_t)b0 * nsub;
+        std::vector<double> e2(nb + 1);
+        for (int b = 0; b <= nb; b++) e2[b] = (double)edges[b] * (double)edges[b];
+        const double reach2 = mode == 1 ? e2[nb] + (double)pimax * (double)pimax : e2[nb];
+        const double reach = std::nextafter(std::sqrt(reach2), HUGE_VAL);   // rounded up
+        OpenGrid og;
+        CellGrid g;
+        for (int d = 0; d < 3; d++) {
+            const double fit = std::floor(extent[d] / (reach * 1.0001));    // cell side >= 1.0001 reach (see OpenGrid)
+            og.nc[d] = (int)std::min(128.0, std::max(1.0, fit));
+            og.lo[d] = (float)lo[d];                                         // exact: a float32 coordinate
+            og.inv[d] = extent[d] > 0.0 ? (float)((double)og.nc[d] / extent[d]) : 0.f;
+        }
+        g.ncx = og.nc[0], g.ncy = og.nc[1], g.ncz = og.nc[2];
+        g.box = g.inv_box = 0.f;   // (the periodic members are not read on the open path)
+        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
+        ABACUS_TRY(sort_into_cells(px[0][0], px[0][1], px[0][2], pw[0], 1, n1, g, S1, scratch, nullptr, nullptr, &og));
+        if (!autocorr) ABACUS_TRY(sort_into_cells(px[1][0], px[1][1], px[1][2], pw[1], 1, n2, g, S2, scratch, nullptr, nullptr, &og));
+        SortedSet &T = autocorr ? S1 : S2;
+
+        ABACUS_TRY(d_edges.reserve((size_t)(nb + 1) * 8));
+        ABACUS_TRY(d_out.reserve(3 * ntot * 8));
+        HIP_TRY(hipMemcpyAsync(d_edges.p, e2.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, stream()));
+        HIP_TRY(hipMemsetAsync(d_out.p, 0, 3 * ntot * 8, stream()));
+        HIP_TRY(hipMemsetAsync(d_eval, 0, 8, stream()));
+        LosArgs a;
+        a.autocorr = autocorr;
+        for (int d = 0; d < 3; d++) a.nc[d] = og.nc[d];
+        a.nbins = nb, a.nsub = nsub;
+        // the pre-test's thresholds (derivation at the kernel): rounded away from the accepted range
+        const double hi_d = reach2 * (1.0 + 0x1p-20), lo_d = e2[0] * (1.0 - 0x1p-20);
+        float hi_f = (float)hi_d, lo_f = (float)lo_d;
+        if ((double)hi_f < hi_d) hi_f = std::nextafterf(hi_f, HUGE_VALF);
+        if ((double)lo_f > lo_d) lo_f = std::nextafterf(lo_f, 0.f);
+        a.pre_hi = hi_f;
+        a.pre_lo = mode != 1 && lo_d >= 1e-30 ? lo_f : 0.f;
+        a.pimax = (double)pimax;
+        a.dpi = npibins > 0 ? (double)pimax / npibins : 1.0;
+        a.mu_max = (double)mu_max;
+        a.inv_dmu = nmubins > 0 ? nmubins / (double)mu_max : 1.0;
+        a.edges2 = d_edges.as<double>();
+        a.x1 = S1.sx, a.y1 = S1.sy, a.z1 = S1.sz, a.w1 = S1.sw;
+        a.x2 = T.sx, a.y2 = T.sy, a.z2 = T.sz, a.w2 = T.sw;
+        a.start1 = S1.start.as<int64_t>(), a.start2 = T.start.as<int64_t>();
+        a.npairs = d_out.as<unsigned long long>();
+        a.wsum = d_out.as<double>() + ntot, a.rsum = a.wsum + ntot;
+        const size_t hist_bytes = ntot * (4 + (weighted ? 8 : 0) + (rs ? 8 : 0));
+#define LOS_RUN(M)                                                                           \
+    do {                                                                                     \
+        if (rs) ABACUS_TRY((los_launch<M, true, true>(a, ncell, hist_bytes, d_eval)));       \
+        else if (weighted) ABACUS_TRY((los_launch<M, true, false>(a, ncell, hist_bytes, d_eval))); \
+        else ABACUS_TRY((los_launch<M, false, false>(a, ncell, hist_bytes, d_eval)));        \
+    } while (0)
+        if (mode == 0) LOS_RUN(0);
+        else if (mode == 1) LOS_RUN(1);
+        else LOS_RUN(2);
+#undef LOS_RUN
+        unsigned long long ev = 0;
+        HIP_TRY(hipMemcpyAsync(npairs + o, a.npairs, ntot * 8, hipMemcpyDeviceToHost, stream()));
+        if (weighted) HIP_TRY(hipMemcpyAsync(wsum + o, a.wsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
+        if (rs) HIP_TRY(hipMemcpyAsync(rsum + o, a.rsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipMemcpyAsync(&ev, d_eval, 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        evaluated += ev;
+        g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = 0;
+        for (int d = 0; d < 3; d++) g_los_cells[d] = og.nc[d];
+    }
+    g_last_evaluated = evaluated;
+    return 0;
+}
+
+extern "C" int abacus_paircount_los(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
+                                    const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,
+                                    const double *origin, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                                    int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    return paircount_los_impl("abacus_paircount_los", mode, x1, y1, z1, w1, n1, x2, y2, z2, w2, n2, 0, origin, bins, nbins, pimax,
+                              npibins, mu_max, nmubins, npairs, wsum, rsum);
+}
+
+extern "C" int abacus_paircount_los_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                                        const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int pos_dtype,
+                                        const double *origin, const float *bins, int nbins, float pimax, int npibins,
+                                        float mu_max, int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_los_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
+    return paircount_los_impl("abacus_paircount_los_dev", mode, x1, y1, z1, w1, n1, x2, y2, z2, w2, n2, pos_dtype == ABACUS_F32 ? 1 : 2,
+                              origin, bins, nbins, pimax, npibins, mu_max, nmubins, npairs, wsum, rsum);
+}
+
+extern "C" int abacus_paircount_los_grid(int *ncell) {
+    ABACUS_ENTER();
+    if (!ncell) return fail("abacus_paircount_los_grid: null argument");
+    for (int d = 0; d < 3; d++) ncell[d] = g_los_cells[d];
+    return 0;
+}
+
+// a device column, observer-centred: dst = float32(src - origin), the subtraction in the column's dtype (the estimators of
+// analysis/tpcf_corrfunc.py centre a sample once and count it against several others)
+extern "C" int abacus_paircount_los_centre(const void *src, int pos_dtype, int64_t n, double origin, float *dst) {
+    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_los_centre: pos_dtype must be ABACUS_F32 or ABACUS_F64");
+    if (n < 0 || (n > 0 && (!src || !dst)) || !std::isfinite(origin)) return fail("abacus_paircount_los_centre: bad argument");
+    ABACUS_ENTER();
+    if (n == 0) return 0;
+    const dim3 grid((unsigned int)std::min<int64_t>(ceil_div(n, 256), 2048));
+    if (pos_dtype == ABACUS_F64) ABACUS_LAUNCH("pair_los_centre", los_centre<double>, grid, dim3(256), 0, (const double *)src, origin, dst, n);
+    else ABACUS_LAUNCH("pair_los_centre", los_centre<float>, grid, dim3(256), 0, (const float *)src, (float)origin, dst, n);
+    HIP_TRY(hipStreamSynchronize(stream()));
     return 0;
 }

@@ -23,7 +23,8 @@ from pathlib import Path
 import numpy as np
 
 from ..analysis.power_spectrum import calc_power
-from ..analysis.tpcf_corrfunc import calc_multipole_fast, calc_wp_fast, calc_xirppi_fast
+from ..analysis.tpcf_corrfunc import (calc_multipole_fast, calc_multipole_lc, calc_wp_fast, calc_wp_lc, calc_xirppi_fast,
+                                      calc_xirppi_lc)
 from .GRAND_HOD import StagedCatalog, gen_gal_cat
 
 _PRIMARY_Z = [3.0, 2.5, 2.0, 1.7, 1.4, 1.1, 0.8, 0.5, 0.4, 0.3, 0.2, 0.1, 0.0]
@@ -559,21 +560,45 @@ class AbacusHOD:
                     clustering[tr2 + '_' + tr1] = clustering[tr1 + '_' + tr2]
         return clustering
 
-    def compute_xirppi(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8, weights=None):
-        """xi(rp, pi) for every tracer pair (:1221-1279); weights: see `_pairs`"""
+    def _lc_origin(self):
+        """the observer of this object's light cone, for the randoms-based estimators"""
+        origin = self.params.get('origin') if getattr(self, 'halo_lc', False) else None
+        if origin is None:
+            raise ValueError('randoms= needs a light-cone catalogue: this AbacusHOD carries no origin')
+        return np.asarray(origin, dtype=np.float64).reshape(-1)[:3]
+
+    def compute_xirppi(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8, weights=None, randoms=None):
+        """xi(rp, pi) for every tracer pair (:1221-1279); weights: see `_pairs`.  randoms: None (the periodic box), or an
+        `LCRandoms` - the Landy-Szalay estimator with the pairwise line of sight seen from the light cone's origin"""
+        if randoms is not None:
+            origin = self._lc_origin()
+            return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2, **w: calc_xirppi_lc(
+                x1, y1, z1, rpbins, pimax, pi_bin_size, randoms, Nthread, x2=x2, y2=y2, z2=z2, origin=origin, **w), weights)
         return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2, **w: calc_xirppi_fast(
             x1, y1, z1, rpbins, pimax, pi_bin_size, self.lbox, Nthread, x2=x2, y2=y2, z2=z2, **w), weights)
 
-    def compute_wp(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8, weights=None):
-        """wp(rp) for every tracer pair (:1826-1885); weights: see `_pairs`"""
+    def compute_wp(self, mock_dict, rpbins, pimax, pi_bin_size, Nthread=8, weights=None, randoms=None):
+        """wp(rp) for every tracer pair (:1826-1885); weights: see `_pairs`; randoms: see `compute_xirppi`"""
+        if randoms is not None:
+            origin = self._lc_origin()
+            return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2, **w: calc_wp_lc(
+                x1, y1, z1, rpbins, pimax, randoms, Nthread, x2=x2, y2=y2, z2=z2, origin=origin, **w), weights)
         return self._pairs(mock_dict, lambda x1, y1, z1, x2, y2, z2, **w: calc_wp_fast(
             x1, y1, z1, rpbins, pimax, self.lbox, Nthread, x2=x2, y2=y2, z2=z2, **w), weights)
 
-    def compute_multipole(self, mock_dict, rpbins, pimax, sbins, nbins_mu, orders=[0, 2], Nthread=8, weights=None):
+    def compute_multipole(self, mock_dict, rpbins, pimax, sbins, nbins_mu, orders=[0, 2], Nthread=8, weights=None,
+                          randoms=None):
         """wp concatenated with xi_l(s) (:1281-1336; like the reference, cross pairs use `rpbins` as s bins, :1313);
-        weights: see `_pairs`"""
+        weights: see `_pairs`; randoms: see `compute_xirppi`"""
+        origin = None if randoms is None else self._lc_origin()
+
         def fn(x1, y1, z1, x2, y2, z2, **w):
             sb = sbins if x2 is None else rpbins
+            if randoms is not None:
+                new_multi = calc_multipole_lc(x1, y1, z1, sb, randoms, Nthread, nbins_mu=nbins_mu, orders=orders, x2=x2, y2=y2,
+                                              z2=z2, origin=origin, **w)
+                new_wp = calc_wp_lc(x1, y1, z1, rpbins, pimax, randoms, Nthread, x2=x2, y2=y2, z2=z2, origin=origin, **w)
+                return np.concatenate((new_wp, new_multi))
             new_multi = calc_multipole_fast(x1, y1, z1, sb, self.lbox, Nthread, nbins_mu=nbins_mu, orders=orders,
                                             x2=x2, y2=y2, z2=z2, **w)
             new_wp = calc_wp_fast(x1, y1, z1, rpbins, pimax, self.lbox, Nthread, x2=x2, y2=y2, z2=z2, **w)

@@ -523,6 +523,38 @@ int abacus_paircount_weighted_dev(int mode, const void *x1, const void *y1, cons
  * older-generation kernel ran), cells per dimension in xy / z, stencil half-width in cells (1 or 2; 0: older kernel) */
 int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z, int *stencil_R);
 
+/*
+ * Light-cone pair counts: a line of sight that belongs to the PAIR, on an open (non-periodic) grid - what
+ * Corrfunc.mocks.DDrppi_mocks / DDsmu_mocks compute from Cartesian columns.  No Corrfunc run stands behind this: the
+ * conventions below are the contract, pinned against the NumPy statement tests/pairs_los_statement.py.
+ *   points   p = float32(column - origin[d]), the subtraction in the column's own dtype (float64 columns of the _dev form
+ *            subtract in float64, float32 columns in float32); origin = (0, 0, 0) leaves float32 columns untouched;
+ *   pair     d = p_i - p_j and l = p_i + p_j in float32, then float64, left to right, no FMA: s2 = d.d, l2 = l.l, t = d.l,
+ *            pi2 = t t / l2; a pair with l2 == 0 is not counted in modes 1 and 2; self pairs of an autocorrelation are excluded;
+ *   mode 0   bin s2.   mode 1: pi = sqrt(pi2) < (double)pimax, bin rp2 = max(s2 - pi2, 0), sub = int(pi / ((double)pimax / npibins)).
+ *   mode 2   bin s2, mu = s2 > 0 ? sqrt(pi2 / s2) : 0 < (double)mu_max, sub = int(mu * (nmubins / (double)mu_max));
+ *   bins     float32 edges >= 0, compared as (double)edge * (double)edge: bin b holds e2[b] <= q < e2[b + 1];
+ *   sums     per (bin, sub-bin) npairs (ordered pairs for an autocorrelation), wsum = sum w_i w_j (float32 weights, product and
+ *            sum in float64), rsum = sum sqrt(q) of the q that chose the bin (s | rp | s), float64.  The float64 atomics leave
+ *            |error| <= n * 2^-52 * sum|term| per bin.
+ * w1 / w2 NULL: unit weights; x2 == NULL: autocorrelation (w2 must be NULL).  wsum == NULL: integer counts only (rsum is then
+ * ignored); rsum == NULL: not computed.  Arguments are validated before the device is touched.
+ * _dev: coordinate columns in HBM (pos_dtype ABACUS_F32 / ABACUS_F64), w1 / w2 float32 DEVICE pointers.
+ * abacus_paircount_stats reports the candidate pairs (summed over the runs of a call with more than 63 separation bins) and
+ * the x / z cell counts of such a call (stencil_R = 0); abacus_paircount_los_grid the cell counts of all three dimensions.
+ */
+int abacus_paircount_los(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
+                         const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2, const double *origin,
+                         const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs,
+                         double *wsum, double *rsum);
+int abacus_paircount_los_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                             const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int pos_dtype,
+                             const double *origin, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                             int nmubins, uint64_t *npairs, double *wsum, double *rsum);
+int abacus_paircount_los_grid(int *ncell /* [3] */);
+/* one device column, observer-centred: dst[i] = float32(src[i] - origin), subtracted in the column's dtype (pos_dtype) */
+int abacus_paircount_los_centre(const void *src, int pos_dtype, int64_t n, double origin, float *dst);
+
 /* ---------------------------------------------------------------- staging (the step in front of the HOD) ---- */
 /*
  * Data-parallel pieces of AbacusHOD.staging() (hod/abacus_hod.py:253-704); host arrays in and out, staging runs once.
