@@ -27,59 +27,41 @@ def _f4(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
 
 
-def _paircount(mode, X1, Y1, Z1, boxsize, bins, X2=None, Y2=None, Z2=None, pimax=0.0, npibins=0, mu_max=1.0,
-               nmubins=0):
-    """host arrays (cast to float32 like the reference, tpcf_corrfunc.py:134-139) or - all of them - `_lib.DeviceArray`
-    columns of float32 / float64 already in HBM (the HOD catalogue: `abacus_paircount_dev`, no PCIe round trip)"""
-    bins = _f4(bins)
+def _counter(entry, mode, bins, cols, weights, geom, pimax, npibins, mu_max, nmubins, want_sums=True, want_rsum=True,
+             host_prep=None):
+    """What the three counters below share.  `entry`: the C function `abacus_<entry>` (host columns) or `abacus_<entry>_dev`
+    (resident ones); `bins`: float32 edges; `cols` = (X1, Y1, Z1, X2, Y2, Z2); `weights` = (W1, W2), or None for an entry
+    without weight and sum arguments; `geom`: the ctypes arguments between the columns and the bins (box size | origin).
+    Columns are host arrays (cast to float32) or - all of them - DeviceArray columns of one dtype; a host weight array next
+    to resident coordinates is uploaded (float32), resident weights next to host coordinates are not accepted.
+    `host_prep(cols, geom)` -> (cols, geom), if given, has the last word on host columns, after every check.
+    Returns (npairs, wsum, rsum); the sums are None when not asked for."""
     nb = len(bins) - 1
     nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
     out = np.zeros(nb * nsub, dtype=np.uint64)
-    cols = [c for c in (X1, Y1, Z1, X2, Y2, Z2) if c is not None]
-    if any(isinstance(c, _lib.DeviceArray) for c in cols):
-        if not all(isinstance(c, _lib.DeviceArray) and c.dtype == cols[0].dtype for c in cols):
-            raise TypeError('device-resident coordinates: every column must be a DeviceArray of one dtype')
-        dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[cols[0].dtype]
-        dp = lambda c: None if c is None else c.ptr     # noqa: E731
-        check(_lib.lib().abacus_paircount_dev(
-            int(mode), dp(X1), dp(Y1), dp(Z1), C.c_int64(X1.shape[0]), dp(X2), dp(Y2), dp(Z2),
-            C.c_int64(0 if X2 is None else X2.shape[0]), dt, C.c_float(boxsize), ptr(bins), int(nb), C.c_float(pimax),
-            int(npibins), C.c_float(mu_max), int(nmubins), ptr(out)))
-        return out
-    X1, Y1, Z1, X2, Y2, Z2 = map(_f4, (X1, Y1, Z1, X2, Y2, Z2))
-    check(_lib.lib().abacus_paircount(
-        int(mode), ptr(X1), ptr(Y1), ptr(Z1), C.c_int64(len(X1)), ptr(X2), ptr(Y2), ptr(Z2),
-        C.c_int64(0 if X2 is None else len(X2)), C.c_float(boxsize), ptr(bins), int(nb), C.c_float(pimax),
-        int(npibins), C.c_float(mu_max), int(nmubins), ptr(out)))
-    return out
-
-
-def _paircount_weighted(mode, X1, Y1, Z1, boxsize, bins, X2=None, Y2=None, Z2=None, W1=None, W2=None, pimax=0.0,
-                        npibins=0, mu_max=1.0, nmubins=0, want_rsum=True):
-    """`_paircount` with per-point float32 weights (None: unit weights): (npairs, wsum, rsum) per (bin, sub-bin) with
-    wsum = sum of w_i * w_j and rsum = sum of the pair separation (r | rp | s), both accumulated in float64 on the device
-    (`abacus_paircount_weighted[_dev]`); rsum is None when `want_rsum` is false.  A host weight array next to resident
-    coordinates is uploaded (float32), resident weights next to host coordinates are not accepted."""
-    bins = _f4(bins)
-    nb = len(bins) - 1
-    nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
-    out = np.zeros(nb * nsub, dtype=np.uint64)
-    wsum = np.zeros(nb * nsub, dtype=np.float64)
-    rsum = np.zeros(nb * nsub, dtype=np.float64) if want_rsum else None
+    wsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums else None
+    rsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums and want_rsum else None
+    X1, X2 = cols[0], cols[3]
+    W1, W2 = weights or (None, None)
     if X2 is None and W2 is not None:
         raise ValueError('weights2 given for an autocorrelation')
     n1, n2 = len(X1), (0 if X2 is None else len(X2))
     for name, w, n in (('weights1', W1, n1), ('weights2', W2, n2)):
         if w is not None and (len(w.shape) != 1 or w.shape[0] != n):
             raise ValueError(f'{name} has shape {tuple(w.shape)}, expected ({n},)')
-    cols = [c for c in (X1, Y1, Z1, X2, Y2, Z2) if c is not None]
-    tail = (C.c_float(boxsize), ptr(bins), int(nb), C.c_float(pimax), int(npibins), C.c_float(mu_max), int(nmubins), ptr(out),
-            ptr(wsum), ptr(rsum))
-    if any(isinstance(c, _lib.DeviceArray) for c in cols):
-        if not all(isinstance(c, _lib.DeviceArray) and c.dtype == cols[0].dtype for c in cols):
+    tail = (ptr(bins), int(nb), C.c_float(pimax), int(npibins), C.c_float(mu_max), int(nmubins), ptr(out))
+    if weights is not None:
+        tail += (ptr(wsum), ptr(rsum))
+
+    def call(fn, p, cols, w1, w2, geom, *dt):
+        ws = ((p(w1),), (p(w2),)) if weights is not None else ((), ())
+        check(fn(int(mode), *map(p, cols[:3]), *ws[0], C.c_int64(n1), *map(p, cols[3:]), *ws[1], C.c_int64(n2), *dt, *geom, *tail))
+        return out, wsum, rsum
+    given = [c for c in cols if c is not None]
+    if any(isinstance(c, _lib.DeviceArray) for c in given):
+        if not all(isinstance(c, _lib.DeviceArray) and c.dtype == given[0].dtype for c in given):
             raise TypeError('device-resident coordinates: every column must be a DeviceArray of one dtype')
-        dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[cols[0].dtype]
-        dp = lambda c: None if c is None else c.ptr     # noqa: E731
+        dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[given[0].dtype]
         own = []
 
         def dev_w(w):
@@ -92,21 +74,33 @@ def _paircount_weighted(mode, X1, Y1, Z1, boxsize, bins, X2=None, Y2=None, Z2=No
             own.append(_lib.DeviceArray(_f4(w)))
             return own[-1]
         try:
-            d1, d2 = dev_w(W1), dev_w(W2)
-            check(_lib.lib().abacus_paircount_weighted_dev(
-                int(mode), dp(X1), dp(Y1), dp(Z1), dp(d1), C.c_int64(n1), dp(X2), dp(Y2), dp(Z2), dp(d2), C.c_int64(n2), dt,
-                *tail))
+            return call(getattr(_lib.lib(), f'abacus_{entry}_dev'), lambda c: None if c is None else c.ptr, cols, dev_w(W1),
+                        dev_w(W2), geom, dt)
         finally:
             for a in own:
                 a.free()
-        return out, wsum, rsum
     if isinstance(W1, _lib.DeviceArray) or isinstance(W2, _lib.DeviceArray):
         raise TypeError('device-resident weights need device-resident coordinates')
-    X1, Y1, Z1, X2, Y2, Z2, W1, W2 = map(_f4, (X1, Y1, Z1, X2, Y2, Z2, W1, W2))
-    check(_lib.lib().abacus_paircount_weighted(
-        int(mode), ptr(X1), ptr(Y1), ptr(Z1), ptr(W1), C.c_int64(n1), ptr(X2), ptr(Y2), ptr(Z2), ptr(W2), C.c_int64(n2),
-        *tail))
-    return out, wsum, rsum
+    if host_prep is not None:
+        cols, geom = host_prep(cols, geom)
+    return call(getattr(_lib.lib(), f'abacus_{entry}'), ptr, [_f4(c) for c in cols], _f4(W1), _f4(W2), geom)
+
+
+def _paircount(mode, X1, Y1, Z1, boxsize, bins, X2=None, Y2=None, Z2=None, pimax=0.0, npibins=0, mu_max=1.0,
+               nmubins=0):
+    """host arrays (cast to float32 like the reference, tpcf_corrfunc.py:134-139) or - all of them - `_lib.DeviceArray`
+    columns of float32 / float64 already in HBM (the HOD catalogue: `abacus_paircount_dev`, no PCIe round trip)"""
+    return _counter('paircount', mode, _f4(bins), (X1, Y1, Z1, X2, Y2, Z2), None, (C.c_float(boxsize),), pimax, npibins, mu_max,
+                    nmubins, want_sums=False)[0]
+
+
+def _paircount_weighted(mode, X1, Y1, Z1, boxsize, bins, X2=None, Y2=None, Z2=None, W1=None, W2=None, pimax=0.0,
+                        npibins=0, mu_max=1.0, nmubins=0, want_rsum=True):
+    """`_paircount` with per-point float32 weights (None: unit weights): (npairs, wsum, rsum) per (bin, sub-bin) with
+    wsum = sum of w_i * w_j and rsum = sum of the pair separation (r | rp | s), both accumulated in float64 on the device
+    (`abacus_paircount_weighted[_dev]`); rsum is None when `want_rsum` is false."""
+    return _counter('paircount_weighted', mode, _f4(bins), (X1, Y1, Z1, X2, Y2, Z2), (W1, W2), (C.c_float(boxsize),), pimax,
+                    npibins, mu_max, nmubins, want_rsum=want_rsum)
 
 
 def _result(npairs, bins, nsub, extra, sums=None, avg_name=None):
@@ -148,14 +142,22 @@ def _weight_kw(kw, avg_kw, autocorr):
     return w1, w2, want_avg
 
 
-def _count(mode, autocorr, bins, nsub, extra, X1, Y1, Z1, X2, Y2, Z2, kw, avg_kw, **geom):
-    """the body shared by DD / DDrppi / DDsmu"""
+def _count(los, mode, autocorr, bins, nsub, extra, X1, Y1, Z1, X2, Y2, Z2, kw, avg_kw, **geom):
+    """the body shared by DD / DDrppi / DDsmu (`los` false: `geom` holds the box size) and their `_los` forms (`los` true:
+    `geom` holds the origin).  `count(**weights)` below is the one place where the two families differ."""
     second = (None, None, None) if autocorr else (X2, Y2, Z2)
+    if los:
+        if not autocorr and any(c is None for c in second):
+            raise ValueError('a cross count needs X2, Y2 and Z2')
+        count = lambda **w: _paircount_los(mode, X1, Y1, Z1, bins, *second, want_sums=bool(w), **w, **geom)     # noqa: E731
+    else:
+        box = geom.pop('boxsize')
+        count = lambda **w: (_paircount_weighted(mode, X1, Y1, Z1, box, bins, *second, **w, **geom) if w else       # noqa: E731
+                             (_paircount(mode, X1, Y1, Z1, box, bins, *second, **geom), None, None))
     wk = _weight_kw(kw, avg_kw, autocorr)
     if wk is None:
-        return _result(_paircount(mode, X1, Y1, Z1, geom.pop('boxsize'), bins, *second, **geom), bins, nsub, extra)
-    n, ws, rs = _paircount_weighted(mode, X1, Y1, Z1, geom.pop('boxsize'), bins, *second, W1=_w_arr(wk[0]), W2=_w_arr(wk[1]),
-                                    want_rsum=wk[2], **geom)
+        return _result(count()[0], bins, nsub, extra)
+    n, ws, rs = count(W1=_w_arr(wk[0]), W2=_w_arr(wk[1]), want_rsum=wk[2])
     return _result(n, bins, nsub, extra, sums=(ws, rs), avg_name=avg_kw[len('output_'):])
 
 
@@ -168,7 +170,7 @@ def DD(autocorr, nthreads, binfile, X1, Y1, Z1, X2=None, Y2=None, Z2=None, perio
     if not periodic or boxsize is None:
         raise NotImplementedError('only periodic boxes with an explicit boxsize are supported')
     bins = np.asarray(binfile, dtype=np.float64)
-    return _count(0, autocorr, bins, 1, {}, X1, Y1, Z1, X2, Y2, Z2, kw, 'output_ravg', boxsize=float(boxsize))
+    return _count(False, 0, autocorr, bins, 1, {}, X1, Y1, Z1, X2, Y2, Z2, kw, 'output_ravg', boxsize=float(boxsize))
 
 
 def DDrppi(autocorr, nthreads, binfile=None, pimax=None, X1=None, Y1=None, Z1=None, X2=None, Y2=None, Z2=None,
@@ -178,7 +180,7 @@ def DDrppi(autocorr, nthreads, binfile=None, pimax=None, X1=None, Y1=None, Z1=No
         raise NotImplementedError('only periodic boxes with an explicit boxsize are supported')
     bins = np.asarray(binfile, dtype=np.float64)
     npi = int(pimax)
-    return _count(1, autocorr, bins, npi, {'pimax': np.arange(1, npi + 1, dtype='f8')}, X1, Y1, Z1, X2, Y2, Z2, kw,
+    return _count(False, 1, autocorr, bins, npi, {'pimax': np.arange(1, npi + 1, dtype='f8')}, X1, Y1, Z1, X2, Y2, Z2, kw,
                   'output_rpavg', boxsize=float(boxsize), pimax=float(pimax), npibins=npi)
 
 
@@ -188,7 +190,7 @@ def DDsmu(autocorr, nthreads, binfile, mu_max, nmu_bins, X1, Y1, Z1, X2=None, Y2
     if not periodic or boxsize is None:
         raise NotImplementedError('only periodic boxes with an explicit boxsize are supported')
     bins = np.asarray(binfile, dtype=np.float64)
-    return _count(2, autocorr, bins, int(nmu_bins), {'mumax': (np.arange(1, nmu_bins + 1) * mu_max / nmu_bins)}, X1, Y1, Z1,
+    return _count(False, 2, autocorr, bins, int(nmu_bins), {'mumax': (np.arange(1, nmu_bins + 1) * mu_max / nmu_bins)}, X1, Y1, Z1,
                   X2, Y2, Z2, kw, 'output_savg', boxsize=float(boxsize), mu_max=float(mu_max), nmubins=int(nmu_bins))
 
 
@@ -314,78 +316,24 @@ def _paircount_los(mode, X1, Y1, Z1, bins, X2=None, Y2=None, Z2=None, W1=None, W
     origin = np.ascontiguousarray(origin, dtype=np.float64)
     if origin.shape != (3,):
         raise ValueError(f'origin has shape {origin.shape}, expected (3,)')
-    out = np.zeros(nb * nsub, dtype=np.uint64)
-    wsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums else None
-    rsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums and want_rsum else None
-    if X2 is None and W2 is not None:
-        raise ValueError('weights2 given for an autocorrelation')
-    n1, n2 = len(X1), (0 if X2 is None else len(X2))
-    for name, w, n in (('weights1', W1, n1), ('weights2', W2, n2)):
-        if w is not None and (len(w.shape) != 1 or w.shape[0] != n):
-            raise ValueError(f'{name} has shape {tuple(w.shape)}, expected ({n},)')
-    cols = [c for c in (X1, Y1, Z1, X2, Y2, Z2) if c is not None]
-    tail = lambda org: (ptr(org), ptr(bins), int(nb), C.c_float(pimax), int(npibins), C.c_float(mu_max), int(nmubins),   # noqa: E731
-                        ptr(out), ptr(wsum), ptr(rsum))
-    if any(isinstance(c, _lib.DeviceArray) for c in cols):
-        if not all(isinstance(c, _lib.DeviceArray) and c.dtype == cols[0].dtype for c in cols):
-            raise TypeError('device-resident coordinates: every column must be a DeviceArray of one dtype')
-        dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[cols[0].dtype]
-        dp = lambda c: None if c is None else c.ptr     # noqa: E731
-        own = []
+    zero = np.zeros(3)
 
-        def dev_w(w):
-            if w is None:
-                return None
-            if isinstance(w, _lib.DeviceArray):
-                if w.dtype != np.float32:
-                    raise TypeError('device-resident weights must be float32')
-                return w
-            own.append(_lib.DeviceArray(_f4(w)))
-            return own[-1]
-        try:
-            d1, d2 = dev_w(W1), dev_w(W2)
-            check(_lib.lib().abacus_paircount_los_dev(
-                int(mode), dp(X1), dp(Y1), dp(Z1), dp(d1), C.c_int64(n1), dp(X2), dp(Y2), dp(Z2), dp(d2), C.c_int64(n2), dt,
-                *tail(origin)))
-        finally:
-            for a in own:
-                a.free()
-        return out, wsum, rsum
-    if isinstance(W1, _lib.DeviceArray) or isinstance(W2, _lib.DeviceArray):
-        raise TypeError('device-resident weights need device-resident coordinates')
-    host = [None if c is None else np.asarray(c) for c in (X1, Y1, Z1, X2, Y2, Z2)]
-    if any(c is not None and c.dtype == np.float64 for c in host):
+    def centre(cols, geom):
+        host = [None if c is None else np.asarray(c) for c in cols]
+        if not any(c is not None and c.dtype == np.float64 for c in host):
+            return cols, geom
         # float64 columns: the subtraction in float64, one rounding to float32 - on the host, the C ABI takes float32 arrays
-        host = [None if c is None else (c - c.dtype.type(origin[i % 3])).astype(np.float32) if c.dtype == np.float64
-                else _f4(c) - np.float32(origin[i % 3]) for i, c in enumerate(host)]
-        origin = np.zeros(3)
-    X1, Y1, Z1, X2, Y2, Z2 = map(_f4, host)
-    W1, W2 = _f4(W1), _f4(W2)
-    check(_lib.lib().abacus_paircount_los(
-        int(mode), ptr(X1), ptr(Y1), ptr(Z1), ptr(W1), C.c_int64(n1), ptr(X2), ptr(Y2), ptr(Z2), ptr(W2), C.c_int64(n2),
-        *tail(origin)))
-    return out, wsum, rsum
-
-
-def _count_los(mode, autocorr, bins, nsub, extra, X1, Y1, Z1, X2, Y2, Z2, origin, kw, avg_kw, **geom):
-    """the body shared by DD_los / DDrppi_los / DDsmu_los: `_count` without a box"""
-    second = (None, None, None) if autocorr else (X2, Y2, Z2)
-    if not autocorr and any(c is None for c in second):
-        raise ValueError('a cross count needs X2, Y2 and Z2')
-    wk = _weight_kw(kw, avg_kw, autocorr)
-    if wk is None:
-        n, _, _ = _paircount_los(mode, X1, Y1, Z1, bins, *second, origin=origin, want_sums=False, **geom)
-        return _result(n, bins, nsub, extra)
-    n, ws, rs = _paircount_los(mode, X1, Y1, Z1, bins, *second, W1=_w_arr(wk[0]), W2=_w_arr(wk[1]), origin=origin,
-                               want_rsum=wk[2], **geom)
-    return _result(n, bins, nsub, extra, sums=(ws, rs), avg_name=avg_kw[len('output_'):])
+        return [None if c is None else (c - c.dtype.type(origin[i % 3])).astype(np.float32) if c.dtype == np.float64
+                else _f4(c) - np.float32(origin[i % 3]) for i, c in enumerate(host)], (ptr(zero),)
+    return _counter('paircount_los', mode, bins, (X1, Y1, Z1, X2, Y2, Z2), (W1, W2), (ptr(origin),), pimax, npibins, mu_max,
+                    nmubins, want_sums=want_sums, want_rsum=want_rsum, host_prep=centre)
 
 
 def DD_los(autocorr, nthreads, binfile, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0), **kw):
     """pair counts in s bins of a non-periodic catalogue in Cartesian columns seen from `origin` (no box, no wrapping);
     weights1 / weights2 / weight_type / output_ravg as `DD`"""
     bins = np.asarray(binfile, dtype=np.float64)
-    return _count_los(0, autocorr, bins, 1, {}, X1, Y1, Z1, X2, Y2, Z2, origin, kw, 'output_ravg')
+    return _count(True, 0, autocorr, bins, 1, {}, X1, Y1, Z1, X2, Y2, Z2, kw, 'output_ravg', origin=origin)
 
 
 def DDrppi_los(autocorr, nthreads, binfile, pimax, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0), **kw):
@@ -397,8 +345,8 @@ def DDrppi_los(autocorr, nthreads, binfile, pimax, X1, Y1, Z1, X2=None, Y2=None,
     npi = int(pimax)
     if npi < 1:
         raise ValueError('pimax must be at least 1 (unit pi bins)')
-    return _count_los(1, autocorr, bins, npi, {'pimax': np.arange(1, npi + 1, dtype='f8')}, X1, Y1, Z1, X2, Y2, Z2, origin, kw,
-                      'output_rpavg', pimax=float(pimax), npibins=npi)
+    return _count(True, 1, autocorr, bins, npi, {'pimax': np.arange(1, npi + 1, dtype='f8')}, X1, Y1, Z1, X2, Y2, Z2, kw,
+                  'output_rpavg', origin=origin, pimax=float(pimax), npibins=npi)
 
 
 def DDsmu_los(autocorr, nthreads, binfile, mu_max, nmu_bins, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0),
@@ -407,8 +355,8 @@ def DDsmu_los(autocorr, nthreads, binfile, mu_max, nmu_bins, X1, Y1, Z1, X2=None
     if not mu_max > 0 or int(nmu_bins) < 1:
         raise ValueError('mu_max must be positive, with at least one mu bin')
     bins = np.asarray(binfile, dtype=np.float64)
-    return _count_los(2, autocorr, bins, int(nmu_bins), {'mumax': (np.arange(1, nmu_bins + 1) * mu_max / nmu_bins)}, X1, Y1, Z1,
-                      X2, Y2, Z2, origin, kw, 'output_savg', mu_max=float(mu_max), nmubins=int(nmu_bins))
+    return _count(True, 2, autocorr, bins, int(nmu_bins), {'mumax': (np.arange(1, nmu_bins + 1) * mu_max / nmu_bins)}, X1, Y1, Z1,
+                  X2, Y2, Z2, kw, 'output_savg', origin=origin, mu_max=float(mu_max), nmubins=int(nmu_bins))
 
 
 def radec_to_xyz(ra_deg, dec_deg, dist):

@@ -15,13 +15,15 @@
 //   rsum = sum of the separation (r | rp = sqrt(dx^2 + dy^2) | s): sqrtf - correctly rounded - of the very r^2 that chose the
 //          bin, accumulated in float64;
 // a missing weight array is unit weights; the weight is sorted into cells WITH its point (both sort paths); float64 atomics
-// make the sums reproducible to n 2^-52 sum|term| per bin, not bit for bit.  Kernel: pair_count_w below.
+// make the sums reproducible to n 2^-52 sum|term| per bin, not bit for bit.
 //
-// Algorithm: both point sets are counting-sorted into a cell grid with cell size >= the largest separation
-// (SoA x|y|z per set, cell_start offsets).  One workgroup per non-empty cell of set 1 walks the 27 neighbour cells
-// of set 2, staging 256 neighbours at a time in LDS; every thread owns one point of set 1 and scans the staged
-// chunk (LDS broadcast reads), binning into a per-workgroup LDS histogram that is flushed with 64-bit atomics.
-// Work is O(N * nbar * 27 * cell^3); the loop is VALU/LDS bound (not HBM): ~20 VALU ops per candidate pair.
+// What this file holds, in order:
+//   grids and the cell sort   CellGrid (periodic box), OpenGrid (bounding box of a light cone); cell_count<COUNT, W, Grid>,
+//                             cell_fill / cell_gather / cell_starts (counting sort below 200 000 points, radix sort above)
+//   unweighted, periodic      pair_count (first generation: the comparator of the tests), pair_count2, pair_count3 (default)
+//   weighted and light cone   one walk in two bodies: pair_count_w (periodic, float32), pair_count_los (open grid, float64)
+//   host side                 one set of work buffers, stage_columns, sort_into_cells, launch helpers, the two drivers
+//                             paircount_impl and paircount_los_impl over one run loop, the C ABI
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -43,11 +45,6 @@ namespace {
 constexpr int PB = 256;          // threads per workgroup
 constexpr int MAX_HIST = 8192;   // LDS histogram entries (bins * sub-bins)
 
-struct CellGrid {
-    int ncx, ncy, ncz;
-    float box, inv_box;
-};
-
 __device__ __forceinline__ int cell_coord(float v, int nc, float inv_box) {
     // fractional position in the box, periodic: works for [0,L), [-L/2,L/2) or anything else
     float f = v * inv_box;
@@ -55,6 +52,32 @@ __device__ __forceinline__ int cell_coord(float v, int nc, float inv_box) {
     int c = (int)(f * (float)nc);
     return c >= nc ? nc - 1 : c;
 }
+
+struct CellGrid {
+    int ncx, ncy, ncz;
+    float box, inv_box;
+    __device__ __forceinline__ int cell(const float v[3]) const {
+        return (cell_coord(v[0], ncx, inv_box) * ncy + cell_coord(v[1], ncy, inv_box)) * ncz + cell_coord(v[2], ncz, inv_box);
+    }
+};
+
+// Open grid of a light cone: the bounding box of both sets, per-dimension cell counts 1 .. 128 with a cell side >= 1.0001
+// reach; cell = min(int((v - lo) inv_cell), nc - 1) in float32; neighbour cells outside the grid are skipped, nothing wraps.
+// The three float32 roundings of the cell index move a point by less than 3 2^-24 nc cells, so two points whose indices
+// differ by 2 or more are further apart than (1 - 5e-5) of a cell side > reach: the 27 cells suffice.
+struct OpenGrid {
+    int nc[3];
+    float lo[3], inv[3];
+    __device__ __forceinline__ int cell(const float v[3]) const {
+        int c[3];
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            c[d] = (int)((v[d] - lo[d]) * inv[d]);
+            c[d] = c[d] >= nc[d] ? nc[d] - 1 : (c[d] < 0 ? 0 : c[d]);   // c < 0: only a NaN coordinate, kept inside the arrays
+        }
+        return (c[0] * nc[1] + c[1]) * nc[2] + c[2];
+    }
+};
 
 // Coordinate frame of a catalogue: the smallest and the largest coordinate per dimension as order-preserving integer keys
 // (so that atomicMin / atomicMax work on floats).  Corrfunc accepts any coordinate range; galaxies from the HOD live in
@@ -71,38 +94,25 @@ __device__ __forceinline__ float funkey(unsigned int k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// COUNT: per-cell counters by global atomics (counting sort, small inputs); else the cell ids become the keys of a radix sort
-// and idx the values.  W (weighted counts): the point's weight rides in the free lane of the packed record
-template <bool COUNT, bool W>
-__global__ void cell_count(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                           const float *__restrict__ w, int64_t n, CellGrid g, unsigned int *__restrict__ counts, unsigned int *__restrict__ cellid,
-                           unsigned int *__restrict__ idx, float4 *__restrict__ packed, int *__restrict__ outside,
-                           Frame *__restrict__ frame) {
-    bool out = false;
+// A thread's smallest and largest keys per dimension into *frame: wave reduction, then ONE pair of global atomics per workgroup
+// and dimension (one per wave was 10^5 atomics on six addresses: 1 ms of cell_count's 1.1).  Every thread of the workgroup calls.
+struct MinMax {
     unsigned int mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {x[i], y[i], z[i]};
-        const int c = (cell_coord(v[0], g.ncx, g.inv_box) * g.ncy + cell_coord(v[1], g.ncy, g.inv_box)) * g.ncz +
-                      cell_coord(v[2], g.ncz, g.inv_box);
-        cellid[i] = (unsigned int)c;
-        if (COUNT) atomicAdd(&counts[c], 1u);
-        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], W ? w[i] : 0.f);   // one 16-B piece per point for the gather
-        out = out || !(v[0] >= 0.f && v[0] < g.box && v[1] >= 0.f && v[1] < g.box && v[2] >= 0.f && v[2] < g.box);
+    __device__ __forceinline__ void take(const float v[3]) {
 #pragma unroll
         for (int d = 0; d < 3; d++) {
             const unsigned int k = fkey(v[d]);
             mn[d] = min(mn[d], k), mx[d] = max(mx[d], k);
         }
     }
-    if (out) *outside = 1;   // some coordinate is not in [0, L)
-    // frame: wave reduction, then ONE pair of global atomics per workgroup and dimension (one per wave was 10^5 atomics
-    // on six addresses: 1 ms of this kernel's 1.1)
+};
+__device__ __forceinline__ void frame_reduce(const MinMax &m, Frame *__restrict__ frame) {
     __shared__ unsigned int s_mn[3], s_mx[3];
     if (threadIdx.x < 3) s_mn[threadIdx.x] = 0xffffffffu, s_mx[threadIdx.x] = 0u;
     __syncthreads();
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-        unsigned int a = mn[d], b = mx[d];
+        unsigned int a = m.mn[d], b = m.mx[d];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) a = min(a, (unsigned int)__shfl_xor((int)a, off, 64)), b = max(b, (unsigned int)__shfl_xor((int)b, off, 64));
         if ((threadIdx.x & 63) == 0 && a <= b) atomicMin(&s_mn[d], a), atomicMax(&s_mx[d], b);
@@ -110,6 +120,56 @@ __global__ void cell_count(const float *__restrict__ x, const float *__restrict_
     __syncthreads();
     if (threadIdx.x < 3 && s_mn[threadIdx.x] <= s_mx[threadIdx.x])
         atomicMin(&frame->mn[threadIdx.x], s_mn[threadIdx.x]), atomicMax(&frame->mx[threadIdx.x], s_mx[threadIdx.x]);
+}
+
+// The cell of every point on either grid.  COUNT: per-cell counters by global atomics (counting sort, small inputs); else the
+// cell ids become the keys of a radix sort and idx the values.  W (weighted counts): the point's weight rides in the free lane
+// of the packed record.  The periodic grid alone keeps the frame and `outside` (some coordinate is not in [0, L)): FramedGrid.
+struct FramedGrid : CellGrid {
+    int *outside;
+    Frame *frame;
+};
+template <bool COUNT, bool W, typename Grid>
+__global__ void cell_count(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                           const float *__restrict__ w, int64_t n, Grid g, unsigned int *__restrict__ counts, unsigned int *__restrict__ cellid,
+                           unsigned int *__restrict__ idx, float4 *__restrict__ packed) {
+    constexpr bool PERIODIC = std::is_same<Grid, FramedGrid>::value;
+    bool out = false;
+    MinMax m;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v[3] = {x[i], y[i], z[i]};
+        const int c = g.cell(v);
+        cellid[i] = (unsigned int)c;
+        if (COUNT) atomicAdd(&counts[c], 1u);
+        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], W ? w[i] : 0.f);   // one 16-B piece per point for the gather
+        if constexpr (PERIODIC) {
+            out = out || !(v[0] >= 0.f && v[0] < g.box && v[1] >= 0.f && v[1] < g.box && v[2] >= 0.f && v[2] < g.box);
+            m.take(v);
+        }
+    }
+    if constexpr (PERIODIC) {
+        if (out) *g.outside = 1;
+        frame_reduce(m, g.frame);
+    }
+}
+
+// bounding box of a set as order-preserving keys (fkey)
+__global__ void bbox_minmax(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, int64_t n,
+                            Frame *__restrict__ frame) {
+    MinMax m;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v[3] = {x[i], y[i], z[i]};
+        m.take(v);
+    }
+    frame_reduce(m, frame);
+}
+
+// observer-centred float32 columns: the subtraction in the column's own dtype, then one rounding (dst may be src).  With
+// origin 0 this is the plain cast of float64 columns (the HOD catalogue), as the reference casts before it calls Corrfunc
+// (analysis/tpcf_corrfunc.py:134-139: `.astype(np.float32)`, round to nearest): x - 0.0 is x for every double.
+template <typename T>
+__global__ void los_centre(const T *src, T origin, float *dst, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)(src[i] - origin);
 }
 
 // W: the weight takes the slot its point drew (the order inside a cell differs from run to run, point and weight stay together)
@@ -811,8 +871,9 @@ __global__ __launch_bounds__(P3_WAVES * 64) void pair_count3(PairArgs a, const F
 //     The sums depend on the order of the atomics in their last bits: |error| <= n 2^-52 sum|term| whatever the order.
 //   * MODE 0: the last bin takes most pairs of logarithmic bins; every lane keeps that bin's three sums in registers and adds
 //     them to the histogram once, at the end (64 lanes on one LDS address serialise; a ballot cannot carry a float64 sum).
-//   * An entry is 20 bytes: W_MAX_HIST entries per launch, more are counted in runs of separation bins (paircount_impl).
+//   * An entry is 20 bytes: W_MAX_HIST entries per launch, more are counted in runs of separation bins (for_runs).
 //   * The autocorrelation walks the full stencil (ordered pairs, nothing is doubled).
+// pair_count_los below is this walk on the open grid: a fix to one belongs in both (profiles/pairs_shared_walk/README.md).
 constexpr int W_MAX_HIST = 2048;
 
 struct WeightArgs {
@@ -945,7 +1006,6 @@ __global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, in
         }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
 // Light cones: pair counts with a PAIRWISE line of sight on an OPEN grid (abacus_paircount_los, Corrfunc.mocks' DDrppi_mocks /
 // DDsmu_mocks on Cartesian columns).  No reference code and no Corrfunc run stands behind this; the conventions are restated
 // here and pinned against the NumPy statement tests/pairs_los_statement.py.
@@ -960,83 +1020,6 @@ __global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, in
 //   rsum = sum sqrt(q) of the q that chose the bin, float64.
 // float64 because rp^2 = s^2 - pi^2 cancels at light-cone distances: with |p| ~ 4000 and pi ~ 30 float32 leaves ~1e-4 on rp^2,
 // percent-level at rp = 0.1.
-// Grid: the bounding box of both sets (one min/max reduction, 24 bytes to the host), per-dimension cell counts 1 .. 128 with a
-// cell side >= 1.0001 reach; cell = min(int((v - lo) inv_cell), nc - 1) in float32; neighbour cells outside the grid are
-// skipped, nothing wraps.  The three float32 roundings of the cell index move a point by less than 3 2^-24 nc cells, so two
-// points whose indices differ by 2 or more are further apart than (1 - 5e-5) of a cell side > reach: the 27 cells suffice.
-struct OpenGrid {
-    int nc[3];
-    float lo[3], inv[3];
-};
-
-__device__ __forceinline__ int open_cell(float v, float lo, float inv, int nc) {
-    const int c = (int)((v - lo) * inv);
-    return c >= nc ? nc - 1 : (c < 0 ? 0 : c);   // c < 0: only a NaN coordinate, kept inside the arrays
-}
-
-template <bool COUNT, bool W>
-__global__ void cell_count_open(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                                const float *__restrict__ w, int64_t n, OpenGrid g, unsigned int *__restrict__ counts,
-                                unsigned int *__restrict__ cellid, unsigned int *__restrict__ idx, float4 *__restrict__ packed) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {x[i], y[i], z[i]};
-        const int c = (open_cell(v[0], g.lo[0], g.inv[0], g.nc[0]) * g.nc[1] + open_cell(v[1], g.lo[1], g.inv[1], g.nc[1])) * g.nc[2] +
-                      open_cell(v[2], g.lo[2], g.inv[2], g.nc[2]);
-        cellid[i] = (unsigned int)c;
-        if (COUNT) atomicAdd(&counts[c], 1u);
-        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], W ? w[i] : 0.f);
-    }
-}
-
-// bounding box of a set as order-preserving keys (fkey): wave reduction, one pair of global atomics per workgroup and dimension
-__global__ void bbox_minmax(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, int64_t n,
-                            Frame *__restrict__ frame) {
-    unsigned int mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {x[i], y[i], z[i]};
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const unsigned int k = fkey(v[d]);
-            mn[d] = min(mn[d], k), mx[d] = max(mx[d], k);
-        }
-    }
-    __shared__ unsigned int s_mn[3], s_mx[3];
-    if (threadIdx.x < 3) s_mn[threadIdx.x] = 0xffffffffu, s_mx[threadIdx.x] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        unsigned int a = mn[d], b = mx[d];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a = min(a, (unsigned int)__shfl_xor((int)a, off, 64)), b = max(b, (unsigned int)__shfl_xor((int)b, off, 64));
-        if ((threadIdx.x & 63) == 0 && a <= b) atomicMin(&s_mn[d], a), atomicMax(&s_mx[d], b);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && s_mn[threadIdx.x] <= s_mx[threadIdx.x])
-        atomicMin(&frame->mn[threadIdx.x], s_mn[threadIdx.x]), atomicMax(&frame->mx[threadIdx.x], s_mx[threadIdx.x]);
-}
-
-// observer-centred float32 columns: the subtraction in the column's own dtype, then one rounding (dst may be src)
-template <typename T>
-__global__ void los_centre(const T *src, T origin, float *dst, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)(src[i] - origin);
-}
-
-struct LosArgs {
-    int autocorr, nc[3], nbins, nsub;
-    // float32 pre-test: a candidate with s2f > pre_hi or s2f < pre_lo skips the float64 arithmetic (see the kernel)
-    float pre_lo, pre_hi;
-    double pimax, dpi, mu_max, inv_dmu;
-    const double *edges2;   // (nbins + 1) squared edges
-    const float *x1, *y1, *z1, *w1, *x2, *y2, *z2, *w2;   // cell order; w NULL: unit weights
-    const int64_t *start1, *start2;
-    unsigned long long *npairs;
-    double *wsum, *rsum;
-};
-
-// Modelled on pair_count_w: a persistent workgroup per non-empty cell of set 1, the in-range neighbour cells as ONE virtual
-// list of which every thread fetches one point per round into registers and walks the slice of its own cell (LDS broadcast
-// reads); LDS histogram (counts | WEIGHTED: sums of w w | RSUM: sums of sqrt(q)), flushed once per workgroup; full stencil for
-// the autocorrelation (ordered pairs, nothing doubled); MODE 0 keeps the last bin in registers like pair_count_w.
 //
 // Pre-test (cannot change membership).  s2f = dx dx + dy dy + dz dz in float32 from the SAME float32 d: three products and two
 // sums of non-negative terms, each rounded once, so s2f = s2 (1 + e) with |e| < 3.1 2^-24 < 2^-22 against the exact - and the
@@ -1048,6 +1031,21 @@ struct LosArgs {
 //   float32(e2[0] (1 - 2^-20)) rounded DOWN, and 0 (test off) when that is below 1e-30: above it an underflowing product
 //   (< 1.2e-38 lost) moves s2f by less than 2^-22 relative too.  s2f < pre_lo implies s2 < e2[0] (1 - 2^-20) (1 + 2^-22) < e2[0].
 // NaN fails both comparisons and falls to the float64 path, which counts nothing for it.
+struct LosArgs {
+    int autocorr, nc[3], nbins, nsub;
+    // float32 pre-test: a candidate with s2f > pre_hi or s2f < pre_lo skips the float64 arithmetic (see above)
+    float pre_lo, pre_hi;
+    double pimax, dpi, mu_max, inv_dmu;
+    const double *edges2;   // (nbins + 1) squared edges
+    const float *x1, *y1, *z1, *w1, *x2, *y2, *z2, *w2;   // cell order; w NULL: unit weights
+    const int64_t *start1, *start2;
+    unsigned long long *npairs;
+    double *wsum, *rsum;
+};
+
+// The walk of pair_count_w on the open grid: a persistent workgroup per non-empty cell of set 1, the in-range neighbour cells
+// as ONE virtual list; LDS histogram ([WEIGHTED: sums of w w] [RSUM: sums of sqrt(q)] counts), flushed once per workgroup; full
+// stencil for the autocorrelation; MODE 0 keeps the last bin in registers.
 template <int MODE, bool WEIGHTED, bool RSUM>
 __global__ __launch_bounds__(PB) void pair_count_los(LosArgs a, int ncell, unsigned long long *__restrict__ evaluated) {
     __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
@@ -1180,57 +1178,103 @@ __global__ __launch_bounds__(PB) void pair_count_los(LosArgs a, int ncell, unsig
         }
 }
 
+// ------------------------------------------------------------------------------------------------------------- host side ----
 struct SortedSet {
-    DevBuf raw, sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wraw, wsorted;
+    DevBuf sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wsorted;
     float *sx, *sy, *sz, *sw;   // sw: the weights in cell order (weighted counts with weights for this set), else NULL
     int64_t n;
 };
 
-// float64 device columns (the HOD catalogue) -> float32, as the reference casts before it calls Corrfunc
-// (analysis/tpcf_corrfunc.py:134-139: `.astype(np.float32)`, round to nearest)
-__global__ void cast_f64_f32(const double *__restrict__ src, float *__restrict__ dst, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)src[i];
+// Empty frame, block of flags and counters in HBM: [0] outside, [16] Frame, [48] candidate pairs evaluated
+const Frame EMPTY_FRAME = {{0xffffffffu, 0xffffffffu, 0xffffffffu}, {0u, 0u, 0u}};
+struct Flags {
+    int *outside;
+    Frame *frame;
+    unsigned long long *evaluated;
+};
+
+// The work buffers of every counter of this file: the library serialises its entry points (ABACUS_ENTER), so the periodic and
+// the light-cone driver take turns on one set
+struct Work {
+    SortedSet S[2];
+    DevBuf cols[2], wts[2];   // staged float32 columns and weights of the two sets
+    DevBuf scratch, edges, out, list, flag;
+    int flags(Flags &f) {
+        ABACUS_TRY(flag.reserve(64));
+        f.outside = flag.as<int>(), f.frame = reinterpret_cast<Frame *>(flag.as<char>() + 16);
+        f.evaluated = reinterpret_cast<unsigned long long *>(flag.as<char>() + 48);
+        HIP_TRY(hipMemsetAsync(flag.p, 0, 64, stream()));
+        HIP_TRY(hipMemcpyAsync(f.frame, &EMPTY_FRAME, sizeof EMPTY_FRAME, hipMemcpyHostToDevice, stream()));
+        return 0;
+    }
+} g_work;
+
+struct Columns {   // float32 device columns of a set, with its weights (NULL: none)
+    const float *x[3], *w;
+};
+
+// Caller columns -> float32 device columns.  where = 0: host float32 arrays (and host weights); 1: device float32; 2: device
+// float64 (device weights).  origin (NULL: none) is subtracted in the column's own dtype before the one rounding; device float32
+// columns that need no shift are read in place.  n > 0.  `label` names the conversion kernel to the profiler.
+int stage_columns(const char *label, const void *const src[3], const float *w, int where, int64_t n, const double *origin,
+                  DevBuf &cols, DevBuf &wts, Columns &c) {
+    const bool shifted = origin && (origin[0] != 0.0 || origin[1] != 0.0 || origin[2] != 0.0);
+    const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 2048);
+    if (where == 1 && !shifted) {
+        for (int d = 0; d < 3; d++) c.x[d] = (const float *)src[d];
+    } else {
+        ABACUS_TRY(cols.reserve(3 * (size_t)n * 4));
+        for (int d = 0; d < 3; d++) {
+            float *dst = cols.as<float>() + (size_t)d * n;
+            const double o = origin ? origin[d] : 0.0;
+            c.x[d] = dst;
+            if (where == 2) {
+                ABACUS_LAUNCH(label, los_centre<double>, dim3(nblk), dim3(256), 0, (const double *)src[d], o, dst, n);
+                continue;
+            }
+            const float *from = (const float *)src[d];
+            if (where == 0) {
+                HIP_TRY(hipMemcpyAsync(dst, from, (size_t)n * 4, hipMemcpyHostToDevice, stream()));
+                from = dst;
+            }
+            if (shifted) ABACUS_LAUNCH(label, los_centre<float>, dim3(nblk), dim3(256), 0, from, (float)o, dst, n);
+        }
+    }
+    c.w = w;
+    if (w && where == 0) {
+        ABACUS_TRY(wts.reserve((size_t)n * 4));
+        HIP_TRY(hipMemcpyAsync(wts.p, w, (size_t)n * 4, hipMemcpyHostToDevice, stream()));
+        c.w = wts.as<float>();
+    }
+    return 0;
 }
 
-// where = 0: host float32 arrays; 1: device float32; 2: device float64.  hw: float32 weights of the points (host memory when
-// where = 0, else device memory) or NULL; they are sorted along with the points into s.sw
-int sort_into_cells(const void *hx, const void *hy, const void *hz, const float *hw, int where, int64_t n, const CellGrid &g,
-                    SortedSet &s, DevBuf &scratch, int *d_outside, Frame *d_frame, const OpenGrid *og = nullptr) {
-    const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
+template <bool COUNT, bool W, typename Grid>
+int count_cells(const Columns &c, int64_t n, const Grid &g, SortedSet &s, int nblk) {
+    ABACUS_LAUNCH("pair_cell_count", (cell_count<COUNT, W, Grid>), dim3(nblk), dim3(256), 0, c.x[0], c.x[1], c.x[2], COUNT ? nullptr : c.w, n, g,
+                  COUNT ? s.counts.as<unsigned int>() : nullptr, s.cellid.as<unsigned int>(), COUNT ? nullptr : s.idx.as<unsigned int>(),
+                  COUNT ? nullptr : s.packed.as<float4>());
+    return 0;
+}
+
+// The set in cell order on either grid (ncell cells): s.sx | sy | sz, s.start and - with weights - s.sw
+template <typename Grid>
+int sort_into_cells(const Columns &c, int64_t n, const Grid &g, int64_t ncell, SortedSet &s, DevBuf &scratch) {
     const size_t n1 = (size_t)std::max<int64_t>(n, 1);
     s.n = n;
     ABACUS_TRY(s.sorted.reserve(3 * n1 * 4));
     ABACUS_TRY(s.counts.reserve((size_t)(ncell + 1) * 4));
     ABACUS_TRY(s.cellid.reserve(n1 * 4));
     ABACUS_TRY(s.start.reserve((size_t)(ncell + 1) * 8));
-    const float *rx, *ry, *rz;
+    const float *rx = c.x[0], *ry = c.x[1], *rz = c.x[2], *rw = c.w;
     s.sx = s.sorted.as<float>();
     s.sy = s.sx + n1;
     s.sz = s.sy + n1;
     const int nblk = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), 2048);
-    if (where == 1) {   // caller's device arrays, read in place
-        rx = (const float *)hx, ry = (const float *)hy, rz = (const float *)hz;
-    } else {
-        ABACUS_TRY(s.raw.reserve(3 * n1 * 4));
-        float *bx = s.raw.as<float>(), *by = bx + n1, *bz = by + n1;
-        const void *src[3] = {hx, hy, hz};
-        float *dst[3] = {bx, by, bz};
-        for (int d = 0; d < 3 && n > 0; d++) {
-            if (where == 0) HIP_TRY(hipMemcpyAsync(dst[d], src[d], n * 4, hipMemcpyHostToDevice, stream()));
-            else ABACUS_LAUNCH("pair_cast", cast_f64_f32, dim3(nblk), dim3(256), 0, (const double *)src[d], dst[d], n);
-        }
-        rx = bx, ry = by, rz = bz;
-    }
-    const float *rw = hw;
     s.sw = nullptr;
-    if (hw) {
+    if (rw) {
         ABACUS_TRY(s.wsorted.reserve(n1 * 4));
         s.sw = s.wsorted.as<float>();
-        if (where == 0) {
-            ABACUS_TRY(s.wraw.reserve(n1 * 4));
-            if (n > 0) HIP_TRY(hipMemcpyAsync(s.wraw.p, hw, n * 4, hipMemcpyHostToDevice, stream()));
-            rw = s.wraw.as<float>();
-        }
     }
     // large inputs: stable radix sort of (cell id, index) + gather + a search per cell (10^7 points: 0.6 ms against 2.2 ms of
     // the counting sort below, whose two passes are a global atomic per point each)
@@ -1239,18 +1283,8 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, const float 
         ABACUS_TRY(s.idx.reserve(n1 * 4));
         ABACUS_TRY(s.idx2.reserve(n1 * 4));
         ABACUS_TRY(s.packed.reserve(n1 * 16));
-        if (og && hw)
-            ABACUS_LAUNCH("pair_cell_count", (cell_count_open<false, true>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, *og, (unsigned int *)nullptr,
-                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>());
-        else if (og)
-            ABACUS_LAUNCH("pair_cell_count", (cell_count_open<false, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, *og, (unsigned int *)nullptr,
-                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>());
-        else if (hw)
-            ABACUS_LAUNCH("pair_cell_count", (cell_count<false, true>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, g, (unsigned int *)nullptr,
-                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>(), d_outside, d_frame);
-        else
-            ABACUS_LAUNCH("pair_cell_count", (cell_count<false, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n, g, (unsigned int *)nullptr,
-                          s.cellid.as<unsigned int>(), s.idx.as<unsigned int>(), s.packed.as<float4>(), d_outside, d_frame);
+        if (rw) ABACUS_TRY((count_cells<false, true>(c, n, g, s, nblk)));
+        else ABACUS_TRY((count_cells<false, false>(c, n, g, s, nblk)));
         int end_bit = 1;
         while (((int64_t)1 << end_bit) < ncell) end_bit++;
         size_t tmp_bytes = 0;
@@ -1262,7 +1296,7 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, const float 
                                                                      s.idx.as<unsigned int>(), s.idx2.as<unsigned int>(), (int)n, 0, end_bit, stream());
         prof_end("pair_cell_sort");
         if (sorted != hipSuccess) return fail("abacus_paircount: radix sort failed");
-        if (hw)
+        if (rw)
             ABACUS_LAUNCH("pair_cell_fill", cell_gather<true>, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(),
                           s.sx, s.sy, s.sz, s.sw);
         else
@@ -1273,15 +1307,9 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, const float 
         return 0;
     }
     HIP_TRY(hipMemsetAsync(s.counts.p, 0, (size_t)(ncell + 1) * 4, stream()));
-    if (n > 0 && og)
-        ABACUS_LAUNCH("pair_cell_count", (cell_count_open<true, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, (const float *)nullptr, n, *og,
-                      s.counts.as<unsigned int>(), s.cellid.as<unsigned int>(), (unsigned int *)nullptr, (float4 *)nullptr);
-    else if (n > 0)
-        ABACUS_LAUNCH("pair_cell_count", (cell_count<true, false>), dim3(nblk), dim3(256), 0, rx, ry, rz, (const float *)nullptr, n, g,
-                      s.counts.as<unsigned int>(), s.cellid.as<unsigned int>(), (unsigned int *)nullptr, (float4 *)nullptr, d_outside,
-                      d_frame);
+    if (n > 0) ABACUS_TRY((count_cells<true, false>(c, n, g, s, nblk)));
     ABACUS_TRY(exclusive_scan_u32(s.counts.as<unsigned int>(), ncell, s.start.as<int64_t>(), scratch, 1));
-    if (n > 0 && hw)
+    if (n > 0 && rw)
         ABACUS_LAUNCH("pair_cell_fill", cell_fill<true>, dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n,
                       s.cellid.as<unsigned int>(), s.start.as<int64_t>(), s.counts.as<unsigned int>(), s.sx, s.sy, s.sz, s.sw);
     else if (n > 0)
@@ -1290,9 +1318,93 @@ int sort_into_cells(const void *hx, const void *hy, const void *hz, const float 
     return 0;
 }
 
+// f(std::integral_constant<int, mode>()): the mode as a template argument of what f launches
+template <typename F>
+int with_mode(int mode, F &&f) {
+    if (mode == 0) return f(std::integral_constant<int, 0>());
+    if (mode == 1) return f(std::integral_constant<int, 1>());
+    return f(std::integral_constant<int, 2>());
+}
+template <typename F>
+int with_flag(bool on, F &&f) { return on ? f(std::true_type()) : f(std::false_type()); }
+
+int cu_count(int &ncu) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    return 0;
+}
+
+// grid of persistent workgroups: min(jobs, CUs x resident workgroups of this kernel at this block size and dynamic LDS)
+template <typename K>
+int resident_grid(K kernel, int block, size_t lds, int64_t jobs, dim3 &grid) {
+    int ncu = 256, per_cu = 1;
+    ABACUS_TRY(cu_count(ncu));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, block, lds));
+    grid = dim3((unsigned int)std::min<int64_t>(jobs, (int64_t)ncu * std::max(per_cu, 1)));
+    return 0;
+}
+
+// One launch bins into at most 63 separation bins (the kernels' edge tables) and max_hist LDS histogram entries.  More bins -
+// Corrfunc takes any number - are counted in runs of consecutive separation bins, each on a grid of its own, smaller reach; a
+// pair ON an edge shared by two runs belongs to the upper bin in both ([lo, hi) bins).  f(first bin, bins, offset in the outputs)
+template <typename F>
+int for_runs(int nbins, int nsub, int max_hist, F &&f) {
+    const int run = std::min(63, max_hist / nsub);
+    for (int b0 = 0; b0 < nbins; b0 += run) ABACUS_TRY(f(b0, std::min(run, nbins - b0), (size_t)b0 * nsub));
+    return 0;
+}
+
+// the squared edges of a run in the kernel's edge type, on the host and in g_work.edges
+template <typename Q>
+int upload_edges(const float *edges, int nb, std::vector<Q> &e2) {
+    e2.resize(nb + 1);
+    for (int b = 0; b <= nb; b++) e2[b] = (Q)edges[b] * (Q)edges[b];
+    ABACUS_TRY(g_work.edges.reserve((size_t)(nb + 1) * sizeof(Q)));
+    HIP_TRY(hipMemcpyAsync(g_work.edges.p, e2.data(), (size_t)(nb + 1) * sizeof(Q), hipMemcpyHostToDevice, stream()));
+    return 0;
+}
+
+// outputs of a run: ntot counts [| ntot sums of w w | ntot sums of the separation] in g_work.out
+struct Outputs {
+    uint64_t *npairs;
+    double *wsum, *rsum;   // NULL: not asked for
+    Outputs at(size_t o) const { return Outputs{npairs + o, wsum ? wsum + o : nullptr, rsum ? rsum + o : nullptr}; }
+    void zero(size_t ntot) const {
+        memset(npairs, 0, ntot * sizeof(uint64_t));
+        if (wsum) memset(wsum, 0, ntot * sizeof(double));
+        if (rsum) memset(rsum, 0, ntot * sizeof(double));
+    }
+};
+int device_outputs(size_t ntot, bool sums, Outputs &d) {
+    const size_t bytes = (sums ? 3 : 1) * ntot * 8;
+    ABACUS_TRY(g_work.out.reserve(bytes));
+    HIP_TRY(hipMemsetAsync(g_work.out.p, 0, bytes, stream()));
+    d.npairs = g_work.out.as<uint64_t>();
+    d.wsum = sums ? g_work.out.as<double>() + ntot : nullptr, d.rsum = sums ? d.wsum + ntot : nullptr;
+    return 0;
+}
+int fetch_outputs(const Outputs &h, const Outputs &d, size_t ntot) {
+    HIP_TRY(hipMemcpyAsync(h.npairs, d.npairs, ntot * 8, hipMemcpyDeviceToHost, stream()));
+    if (h.wsum) HIP_TRY(hipMemcpyAsync(h.wsum, d.wsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
+    if (h.rsum) HIP_TRY(hipMemcpyAsync(h.rsum, d.rsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
+    return 0;
+}
+
+// the sorted sets and the outputs of a run, as a kernel reads them: Args = PairArgs | LosArgs, Sums = WeightArgs | LosArgs
+template <typename Args, typename Sums>
+void fill_sets(Args &a, Sums &s, int autocorr, int nbins, int nsub, const Outputs &d) {
+    const SortedSet &S1 = g_work.S[0], &T = g_work.S[autocorr ? 0 : 1];
+    a.autocorr = autocorr, a.nbins = nbins, a.nsub = nsub;
+    a.x1 = S1.sx, a.y1 = S1.sy, a.z1 = S1.sz, a.x2 = T.sx, a.y2 = T.sy, a.z2 = T.sz;
+    a.start1 = S1.start.as<int64_t>(), a.start2 = T.start.as<int64_t>();
+    a.npairs = reinterpret_cast<unsigned long long *>(d.npairs);
+    s.w1 = S1.sw, s.w2 = T.sw, s.wsum = d.wsum, s.rsum = d.rsum;
+}
+
 }  // namespace
 
-static unsigned long long g_last_evaluated = 0;   // candidate pairs of the last call (wave-per-cell kernel only)
+static unsigned long long g_last_evaluated = 0;   // candidate pairs of the last call (not of the first two generations)
 static int g_last_cells[3] = {0, 0, 0};
 
 // weighted: also wsum (and rsum unless NULL) per bin, by pair_count_w; w1 / w2 (host memory when where = 0, else device memory)
@@ -1312,210 +1424,159 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
     if (nsub > max_hist) return fail("abacus_paircount: %d pi / mu bins exceed the LDS histogram", nsub);
     if (weighted && !wsum) return fail("abacus_paircount_weighted: wsum is NULL");
     if (weighted && autocorr && w2) return fail("abacus_paircount_weighted: w2 given for an autocorrelation (x2 is NULL)");
-    // One launch bins into at most 63 separation bins (the kernels' edge tables) and MAX_HIST counters (weighted: W_MAX_HIST
-    // entries of 20 bytes) in LDS.  More bins -
-    // Corrfunc takes any number - are counted in runs of consecutive separation bins, each a call of its own with its own,
-    // smaller reach; a pair ON an edge shared by two runs belongs to the upper bin in both ([lo, hi) bins)
-    const int run = std::min(63, max_hist / nsub);
-    if (nbins > run) {
-        for (int a = 0; a < nbins; a += run) {
-            const int n = std::min(run, nbins - a);
-            const size_t o = (size_t)a * nsub;
-            ABACUS_TRY(paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, where, boxsize, bins + a, n, pimax, npibins, mu_max,
-                                      nmubins, npairs + o, weighted, w1, w2, wsum ? wsum + o : nullptr, rsum ? rsum + o : nullptr));
-        }
-        return 0;
-    }
     if (n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("abacus_paircount: too many points");
-    const float rmax = bins[nbins];
-    for (int b = 0; b < nbins; b++)
-        if (!(bins[b + 1] > bins[b])) return fail("abacus_paircount: bin edges must increase");
-    const float reach_xy = rmax, reach_z = mode == 1 ? pimax : rmax;
-    if (reach_xy > 0.5f * boxsize || reach_z > 0.5f * boxsize)
-        return fail("abacus_paircount: maximum separation exceeds half the box (minimum image not unique)");
-    const size_t ntot = (size_t)nbins * nsub;
-    memset(npairs, 0, ntot * sizeof(uint64_t));
-    if (wsum) memset(wsum, 0, ntot * sizeof(double));
-    if (rsum) memset(rsum, 0, ntot * sizeof(double));
-    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
+    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
+    const float *const srcw[2] = {w1, w2};
+    const int64_t ns[2] = {n1, n2};
+    const int nsets = autocorr ? 1 : 2;
+    Work &W = g_work;
+    // every run stages, sorts (the grid follows the run's reach) and counts
+    return for_runs(nbins, nsub, max_hist, [&](int b0, int nb, size_t o) -> int {
+        const float *edges = bins + b0;
+        const float rmax = edges[nb];
+        for (int b = 0; b < nb; b++)
+            if (!(edges[b + 1] > edges[b])) return fail("abacus_paircount: bin edges must increase");
+        const float reach_xy = rmax, reach_z = mode == 1 ? pimax : rmax;
+        if (reach_xy > 0.5f * boxsize || reach_z > 0.5f * boxsize)
+            return fail("abacus_paircount: maximum separation exceeds half the box (minimum image not unique)");
+        const size_t ntot = (size_t)nb * nsub;
+        const Outputs host = Outputs{npairs, wsum, rsum}.at(o);
+        host.zero(ntot);
+        if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
 
-    CellGrid g;
-    g.box = boxsize;
-    g.inv_box = 1.0f / boxsize;
-    // cells of size >= reach / R: R = 2 (125-cell stencil of cells an eighth the volume: 1.7x fewer candidate pairs) when
-    // the catalogue is dense enough to keep a wave busy with a small cell, else R = 1
-    const int gen = option("pairs_gen") ? option("pairs_gen") : 3;   // comparators: 1, 2 = the older kernels
-    auto ncells = [&](float reach, int R, int cap) {
-        int nc = (int)floorf(boxsize / reach * (float)R * 0.9999f);   // cell size strictly >= reach / R
-        nc = std::min(nc, cap);
-        return nc < 3 ? 1 : nc;
-    };
-    const bool v1 = gen == 1 && !weighted;   // first-generation kernel (comparator of the tests)
-    int R = 1;
-    if (!v1 && !weighted) {   // the weighted kernel walks 27 cells of the full reach
-        const double nmax = (double)std::max(n1, autocorr ? n1 : n2);
-        const double per_cell = nmax * ((double)reach_xy / boxsize) * ((double)reach_xy / boxsize) * ((double)reach_z / boxsize);
-        if (gen >= 3 && per_cell > 12.0 && ncells(reach_xy, 2, 192) >= 5 && ncells(reach_z, 2, 192) >= 5) R = 2;
-    }
-    g.ncx = g.ncy = ncells(reach_xy, R, R == 2 ? 192 : 128);
-    g.ncz = ncells(reach_z, R, R == 2 ? 192 : 128);
-    // the cap may leave cells larger than reach / R: still correct (a cell >= reach / R is all the stencil needs)
-    const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-    const bool use3 = !v1 && !weighted && gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1;
-
-    static SortedSet S1, S2;
-    static DevBuf scratch, d_edges, d_npairs, d_work, d_flag, d_sums;
-    ABACUS_TRY(d_flag.reserve(64));
-    HIP_TRY(hipMemsetAsync(d_flag.p, 0, 64, stream()));
-    Frame *d_frame = reinterpret_cast<Frame *>(d_flag.as<int>() + 4);
-    unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_flag.as<int>() + 12);   // byte 48
-    {
-        Frame f0;
-        for (int d = 0; d < 3; d++) f0.mn[d] = 0xffffffffu, f0.mx[d] = 0u;
-        HIP_TRY(hipMemcpyAsync(d_frame, &f0, sizeof f0, hipMemcpyHostToDevice, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));   // f0 is a stack object
-    }
-    ABACUS_TRY(sort_into_cells(x1, y1, z1, w1, where, n1, g, S1, scratch, d_flag.as<int>(), d_frame));
-    if (!autocorr) ABACUS_TRY(sort_into_cells(x2, y2, z2, w2, where, n2, g, S2, scratch, d_flag.as<int>(), d_frame));
-    SortedSet &T = autocorr ? S1 : S2;
-
-    int nwork = 0, *d_wc = nullptr, *d_wo = nullptr;
-    int h_outside = 0;
-    if (v1) {   // first-generation kernel: host-built work list, one workgroup per 256 points of a non-empty cell
-        std::vector<int64_t> start1((size_t)ncell + 1);
-        HIP_TRY(hipMemcpyAsync(start1.data(), S1.start.p, (size_t)(ncell + 1) * 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        std::vector<int> wc, wo;
-        for (int64_t c = 0; c < ncell; c++)
-            for (int64_t o = 0; o < start1[c + 1] - start1[c]; o += PB) wc.push_back((int)c), wo.push_back((int)o);
-        nwork = (int)wc.size();
-        ABACUS_TRY(d_work.reserve((size_t)std::max(nwork, 1) * 8));
-        d_wc = d_work.as<int>(), d_wo = d_wc + std::max(nwork, 1);
-        HIP_TRY(hipMemcpyAsync(d_wc, wc.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
-        HIP_TRY(hipMemcpyAsync(d_wo, wo.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-    }
-
-    std::vector<float> e2(nbins + 1);
-    for (int b = 0; b <= nbins; b++) e2[b] = bins[b] * bins[b];
-    ABACUS_TRY(d_edges.reserve((nbins + 1) * 4));
-    ABACUS_TRY(d_npairs.reserve(ntot * 8));
-    HIP_TRY(hipMemcpyAsync(d_edges.p, e2.data(), (nbins + 1) * 4, hipMemcpyHostToDevice, stream()));
-    HIP_TRY(hipMemsetAsync(d_npairs.p, 0, ntot * 8, stream()));
-
-    PairArgs a;
-    a.mode = mode;
-    a.autocorr = autocorr;
-    a.in_box = !h_outside;   // (first-generation kernel does not use it)
-    a.g = g;
-    a.nbins = nbins;
-    a.nsub = nsub;
-    a.half = boxsize * 0.5f;
-    a.pimax = pimax;
-    a.dpi = npibins > 0 ? pimax / (float)npibins : 1.0f;
-    a.mu_max = mu_max;
-    a.inv_dmu = nmubins > 0 ? (float)nmubins / mu_max : 1.0f;
-    a.edges2 = d_edges.as<float>();
-    // cells of the bin table: the coarsest 2^m per octave (m = 2 .. 8) that keep the inner edges apart, at most 8192 cells
-    a.lut_sh = a.lut_off = a.lut_ncell = 0;
-    a.no_blocks = option("pairs_noblocks");
-    if (!option("pairs_nolut") && nbins >= 1 && e2[0] >= 0.f) {
-        auto fbits = [](float v) {
-            unsigned int u;
-            memcpy(&u, &v, 4);
-            return u;
+        CellGrid g;
+        g.box = boxsize;
+        g.inv_box = 1.0f / boxsize;
+        // cells of size >= reach / R: R = 2 (125-cell stencil of cells an eighth the volume: 1.7x fewer candidate pairs) when
+        // the catalogue is dense enough to keep a wave busy with a small cell, else R = 1
+        const int gen = option("pairs_gen") ? option("pairs_gen") : 3;   // comparators: 1, 2 = the older kernels
+        auto ncells = [&](float reach, int R, int cap) {
+            int nc = (int)floorf(boxsize / reach * (float)R * 0.9999f);   // cell size strictly >= reach / R
+            nc = std::min(nc, cap);
+            return nc < 3 ? 1 : nc;
         };
-        for (int m = 2; m <= 8 && !a.lut_ncell; m++) {
-            const int sh = 23 - m;
-            const unsigned int c0 = fbits(e2[0]) >> sh, c1 = fbits(e2[nbins]) >> sh;
-            if (c1 - c0 + 1 > 8192u) break;
-            bool ok = true;
-            for (int b = 1; b + 1 < nbins && ok; b++) ok = (fbits(e2[b]) >> sh) != (fbits(e2[b + 1]) >> sh);
-            for (int b = 0; b < nbins && ok; b++) ok = e2[b] < e2[b + 1];
-            if (ok) a.lut_sh = sh, a.lut_off = (int)c0, a.lut_ncell = (int)(c1 - c0 + 1);
+        const bool v1 = gen == 1 && !weighted;   // first-generation kernel (comparator of the tests)
+        int R = 1;
+        if (!v1 && !weighted) {   // the weighted kernel walks 27 cells of the full reach
+            const double nmax = (double)std::max(n1, autocorr ? n1 : n2);
+            const double per_cell = nmax * ((double)reach_xy / boxsize) * ((double)reach_xy / boxsize) * ((double)reach_z / boxsize);
+            if (gen >= 3 && per_cell > 12.0 && ncells(reach_xy, 2, 192) >= 5 && ncells(reach_z, 2, 192) >= 5) R = 2;
         }
-    }
-    a.x1 = S1.sx, a.y1 = S1.sy, a.z1 = S1.sz;
-    a.x2 = T.sx, a.y2 = T.sy, a.z2 = T.sz;
-    a.start1 = S1.start.as<int64_t>();
-    a.start2 = T.start.as<int64_t>();
-    a.npairs = d_npairs.as<unsigned long long>();
-    if (weighted) {
-        ABACUS_TRY(d_sums.reserve(2 * ntot * 8));
-        HIP_TRY(hipMemsetAsync(d_sums.p, 0, 2 * ntot * 8, stream()));
+        g.ncx = g.ncy = ncells(reach_xy, R, R == 2 ? 192 : 128);
+        g.ncz = ncells(reach_z, R, R == 2 ? 192 : 128);
+        // the cap may leave cells larger than reach / R: still correct (a cell >= reach / R is all the stencil needs)
+        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
+        const bool use3 = !v1 && !weighted && gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1;
+
+        Flags fl;
+        ABACUS_TRY(W.flags(fl));
+        for (int k = 0; k < nsets; k++) {
+            Columns c;
+            ABACUS_TRY(stage_columns("pair_cast", src[k], srcw[k], where, ns[k], nullptr, W.cols[k], W.wts[k], c));
+            ABACUS_TRY(sort_into_cells(c, ns[k], FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[k], W.scratch));
+        }
+        const SortedSet &S1 = W.S[0], &T = W.S[nsets - 1];
+
+        int nwork = 0, *d_wc = nullptr, *d_wo = nullptr;
+        if (v1) {   // first-generation kernel: host-built work list, one workgroup per 256 points of a non-empty cell
+            std::vector<int64_t> start1((size_t)ncell + 1);
+            HIP_TRY(hipMemcpyAsync(start1.data(), S1.start.p, (size_t)(ncell + 1) * 8, hipMemcpyDeviceToHost, stream()));
+            HIP_TRY(hipStreamSynchronize(stream()));
+            std::vector<int> wc, wo;
+            for (int64_t c = 0; c < ncell; c++)
+                for (int64_t off = 0; off < start1[c + 1] - start1[c]; off += PB) wc.push_back((int)c), wo.push_back((int)off);
+            nwork = (int)wc.size();
+            ABACUS_TRY(W.list.reserve((size_t)std::max(nwork, 1) * 8));
+            d_wc = W.list.as<int>(), d_wo = d_wc + std::max(nwork, 1);
+            HIP_TRY(hipMemcpyAsync(d_wc, wc.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
+            HIP_TRY(hipMemcpyAsync(d_wo, wo.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
+            HIP_TRY(hipStreamSynchronize(stream()));
+        }
+
+        std::vector<float> e2;
+        ABACUS_TRY(upload_edges(edges, nb, e2));
+        Outputs dev;
+        ABACUS_TRY(device_outputs(ntot, weighted != 0, dev));
+        PairArgs a;
         WeightArgs wa;
-        wa.w1 = S1.sw, wa.w2 = T.sw;
-        wa.wsum = d_sums.as<double>(), wa.rsum = wa.wsum + ntot;
-        int dev = 0, ncu = 256, per_cu = 2;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        const size_t hist_bytes = ntot * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
-        const bool rs = rsum != nullptr;
-#define PW_FN(M) (rs ? (const void *)pair_count_w<M, true> : (const void *)pair_count_w<M, false>)
-        const void *fn = mode == 0 ? PW_FN(0) : (mode == 1 ? PW_FN(1) : PW_FN(2));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, PB, hist_bytes));
-        const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * std::max(per_cu, 1)));
-#define PW_RUN(M)                                                                                                               \
-    do {                                                                                                                        \
-        if (rs) ABACUS_LAUNCH("pair_count_w", (pair_count_w<M, true>), grid, dim3(PB), hist_bytes, a, wa, (int)ncell, d_eval);   \
-        else ABACUS_LAUNCH("pair_count_w", (pair_count_w<M, false>), grid, dim3(PB), hist_bytes, a, wa, (int)ncell, d_eval);     \
-    } while (0)
-        if (mode == 0) PW_RUN(0);
-        else if (mode == 1) PW_RUN(1);
-        else PW_RUN(2);
-#undef PW_RUN
-#undef PW_FN
-        HIP_TRY(hipMemcpyAsync(wsum, d_sums.p, ntot * 8, hipMemcpyDeviceToHost, stream()));
-        if (rsum) HIP_TRY(hipMemcpyAsync(rsum, d_sums.as<double>() + ntot, ntot * 8, hipMemcpyDeviceToHost, stream()));
-    } else if (v1) {
-        if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
-    } else if (use3) {
-        int dev = 0, ncu = 256;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        const bool lut = a.lut_ncell > 0;
-        const size_t hist_bytes = ((ntot + 1) & ~(size_t)1) * sizeof(unsigned int) + (size_t)a.lut_ncell * sizeof(uint2);
-        int per_cu = 4;   // persistent waves: as many workgroups as are resident at once
-#define P3_FN(M) (lut ? (const void *)pair_count3<M, true> : (const void *)pair_count3<M, false>)
-        const void *fn = mode == 0 ? P3_FN(0) : (mode == 1 ? P3_FN(1) : P3_FN(2));
-        if (hist_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, P3_WAVES * 64, hist_bytes));
-        const dim3 grid((unsigned int)std::min<int64_t>(ceil_div(ncell, P3_WAVES), (int64_t)ncu * std::max(per_cu, 1)));
-#define P3_RUN(M)                                                                                                                  \
-    do {                                                                                                                           \
-        if (lut) ABACUS_LAUNCH("pair_count", (pair_count3<M, true>), grid, dim3(P3_WAVES * 64), hist_bytes, a, d_frame, (int)ncell, R, d_eval); \
-        else ABACUS_LAUNCH("pair_count", (pair_count3<M, false>), grid, dim3(P3_WAVES * 64), hist_bytes, a, d_frame, (int)ncell, R, d_eval); \
-    } while (0)
-        if (mode == 0) P3_RUN(0);
-        else if (mode == 1) P3_RUN(1);
-        else P3_RUN(2);
-#undef P3_RUN
-#undef P3_FN
-    } else {
-        int dev = 0, ncu = 256;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * 8));
-        const size_t hist_bytes = ntot * sizeof(unsigned int);
-        const int *flag = d_flag.as<int>();
-        // a few points per cell: stage all neighbour cells together (one round per slice instead of 27)
-        const bool agg = (double)T.n / (double)ncell < 12.0;
-#define LAUNCH_PC(M)                                                                                         \
-    do {                                                                                                     \
-        if (agg) ABACUS_LAUNCH("pair_count", (pair_count2<M, true>), grid, dim3(PB), hist_bytes, a, flag, (int)ncell);  \
-        else ABACUS_LAUNCH("pair_count", (pair_count2<M, false>), grid, dim3(PB), hist_bytes, a, flag, (int)ncell); \
-    } while (0)
-        if (mode == 0) LAUNCH_PC(0);
-        else if (mode == 1) LAUNCH_PC(1);
-        else LAUNCH_PC(2);
-#undef LAUNCH_PC
-    }
-    HIP_TRY(hipMemcpyAsync(npairs, d_npairs.p, ntot * 8, hipMemcpyDeviceToHost, stream()));
-    g_last_evaluated = 0;
-    HIP_TRY(hipMemcpyAsync(&g_last_evaluated, d_eval, 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
-    g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = use3 ? R : 0;
-    return 0;
+        fill_sets(a, wa, autocorr, nb, nsub, dev);
+        a.mode = mode;
+        a.in_box = 1;   // (no kernel reads it: pair_count2 takes the device flag)
+        a.g = g;
+        a.half = boxsize * 0.5f;
+        a.pimax = pimax;
+        a.dpi = npibins > 0 ? pimax / (float)npibins : 1.0f;
+        a.mu_max = mu_max;
+        a.inv_dmu = nmubins > 0 ? (float)nmubins / mu_max : 1.0f;
+        a.edges2 = W.edges.as<float>();
+        // cells of the bin table: the coarsest 2^m per octave (m = 2 .. 8) that keep the inner edges apart, at most 8192 cells
+        a.lut_sh = a.lut_off = a.lut_ncell = 0;
+        a.no_blocks = option("pairs_noblocks");
+        if (!option("pairs_nolut") && e2[0] >= 0.f) {
+            auto fbits = [](float v) {
+                unsigned int u;
+                memcpy(&u, &v, 4);
+                return u;
+            };
+            for (int m = 2; m <= 8 && !a.lut_ncell; m++) {
+                const int sh = 23 - m;
+                const unsigned int c0 = fbits(e2[0]) >> sh, c1 = fbits(e2[nb]) >> sh;
+                if (c1 - c0 + 1 > 8192u) break;
+                bool ok = true;
+                for (int b = 1; b + 1 < nb && ok; b++) ok = (fbits(e2[b]) >> sh) != (fbits(e2[b + 1]) >> sh);
+                for (int b = 0; b < nb && ok; b++) ok = e2[b] < e2[b + 1];
+                if (ok) a.lut_sh = sh, a.lut_off = (int)c0, a.lut_ncell = (int)(c1 - c0 + 1);
+            }
+        }
+        if (weighted) {
+            const size_t hist_bytes = ntot * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
+            ABACUS_TRY(with_mode(mode, [&](auto M) {
+                return with_flag(rsum != nullptr, [&](auto RS) -> int {
+                    const auto kernel = pair_count_w<decltype(M)::value, decltype(RS)::value>;
+                    dim3 grid;
+                    ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+                    ABACUS_LAUNCH("pair_count_w", kernel, grid, dim3(PB), hist_bytes, a, wa, (int)ncell, fl.evaluated);
+                    return 0;
+                });
+            }));
+        } else if (v1) {
+            if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
+        } else if (use3) {
+            const bool lut = a.lut_ncell > 0;
+            const size_t hist_bytes = ((ntot + 1) & ~(size_t)1) * sizeof(unsigned int) + (size_t)a.lut_ncell * sizeof(uint2);
+            ABACUS_TRY(with_mode(mode, [&](auto M) {
+                return with_flag(lut, [&](auto LUT) -> int {
+                    const auto kernel = pair_count3<decltype(M)::value, decltype(LUT)::value>;
+                    if (hist_bytes > 48 * 1024)
+                        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
+                    dim3 grid;   // persistent waves: as many workgroups as are resident at once
+                    ABACUS_TRY(resident_grid(kernel, P3_WAVES * 64, hist_bytes, ceil_div(ncell, P3_WAVES), grid));
+                    ABACUS_LAUNCH("pair_count", kernel, grid, dim3(P3_WAVES * 64), hist_bytes, a, fl.frame, (int)ncell, R, fl.evaluated);
+                    return 0;
+                });
+            }));
+        } else {
+            int ncu = 256;
+            ABACUS_TRY(cu_count(ncu));
+            const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * 8));
+            const size_t hist_bytes = ntot * sizeof(unsigned int);
+            // a few points per cell: stage all neighbour cells together (one round per slice instead of 27)
+            const bool agg = (double)T.n / (double)ncell < 12.0;
+            ABACUS_TRY(with_mode(mode, [&](auto M) {
+                return with_flag(agg, [&](auto AGG) -> int {
+                    ABACUS_LAUNCH("pair_count", (pair_count2<decltype(M)::value, decltype(AGG)::value>), grid, dim3(PB), hist_bytes, a,
+                                  (const int *)fl.outside, (int)ncell);
+                    return 0;
+                });
+            }));
+        }
+        ABACUS_TRY(fetch_outputs(host, dev, ntot));
+        g_last_evaluated = 0;
+        HIP_TRY(hipMemcpyAsync(&g_last_evaluated, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = use3 ? R : 0;
+        return 0;
+    });
 }
 
 extern "C" int abacus_paircount(int mode, const float *x1, const float *y1, const float *z1, int64_t n1,
@@ -1570,17 +1631,6 @@ static float funkey_host(unsigned int k) {
     return v;
 }
 
-template <int MODE, bool W, bool R>
-static int los_launch(const LosArgs &a, int64_t ncell, size_t hist_bytes, unsigned long long *d_eval) {
-    int dev = 0, ncu = 256, per_cu = 2;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)pair_count_los<MODE, W, R>, PB, hist_bytes));
-    const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * std::max(per_cu, 1)));
-    ABACUS_LAUNCH("pair_count_los", (pair_count_los<MODE, W, R>), grid, dim3(PB), hist_bytes, a, (int)ncell, d_eval);
-    return 0;
-}
-
 // where = 0: host float32 arrays (and host weights); 1: device float32; 2: device float64 (device weights)
 static int paircount_los_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
                               const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int where,
@@ -1605,64 +1655,29 @@ static int paircount_los_impl(const char *who, int mode, const void *x1, const v
         if (!std::isfinite(origin[d])) return fail("%s: origin must be finite", who);
     ABACUS_ENTER();
     const bool weighted = wsum != nullptr, rs = weighted && rsum != nullptr;   // wsum == NULL: integer counts only
-    const size_t nall = (size_t)nbins * nsub;
-    memset(npairs, 0, nall * sizeof(uint64_t));
-    if (wsum) memset(wsum, 0, nall * sizeof(double));
-    if (rs) memset(rsum, 0, nall * sizeof(double));
+    const Outputs result{npairs, wsum, rs ? rsum : nullptr};
+    result.zero((size_t)nbins * nsub);
     g_last_evaluated = 0;
     g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
     g_los_cells[0] = g_los_cells[1] = g_los_cells[2] = 0;
     if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
 
-    // observer-centred float32 columns of both sets in HBM
-    static SortedSet S1, S2;
-    static DevBuf cols[2], wts[2], scratch, d_edges, d_out, d_flag;
-    const float *px[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}, *pw[2] = {nullptr, nullptr};
-    const void *src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
-    const float *srcw[2] = {weighted ? w1 : nullptr, weighted ? w2 : nullptr};
-    const int64_t ns[2] = {n1, autocorr ? 0 : n2};
-    const bool shifted = origin[0] != 0.0 || origin[1] != 0.0 || origin[2] != 0.0;
-    for (int k = 0; k < (autocorr ? 1 : 2); k++) {
-        const int64_t n = ns[k];
-        const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 2048);
-        if (where == 1 && !shifted) {   // caller's device arrays, read in place
-            for (int d = 0; d < 3; d++) px[k][d] = (const float *)src[k][d];
-        } else {
-            ABACUS_TRY(cols[k].reserve(3 * (size_t)n * 4));
-            for (int d = 0; d < 3; d++) {
-                float *dst = cols[k].as<float>() + (size_t)d * n;
-                px[k][d] = dst;
-                if (where == 2) {
-                    ABACUS_LAUNCH("pair_los_centre", los_centre<double>, dim3(nblk), dim3(256), 0, (const double *)src[k][d], origin[d], dst, n);
-                    continue;
-                }
-                const float *from = (const float *)src[k][d];
-                if (where == 0) {
-                    HIP_TRY(hipMemcpyAsync(dst, from, (size_t)n * 4, hipMemcpyHostToDevice, stream()));
-                    from = dst;
-                }
-                if (shifted) ABACUS_LAUNCH("pair_los_centre", los_centre<float>, dim3(nblk), dim3(256), 0, from, (float)origin[d], dst, n);
-            }
-        }
-        pw[k] = srcw[k];
-        if (srcw[k] && where == 0) {
-            ABACUS_TRY(wts[k].reserve((size_t)n * 4));
-            HIP_TRY(hipMemcpyAsync(wts[k].p, srcw[k], (size_t)n * 4, hipMemcpyHostToDevice, stream()));
-            pw[k] = wts[k].as<float>();
-        }
-    }
-    // bounding box of both sets: one reduction, 24 bytes to the host
-    ABACUS_TRY(d_flag.reserve(64));
-    Frame *d_frame = d_flag.as<Frame>();
-    unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_flag.as<char>() + 32);
-    Frame fr;
-    for (int d = 0; d < 3; d++) fr.mn[d] = 0xffffffffu, fr.mx[d] = 0u;
-    HIP_TRY(hipMemsetAsync(d_flag.p, 0, 64, stream()));
-    HIP_TRY(hipMemcpyAsync(d_frame, &fr, sizeof fr, hipMemcpyHostToDevice, stream()));
-    for (int k = 0; k < (autocorr ? 1 : 2); k++)
+    // observer-centred float32 columns of both sets in HBM, and their bounding box: one reduction, 24 bytes to the host
+    Work &W = g_work;
+    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
+    const float *const srcw[2] = {weighted ? w1 : nullptr, weighted ? w2 : nullptr};
+    const int64_t ns[2] = {n1, n2};
+    const int nsets = autocorr ? 1 : 2;
+    Columns cols[2];
+    Flags fl;
+    ABACUS_TRY(W.flags(fl));
+    for (int k = 0; k < nsets; k++) {
+        ABACUS_TRY(stage_columns("pair_los_centre", src[k], srcw[k], where, ns[k], origin, W.cols[k], W.wts[k], cols[k]));
         ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
-                      px[k][0], px[k][1], px[k][2], ns[k], d_frame);
-    HIP_TRY(hipMemcpyAsync(&fr, d_frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
+                      cols[k].x[0], cols[k].x[1], cols[k].x[2], ns[k], fl.frame);
+    }
+    Frame fr;
+    HIP_TRY(hipMemcpyAsync(&fr, fl.frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
     HIP_TRY(hipStreamSynchronize(stream()));
     double lo[3], extent[3];
     for (int d = 0; d < 3; d++) {
@@ -1671,43 +1686,30 @@ static int paircount_los_impl(const char *who, int mode, const void *x1, const v
         if (!(extent[d] >= 0.0) || !std::isfinite(extent[d]) || !std::isfinite(lo[d])) return fail("%s: coordinates are not finite", who);
     }
 
-    // One launch bins into at most 63 separation bins and W_MAX_HIST LDS entries; more are counted in runs of consecutive
-    // separation bins, each on a grid of its own, smaller reach (a pair ON an edge shared by two runs belongs to the upper bin
-    // in both).  The columns above and the bounding box serve every run.
-    const int run = std::min(63, W_MAX_HIST / nsub);
+    // the columns above and the bounding box serve every run; a run sorts them into a grid of its own reach and counts
     unsigned long long evaluated = 0;
-    for (int b0 = 0; b0 < nbins; b0 += run) {
-        const int nb = std::min(run, nbins - b0);
-        const float *edges = bins + b0;
-        const size_t ntot = (size_t)nb * nsub, o = (size_t)b0 * nsub;
-        std::vector<double> e2(nb + 1);
-        for (int b = 0; b <= nb; b++) e2[b] = (double)edges[b] * (double)edges[b];
+    ABACUS_TRY(for_runs(nbins, nsub, W_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
+        const size_t ntot = (size_t)nb * nsub;
+        std::vector<double> e2;
+        ABACUS_TRY(upload_edges(bins + b0, nb, e2));
         const double reach2 = mode == 1 ? e2[nb] + (double)pimax * (double)pimax : e2[nb];
         const double reach = std::nextafter(std::sqrt(reach2), HUGE_VAL);   // rounded up
         OpenGrid og;
-        CellGrid g;
         for (int d = 0; d < 3; d++) {
             const double fit = std::floor(extent[d] / (reach * 1.0001));    // cell side >= 1.0001 reach (see OpenGrid)
             og.nc[d] = (int)std::min(128.0, std::max(1.0, fit));
             og.lo[d] = (float)lo[d];                                         // exact: a float32 coordinate
             og.inv[d] = extent[d] > 0.0 ? (float)((double)og.nc[d] / extent[d]) : 0.f;
         }
-        g.ncx = og.nc[0], g.ncy = og.nc[1], g.ncz = og.nc[2];
-        g.box = g.inv_box = 0.f;   // (the periodic members are not read on the open path)
-        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-        ABACUS_TRY(sort_into_cells(px[0][0], px[0][1], px[0][2], pw[0], 1, n1, g, S1, scratch, nullptr, nullptr, &og));
-        if (!autocorr) ABACUS_TRY(sort_into_cells(px[1][0], px[1][1], px[1][2], pw[1], 1, n2, g, S2, scratch, nullptr, nullptr, &og));
-        SortedSet &T = autocorr ? S1 : S2;
+        const int64_t ncell = (int64_t)og.nc[0] * og.nc[1] * og.nc[2];
+        for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells(cols[k], ns[k], og, ncell, W.S[k], W.scratch));
 
-        ABACUS_TRY(d_edges.reserve((size_t)(nb + 1) * 8));
-        ABACUS_TRY(d_out.reserve(3 * ntot * 8));
-        HIP_TRY(hipMemcpyAsync(d_edges.p, e2.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, stream()));
-        HIP_TRY(hipMemsetAsync(d_out.p, 0, 3 * ntot * 8, stream()));
-        HIP_TRY(hipMemsetAsync(d_eval, 0, 8, stream()));
+        Outputs dev;
+        ABACUS_TRY(device_outputs(ntot, true, dev));
+        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
         LosArgs a;
-        a.autocorr = autocorr;
+        fill_sets(a, a, autocorr, nb, nsub, dev);
         for (int d = 0; d < 3; d++) a.nc[d] = og.nc[d];
-        a.nbins = nb, a.nsub = nsub;
         // the pre-test's thresholds (derivation at the kernel): rounded away from the accepted range
         const double hi_d = reach2 * (1.0 + 0x1p-20), lo_d = e2[0] * (1.0 - 0x1p-20);
         float hi_f = (float)hi_d, lo_f = (float)lo_d;
@@ -1719,33 +1721,29 @@ static int paircount_los_impl(const char *who, int mode, const void *x1, const v
         a.dpi = npibins > 0 ? (double)pimax / npibins : 1.0;
         a.mu_max = (double)mu_max;
         a.inv_dmu = nmubins > 0 ? nmubins / (double)mu_max : 1.0;
-        a.edges2 = d_edges.as<double>();
-        a.x1 = S1.sx, a.y1 = S1.sy, a.z1 = S1.sz, a.w1 = S1.sw;
-        a.x2 = T.sx, a.y2 = T.sy, a.z2 = T.sz, a.w2 = T.sw;
-        a.start1 = S1.start.as<int64_t>(), a.start2 = T.start.as<int64_t>();
-        a.npairs = d_out.as<unsigned long long>();
-        a.wsum = d_out.as<double>() + ntot, a.rsum = a.wsum + ntot;
+        a.edges2 = W.edges.as<double>();
         const size_t hist_bytes = ntot * (4 + (weighted ? 8 : 0) + (rs ? 8 : 0));
-#define LOS_RUN(M)                                                                           \
-    do {                                                                                     \
-        if (rs) ABACUS_TRY((los_launch<M, true, true>(a, ncell, hist_bytes, d_eval)));       \
-        else if (weighted) ABACUS_TRY((los_launch<M, true, false>(a, ncell, hist_bytes, d_eval))); \
-        else ABACUS_TRY((los_launch<M, false, false>(a, ncell, hist_bytes, d_eval)));        \
-    } while (0)
-        if (mode == 0) LOS_RUN(0);
-        else if (mode == 1) LOS_RUN(1);
-        else LOS_RUN(2);
-#undef LOS_RUN
+        auto launch = [&](auto M, auto WT, auto RS) -> int {
+            const auto kernel = pair_count_los<decltype(M)::value, decltype(WT)::value, decltype(RS)::value>;
+            dim3 grid;
+            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+            ABACUS_LAUNCH("pair_count_los", kernel, grid, dim3(PB), hist_bytes, a, (int)ncell, fl.evaluated);
+            return 0;
+        };
+        ABACUS_TRY(with_mode(mode, [&](auto M) {
+            if (rs) return launch(M, std::true_type(), std::true_type());
+            if (weighted) return launch(M, std::true_type(), std::false_type());
+            return launch(M, std::false_type(), std::false_type());
+        }));
         unsigned long long ev = 0;
-        HIP_TRY(hipMemcpyAsync(npairs + o, a.npairs, ntot * 8, hipMemcpyDeviceToHost, stream()));
-        if (weighted) HIP_TRY(hipMemcpyAsync(wsum + o, a.wsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
-        if (rs) HIP_TRY(hipMemcpyAsync(rsum + o, a.rsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipMemcpyAsync(&ev, d_eval, 8, hipMemcpyDeviceToHost, stream()));
+        ABACUS_TRY(fetch_outputs(result.at(o), dev, ntot));
+        HIP_TRY(hipMemcpyAsync(&ev, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
         HIP_TRY(hipStreamSynchronize(stream()));
         evaluated += ev;
-        g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = 0;
+        g_last_cells[0] = og.nc[0], g_last_cells[1] = og.nc[2], g_last_cells[2] = 0;
         for (int d = 0; d < 3; d++) g_los_cells[d] = og.nc[d];
-    }
+        return 0;
+    }));
     g_last_evaluated = evaluated;
     return 0;
 }
