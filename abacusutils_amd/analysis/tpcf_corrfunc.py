@@ -442,12 +442,21 @@ def _ls_weightsum(mode, a, b, bins, geom):
 
 class LCRandoms(_LCSample):
     """The randoms of a light-cone catalogue for `calc_xirppi_lc` / `calc_wp_lc` / `calc_multipole_lc`: uploaded once,
-    and RR - the most expensive term - counted once per (mode, bins, pi / mu binning) and kept."""
+    and RR - the most expensive term - counted once per (mode, bins, pi / mu binning) and kept.  For `analysis.lc_power` (`fkp_field`,
+    `calc_power_lc`) the same object keeps the randoms' mesh, deposited once per (nmesh, box, cloud), and takes `nbar`: the number
+    density of the random catalogue at each random (a host array or a `DeviceArray`, e.g. from `lc_power.radial_nbar`), which
+    normalises the power spectrum."""
 
-    def __init__(self, x, y, z, w=None, origin=(0.0, 0.0, 0.0)):
+    def __init__(self, x, y, z, w=None, origin=(0.0, 0.0, 0.0), nbar=None):
         super().__init__(x, y, z, w, origin)
         self._rr = {}
         self.rr_counted = 0      # RR runs so far (a cache hit does not count)
+        if nbar is not None and tuple(nbar.shape if isinstance(nbar, _lib.DeviceArray) else np.shape(nbar)) != (self.n,):
+            raise ValueError(f'nbar must have shape ({self.n},)')
+        self.nbar = nbar
+        self._mesh = {}          # lc_power: (nmesh, box side, corner, cloud) -> the randoms' padded mesh in HBM
+        self.mesh_built = 0      # deposits of the randoms so far (a cache hit does not count)
+        self._w2n = None         # lc_power: sum w^2 nbar in float64
 
     def rr(self, mode, bins, geom):
         key = (int(mode), _f4(bins).tobytes(), tuple(sorted(geom.items())))

@@ -606,9 +606,29 @@ class AbacusHOD:
         return self._pairs(mock_dict, fn, weights)
 
     def compute_power(self, mock_dict, nbins_k, nbins_mu, k_hMpc_max, logk, poles=[], paste='TSC', num_cells=550,
-                      compensated=False, interlaced=False):
+                      compensated=False, interlaced=False, randoms=None):
         r"""P(k, mu) and/or P_l(k) for every tracer pair (:1338-1472).  Returned keys: '{a}_{b}', '..._modes',
-        '..._ell', '..._ell_modes', 'k_binc', 'mu_binc'."""
+        '..._ell', '..._ell_modes', 'k_binc', 'mu_binc'.
+
+        randoms: None (the periodic box, above), or an `LCRandoms` with `nbar=` on a light-cone object - the FKP / Yamamoto
+        multipoles of `analysis.lc_power.calc_power_lc` seen from the light cone's origin, every tracer's F_0 and F_l built once
+        from its columns in HBM.  Returned keys then: '{a}_{b}_ell' (len(poles), nbins_k), '{a}_{b}_ell_modes' and 'k_binc' only:
+        there is no P(k, mu) with a line of sight that varies across the catalogue, `nbins_mu` is ignored, `interlaced` must be
+        false, `poles` is a non-empty subset of (0, 2, 4) and `num_cells` even.  A 'w' column weights its tracer."""
+        if randoms is not None:
+            from ..analysis.lc_power import calc_power_lc_multi
+            if interlaced:
+                raise NotImplementedError('randoms=: the light-cone spectra are not interlaced')
+            origin = self._lc_origin()
+            samples = {tr: (*self._xyz(mock_dict, tr), mock_dict[tr].get('w', None)) for tr in mock_dict.keys()}
+            tabs, k_mid = calc_power_lc_multi(samples, randoms, nbins_k, num_cells, poles, k_max=k_hMpc_max, logk=logk, paste=paste,
+                                              compensated=compensated, origin=origin)
+            clustering = {'k_binc': k_mid}
+            for (tr1, tr2), power in tabs.items():
+                for a, b in ((tr1, tr2), (tr2, tr1)):
+                    clustering[f'{a}_{b}_ell'] = power['poles']
+                    clustering[f'{a}_{b}_ell_modes'] = power['N_mode']
+            return clustering
         Lbox = self.lbox
         clustering = {}
         # the untouched result of the latest run_hod, unweighted: every tracer's field from its columns in HBM, deposited

@@ -823,6 +823,47 @@ int abacus_recon_displacement_dev(const void *delta_padded, int normalised, int 
 int abacus_recon_shift_dev(const float *pos, int64_t np, double offset, const float *psi_x, const float *psi_y, const float *psi_z, int n,
                            double Lbox, int paste, double los_factor, float *out);
 
+/* ---------------------------------------------------------------- light-cone power spectrum --------------- */
+/*
+ * FKP field and Yamamoto multipoles of a light-cone catalogue on DEVICE pointers (csrc/zcv.hip, behind the recon section; Python:
+ * analysis/lc_power.py); every call enqueues on the library stream.  replaces: nothing in the reference, whose power spectra assume a
+ * periodic box and a global line of sight.  Estimator: Feldman, Kaiser & Peacock 1994 with the end-point line of sight of Yamamoto
+ * et al. 2006, through the spherical-harmonic decomposition of Hand et al. 2017 (1 + 5 + 9 transforms for l = 0, 2, 4).
+ *   F = D - alpha R: the raw weighted deposits (weight per cell, no normalisation) of data and randoms, columns centred on the
+ *   observer, in a box of side Lbox with its corner at `corner`; cell i is centred at corner + i Lbox / n.
+ *   F_0(k) = R2C(F) (a bare sum over cells);  F_l(k) = sum_m S_lm(k^) R2C[S_lm(r^_cell) F](k),  l = 2, 4,
+ * with S_lm the real harmonics scaled so that sum_m S_lm(a) S_lm(b) = L_l(a . b): polynomials in the unit vector, float32, listed in
+ * tests/lc_power_statement.py.  S_lm = 0 for l > 0 in the cell with |r| = 0 and at k = 0.  k^ is formed from the mode numbers (index i
+ * -> i below n/2, i - n from n/2 on for x and y, 0 .. n/2 on z).  No inverse transform follows: the Nyquist planes are left as
+ * computed.  "Padded meshes" as in the recon section: n * n rows of abacus_slab_pitch(n) floats, abacus_zcv_spectrum_bytes(n) bytes;
+ * a padded spectrum is the same memory after the in-place R2C.  n even, 2 .. 32767.  The spectra are binned by abacus_zcv_power_pair.
+ */
+/* fails, naming the largest mesh that fits, when `nmeshes` more padded meshes (F, F_0, the requested F_l, one work mesh, the randoms'
+ * mesh where it is not cached yet) + the packed copies, weights and deposit lists of np points do not fit the free device memory */
+int abacus_lc_check_memory(int n, int nmeshes, int64_t np);
+/* lohi_host[0..2] = the minima of the three float32 device columns, [3..5] the maxima: a two-stage reduction without atomics.  An
+ * axis with a coordinate that is not finite reports (-inf, +inf). */
+int abacus_lc_extent_dev(const float *x, const float *y, const float *z, int64_t np, float *lohi_host);
+/* three float32 device columns -> out (np, 3) float32 = column - f32(corner[axis]), one float32 subtraction: the copy a deposit works on */
+int abacus_lc_pack_dev(const float *x, const float *y, const float *z, int64_t np, const double *corner, float *out);
+/* mesh_padded = the raw deposit of the np points pos (np, 3) float32 in [0, Lbox) with the weights w (float32, NULL: unit weights) and
+ * the cloud of `paste` (0: TSC, 1: CIC), every cell written (no separate zeroing), tile sums in float64.  The deposit is periodic:
+ * the caller keeps the points two cells away from the faces.  pos may be sorted in place. */
+int abacus_lc_deposit_dev(float *pos, int64_t np, const float *w, double Lbox, int n, int paste, float *mesh_padded);
+/* dst_padded += f32(a) src_padded over whole padded meshes (F = D + (-alpha) R: one deposit and this): 8 B read, 4 B written per cell */
+int abacus_lc_axpy_dev(float *dst_padded, const float *src_padded, int n, double a);
+/* F_padded (not modified) -> out_padded = F_l(k), l = ell in {0, 2, 4}.  ell = 0: a copy and one R2C.  ell > 0, for each of the 2 ell + 1
+ * m: lc_ylm_mult (work = S_lm(r^_cell) F, one (i, j) row per wave, 4 B read + 4 B written per cell), R2C of the work mesh in place,
+ * lc_ylm_accum (out (+)= S_lm(k^) work, the first m writes: 8 B read + 8 B written per mode, 8 B more read from the second m on).
+ * corner[3]: the box corner relative to the observer, used as float32.  work_padded: a padded mesh (unused for ell = 0).  The three
+ * buffers must differ.  The transform may take one padded work mesh from the scratch pool or a hipFFT work area. */
+int abacus_lc_multipole_dev(const float *F_padded, int n, double Lbox, const double *corner, int ell, float *work_padded, void *out_padded);
+/* spec_padded *= 1 / ((W[a] W[b]) W[c]) in float32, W_host the n float32 values of get_W_compensated: the compensation of the cloud */
+int abacus_lc_compensate_dev(void *spec_padded, int n, const float *W_host);
+/* out_host[0] = sum_i w_i^2 nbar_i in float64 (w float32 device weights, NULL: unit weights; nbar a device column, float64 if nbar_f64
+ * else float32): per-workgroup partial sums, then one workgroup over them, both in a fixed order - the same bits on every run */
+int abacus_lc_sum_w2n_dev(const float *w, const void *nbar, int nbar_f64, int64_t np, double *out_host);
+
 /* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
  * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
  * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
