@@ -24,6 +24,8 @@
 //   weighted and light cone   one walk in two bodies: pair_count_w (periodic, float32), pair_count_los (open grid, float64)
 //   host side                 one set of work buffers, stage_columns, sort_into_cells, launch helpers, the two drivers
 //                             paircount_impl and paircount_los_impl over one run loop, the C ABI
+//   jackknife                 pair_count_jk / pair_count_los_jk (the two walks with per-region histograms), the label-aware
+//                             sort, the drivers paircount_jk_impl / paircount_los_jk_impl, abacus_jk_box_labels_dev
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -1782,6 +1784,870 @@ extern "C" int abacus_paircount_los_centre(const void *src, int pos_dtype, int64
     const dim3 grid((unsigned int)std::min<int64_t>(ceil_div(n, 256), 2048));
     if (pos_dtype == ABACUS_F64) ABACUS_LAUNCH("pair_los_centre", los_centre<double>, grid, dim3(256), 0, (const double *)src, origin, dst, n);
     else ABACUS_LAUNCH("pair_los_centre", los_centre<float>, grid, dim3(256), 0, (const float *)src, (float)origin, dst, n);
+    HIP_TRY(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ jackknife pair counts ----
+// Per-region pair counts in ONE walk (abacus_paircount_jk, abacus_paircount_los_jk): every point carries an int32 label in
+// [0, nreg) and per (bin, sub-bin) q and region k
+//   first[k][q] = pairs of q whose point of set 1 has label k,     both[k][q] = those whose point of set 2 has label k too,
+// as integer counts and as sums of w_i w_j (float64 products and sums, like wsum above).  total[q] = sum_k first[k][q] is the
+// parent counter's result; there are no separation sums here.  second[k][q] (the point of set 2 has label k) is no output:
+// membership is symmetric under exchange of the two points in every mode of both families - d -> -d negates exactly (the
+// minimum image adds -+L to -+d), so r^2, |dz|, mu, and on the light cone l = p_i + p_j, |t| and pi^2 are bit-equal - hence
+// second of (1, 2) is first of (2, 1): the autocorrelation has second = first, a cross count calls again with the sets
+// exchanged.  The expressions that decide membership and bin are those of pair_count_w / pair_count_los, untouched.
+//   * The labels ride through the cell sort (one radix sort of the key cell << bits | label - the stable label pass in front
+//     of the cell pass, fused), so a cell's slice is a few runs of constant label; with sub-box regions normally one.
+//   * A primary slice ends with its label run: ni = min(PB, end of run - i0), found in the slice's labels in LDS.
+//   * Two LDS histograms of nh entries (first | both, each a float64 sum and a u32 count: 24 bytes per entry, JK_MAX_HIST
+//     entries per launch; the unweighted light-cone count drops the sums) accumulate ONE label.  They are flushed - non-zero
+//     entries, global atomics to out[label][q] - when the next run's label differs, across cells too, and at the end; a
+//     workgroup walks a CONTIGUOUS range of cells (an equal share of the points), so that consecutive cells of one sub-box
+//     flush once.
+//   * MODE 0 keeps the last bin of both histograms in registers, per run.
+// The candidate count is the parent's: splitting slices into runs leaves sum ni M unchanged.
+namespace {
+
+constexpr int JK_MAX_HIST = 2048;
+constexpr int JK_MAX_REG = 65535;
+constexpr int64_t JK_MAX_OUT = (int64_t)1 << 24;
+
+struct JkOut {   // four arrays [nreg][stride]; a run's kernel writes columns 0 .. nh of every row (the pointers are offset)
+    unsigned long long *nfirst, *nboth;
+    double *wfirst, *wboth;   // not read by an unweighted kernel
+    size_t stride;
+    unsigned long long *flushes;
+};
+
+template <bool WEIGHTED>
+struct JkHist {
+    double *wf, *wb;
+    unsigned int *cf, *cb;
+    int nh;
+    __device__ __forceinline__ JkHist(double *base, int n) : nh(n) {
+        wf = base, wb = base + (WEIGHTED ? n : 0);
+        cf = reinterpret_cast<unsigned int *>(wb + (WEIGHTED ? n : 0)), cb = cf + n;
+    }
+    __device__ __forceinline__ void clear() const {
+        for (int q = threadIdx.x; q < nh; q += PB) {
+            cf[q] = 0u, cb[q] = 0u;
+            if (WEIGHTED) wf[q] = 0.0, wb[q] = 0.0;
+        }
+    }
+    __device__ __forceinline__ void add(int q, bool same, double ww) const {
+        atomicAdd(&cf[q], 1u);
+        if (WEIGHTED) atomicAdd(&wf[q], ww);
+        if (same) {
+            atomicAdd(&cb[q], 1u);
+            if (WEIGHTED) atomicAdd(&wb[q], ww);
+        }
+    }
+    // every thread of the workgroup: the accumulated entries to region k's rows, and the histograms zero again
+    __device__ __forceinline__ void flush(const JkOut &o, int k) const {
+        __syncthreads();
+        const size_t row = (size_t)k * o.stride;
+        for (int q = threadIdx.x; q < nh; q += PB)
+            if (cf[q]) {
+                atomicAdd(&o.nfirst[row + q], (unsigned long long)cf[q]);
+                if (WEIGHTED) atomicAdd(&o.wfirst[row + q], wf[q]), wf[q] = 0.0;
+                cf[q] = 0u;
+                if (cb[q]) {
+                    atomicAdd(&o.nboth[row + q], (unsigned long long)cb[q]);
+                    if (WEIGHTED) atomicAdd(&o.wboth[row + q], wb[q]), wb[q] = 0.0;
+                    cb[q] = 0u;
+                }
+            }
+        __syncthreads();
+    }
+};
+
+// MODE 0: a lane's pairs of the last bin for the run's label (a lane's share stays far below 2^32 between two flushes)
+template <bool WEIGHTED>
+struct JkTop {
+    unsigned long long nf = 0, nb = 0;
+    double wf = 0.0, wb = 0.0;
+    __device__ __forceinline__ void add(bool same, double ww) {
+        nf++, wf += ww;
+        if (same) nb++, wb += ww;
+    }
+    __device__ __forceinline__ void fold(const JkHist<WEIGHTED> &h, int q) {
+        if (!nf) return;
+        atomicAdd(&h.cf[q], (unsigned int)nf);
+        if (WEIGHTED) atomicAdd(&h.wf[q], wf);
+        if (nb) {
+            atomicAdd(&h.cb[q], (unsigned int)nb);
+            if (WEIGHTED) atomicAdd(&h.wb[q], wb);
+        }
+        nf = nb = 0, wf = wb = 0.0;
+    }
+};
+
+// il[0 .. cap): the labels of the points a slice could take, ascending (the sort's order inside a cell): the length of the
+// run of il[0].  Every thread searches the same way (broadcast reads)
+__device__ __forceinline__ int jk_run_length(const int *il, int cap) {
+    const int L = il[0];
+    int lo = 1, hi = cap;   // the first index in [1, cap] whose label is not L
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (il[mid] != L) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// The cells of this workgroup: a CONTIGUOUS range holding its share of the points of set 1 - workgroup b takes the cells whose
+// first point lies in [n b / G, n (b + 1) / G) (an equal share of the cells leaves most workgroups of a light cone, whose
+// bounding box is mostly empty, without work).  Every thread searches the same way
+__device__ __forceinline__ void jk_cell_range(const int64_t *__restrict__ start, int ncell, int &c_lo, int &c_hi) {
+    const int64_t n = start[ncell];
+    auto first_cell_from = [&](int64_t target) {   // the first cell whose first point is not before `target`
+        int lo = 0, hi = ncell;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (start[mid] < target) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    };
+    c_lo = first_cell_from(n * (int64_t)blockIdx.x / (int64_t)gridDim.x);
+    c_hi = blockIdx.x + 1 == gridDim.x ? ncell : first_cell_from(n * (int64_t)(blockIdx.x + 1) / (int64_t)gridDim.x);
+}
+
+// the walk of pair_count_w (no separation sums) with the two histograms of the current label
+template <int MODE>
+__global__ __launch_bounds__(PB) void pair_count_jk(PairArgs a, WeightArgs wa, const int *__restrict__ lab1, const int *__restrict__ lab2,
+                                                    JkOut out, int ncell, unsigned long long *__restrict__ evaluated) {
+    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
+    __shared__ int il[PB];
+    __shared__ float e2[64];
+    __shared__ int64_t nb_j0[27];
+    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
+    extern __shared__ __align__(8) double jk_lds[];   // nh sums first | nh sums both | nh counts first | nh counts both
+    const int tid = threadIdx.x;
+    const int nh = a.nbins * a.nsub;
+    const JkHist<true> h(jk_lds, nh);
+    h.clear();
+    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
+    __syncthreads();
+    const float lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
+    const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
+    const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
+    JkTop<true> top;
+    unsigned long long n_eval = 0;
+    unsigned int nflush = 0;
+    int cur = -1;                            // the label the histograms hold (none yet)
+    int c_lo, c_hi;
+    jk_cell_range(a.start1, ncell, c_lo, c_hi);
+    for (int c1 = c_lo; c1 < c_hi; c1++) {
+        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
+        if (cbeg == cend) continue;
+        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
+        if (tid < 64) {
+            int len = 0;
+            int64_t j0 = 0;
+            if (tid < nnb) {
+                const int cz = c1 % a.g.ncz, cy = (c1 / a.g.ncz) % a.g.ncy, cx = c1 / (a.g.ncz * a.g.ncy);
+                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
+                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
+                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
+                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
+                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
+                j0 = a.start2[c2];
+                len = (int)(a.start2[c2 + 1] - j0);
+            }
+            int incl = len;
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) {
+                const int v = __shfl_up(incl, d, 64);
+                if (tid >= d) incl += v;
+            }
+            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
+            if (tid == nnb - 1) nb_pre[nnb] = incl;
+        }
+        __syncthreads();
+        const int M = nb_pre[nnb];
+        for (int64_t i0 = cbeg; i0 < cend;) {
+            const int cap = (int)min((int64_t)PB, cend - i0);
+            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
+            if (tid < cap) {                  // the points behind the run's end are loaded again by the next slice
+                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
+                iw[tid] = wa.w1 ? wa.w1[i0 + tid] : 1.0f;
+                il[tid] = lab1[i0 + tid];
+            }
+            __syncthreads();
+            const int L = il[0], ni = jk_run_length(il, cap);
+            if (L != cur) {                   // uniform: another region from here on
+                if (cur >= 0) {
+                    if (MODE == 0) top.fold(h, a.nbins - 1);
+                    h.flush(out, cur);
+                    nflush++;
+                }
+                cur = L;
+            }
+            for (int base = 0; base < M; base += PB) {
+                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
+                const int v = base + tid;
+                if (v >= M) continue;
+                int sg = 0;
+                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[nnb]: ends at a non-empty cell
+                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
+                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
+                const double wj = wa.w2 ? (double)wa.w2[jj] : 1.0;
+                const bool same = lab2[jj] == L;
+                for (int i = 0; i < ni; i++) {
+                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
+                    const float dx = min_image(ix[i] - xj, a.half, a.g.box);
+                    const float dy = min_image(iy[i] - yj, a.half, a.g.box);
+                    const float dz = min_image(iz[i] - zj, a.half, a.g.box);
+                    float r2;
+                    int sub = 0;
+                    if (MODE == 1) {
+                        const float adz = fabsf(dz);
+                        if (adz >= a.pimax) continue;
+                        r2 = dx * dx + dy * dy;
+                        if (r2 < lo2 || r2 >= hi2) continue;
+                        sub = (int)(adz / a.dpi);
+                        if (sub >= a.nsub) continue;
+                    } else {
+                        r2 = dx * dx + dy * dy + dz * dz;
+                        if (r2 < lo2 || r2 >= hi2) continue;
+                    }
+                    if (MODE == 2) {
+                        const float sep = sqrtf(r2);
+                        const float mu = sep > 0.f ? fabsf(dz) / sep : 0.f;
+                        if (mu >= a.mu_max) continue;
+                        sub = (int)(mu * a.inv_dmu);
+                        if (sub >= a.nsub) continue;
+                    }
+                    const double ww = (double)iw[i] * wj;
+                    if (MODE == 0 && r2 >= top2) {
+                        top.add(same, ww);
+                        continue;
+                    }
+                    int b = a.nbins - 1;
+                    while (r2 < e2[b]) b--;
+                    h.add(b * a.nsub + sub, same, ww);
+                }
+            }
+            i0 += ni;
+        }
+    }
+    if (cur >= 0) {
+        if (MODE == 0) top.fold(h, a.nbins - 1);
+        h.flush(out, cur);
+        nflush++;
+    }
+    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
+    if (tid == 0 && nflush) atomicAdd(out.flushes, (unsigned long long)nflush);
+}
+
+// the walk of pair_count_los (no separation sums) with the two histograms of the current label
+template <int MODE, bool WEIGHTED>
+__global__ __launch_bounds__(PB) void pair_count_los_jk(LosArgs a, const int *__restrict__ lab1, const int *__restrict__ lab2, JkOut out,
+                                                        int ncell, unsigned long long *__restrict__ evaluated) {
+    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
+    __shared__ int il[PB];
+    __shared__ double e2[64];
+    __shared__ int64_t nb_j0[27];
+    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
+    extern __shared__ __align__(8) double jk_lds[];   // [nh sums first | nh sums both] nh counts first | nh counts both
+    const int tid = threadIdx.x;
+    const int nh = a.nbins * a.nsub;
+    const JkHist<WEIGHTED> h(jk_lds, nh);
+    h.clear();
+    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
+    __syncthreads();
+    const double lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
+    const int ncx = a.nc[0], ncy = a.nc[1], ncz = a.nc[2];
+    JkTop<WEIGHTED> top;
+    unsigned long long n_eval = 0;
+    unsigned int nflush = 0;
+    int cur = -1;                            // the label the histograms hold (none yet)
+    int c_lo, c_hi;
+    jk_cell_range(a.start1, ncell, c_lo, c_hi);
+    for (int c1 = c_lo; c1 < c_hi; c1++) {
+        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
+        if (cbeg == cend) continue;
+        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
+        if (tid < 64) {
+            int len = 0;
+            int64_t j0 = 0;
+            if (tid < 27) {
+                const int cz = c1 % ncz, cy = (c1 / ncz) % ncy, cx = c1 / (ncz * ncy);
+                const int nx = cx + tid / 9 - 1, ny = cy + (tid / 3) % 3 - 1, nz = cz + tid % 3 - 1;
+                if (nx >= 0 && nx < ncx && ny >= 0 && ny < ncy && nz >= 0 && nz < ncz) {   // open grid: nothing wraps
+                    const int c2 = (nx * ncy + ny) * ncz + nz;
+                    j0 = a.start2[c2];
+                    len = (int)(a.start2[c2 + 1] - j0);
+                }
+            }
+            int incl = len;
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) {
+                const int v = __shfl_up(incl, d, 64);
+                if (tid >= d) incl += v;
+            }
+            if (tid < 27) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
+            if (tid == 26) nb_pre[27] = incl;
+        }
+        __syncthreads();
+        const int M = nb_pre[27];
+        for (int64_t i0 = cbeg; i0 < cend;) {
+            const int cap = (int)min((int64_t)PB, cend - i0);
+            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
+            if (tid < cap) {                  // the points behind the run's end are loaded again by the next slice
+                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
+                iw[tid] = WEIGHTED && a.w1 ? a.w1[i0 + tid] : 1.0f;
+                il[tid] = lab1[i0 + tid];
+            }
+            __syncthreads();
+            const int L = il[0], ni = jk_run_length(il, cap);
+            if (L != cur) {                   // uniform: another region from here on
+                if (cur >= 0) {
+                    if (MODE == 0) top.fold(h, a.nbins - 1);
+                    h.flush(out, cur);
+                    nflush++;
+                }
+                cur = L;
+            }
+            for (int base = 0; base < M; base += PB) {
+                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
+                const int v = base + tid;
+                if (v >= M) continue;
+                int sg = 0;
+                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[27]: ends at a non-empty cell
+                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
+                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
+                const double wj = WEIGHTED && a.w2 ? (double)a.w2[jj] : 1.0;
+                const bool same = lab2[jj] == L;
+                for (int i = 0; i < ni; i++) {
+                    const float dxf = ix[i] - xj, dyf = iy[i] - yj, dzf = iz[i] - zj;
+                    const float s2f = dxf * dxf + dyf * dyf + dzf * dzf;
+                    if (s2f > a.pre_hi || s2f < a.pre_lo) continue;
+                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
+                    const double dx = (double)dxf, dy = (double)dyf, dz = (double)dzf;
+                    const double s2 = dx * dx + dy * dy + dz * dz;
+                    double q = s2, pi2 = 0.0;
+                    int sub = 0;
+                    if (MODE == 0) {
+                        if (!(q >= lo2 && q < hi2)) continue;
+                    } else {
+                        if (MODE == 2 && !(q >= lo2 && q < hi2)) continue;
+                        const double lx = (double)(ix[i] + xj), ly = (double)(iy[i] + yj), lz = (double)(iz[i] + zj);
+                        const double l2 = lx * lx + ly * ly + lz * lz;
+                        if (l2 == 0.0) continue;                // no line of sight
+                        const double t = dx * lx + dy * ly + dz * lz;
+                        pi2 = t * t / l2;
+                        if (MODE == 1) {
+                            const double pi = sqrt(pi2);
+                            if (!(pi < a.pimax)) continue;
+                            const double rp2 = s2 - pi2;
+                            q = rp2 > 0.0 ? rp2 : 0.0;
+                            if (!(q >= lo2 && q < hi2)) continue;
+                            sub = (int)(pi / a.dpi);
+                        } else {
+                            const double mu = s2 > 0.0 ? sqrt(pi2 / s2) : 0.0;
+                            if (!(mu < a.mu_max)) continue;
+                            sub = (int)(mu * a.inv_dmu);
+                        }
+                        if (sub >= a.nsub) continue;
+                    }
+                    const double ww = WEIGHTED ? (double)iw[i] * wj : 0.0;
+                    if (MODE == 0 && q >= top2) {
+                        top.add(same, ww);
+                        continue;
+                    }
+                    int b = a.nbins - 1;
+                    while (q < e2[b]) b--;
+                    h.add(b * a.nsub + sub, same, ww);
+                }
+            }
+            i0 += ni;
+        }
+    }
+    if (cur >= 0) {
+        if (MODE == 0) top.fold(h, a.nbins - 1);
+        h.flush(out, cur);
+        nflush++;
+    }
+    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
+    if (tid == 0 && nflush) atomicAdd(out.flushes, (unsigned long long)nflush);
+}
+
+// smallest and largest label of a set: range[0] = min, range[1] = max (the host refuses a call whose labels leave [0, nreg)
+// before anything is sorted or counted)
+__global__ void jk_label_range(const int *__restrict__ labels, int64_t n, int *__restrict__ range) {
+    int mn = 0x7fffffff, mx = (int)0x80000000;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int l = labels[i];
+        mn = min(mn, l), mx = max(mx, l);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off, 64)), mx = max(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0 && mn <= mx) atomicMin(&range[0], mn), atomicMax(&range[1], mx);
+}
+
+// the sort key of a point: its cell above its label (the label masked to its bits: it was range-checked before)
+template <typename K, typename Grid>
+__global__ void jk_cell_keys(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                             const int *__restrict__ labels, int64_t n, Grid g, int lab_bits, K *__restrict__ keys,
+                             unsigned int *__restrict__ idx) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v[3] = {x[i], y[i], z[i]};
+        keys[i] = ((K)g.cell(v) << lab_bits) | (K)((unsigned int)labels[i] & ((1u << lab_bits) - 1u));
+        idx[i] = (unsigned int)i;
+    }
+}
+// behind the sort: points, weights and labels in (cell, label, input) order
+__global__ void jk_gather(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                          const float *__restrict__ w, const int *__restrict__ labels, int64_t n, const unsigned int *__restrict__ idx,
+                          float *__restrict__ sx, float *__restrict__ sy, float *__restrict__ sz, float *__restrict__ sw,
+                          int *__restrict__ sl) {
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned int i = idx[s];
+        sx[s] = x[i], sy[s] = y[i], sz[s] = z[i], sl[s] = labels[i];
+        if (w) sw[s] = w[i];
+    }
+}
+template <typename K>
+__global__ void jk_cell_starts(const K *__restrict__ keys, int64_t n, int64_t ncell, int lab_bits, int64_t *__restrict__ start) {
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= ncell; c += (int64_t)gridDim.x * blockDim.x) {
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)(keys[mid] >> lab_bits) < c) lo = mid + 1;
+            else hi = mid;
+        }
+        start[c] = lo;
+    }
+}
+
+// labels of an nx x ny x nz split of the periodic box, from the float32 coordinate the counter sees, wrapped like the cell grid
+template <typename T>
+__global__ void jk_box_labels(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z, int64_t n, float inv_box,
+                              int nx, int ny, int nz, int *__restrict__ labels) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int cx = max(cell_coord((float)x[i], nx, inv_box), 0), cy = max(cell_coord((float)y[i], ny, inv_box), 0),
+                  cz = max(cell_coord((float)z[i], nz, inv_box), 0);
+        labels[i] = (cx * ny + cy) * nz + cz;
+    }
+}
+
+struct JkWork {
+    DevBuf labs[2], keys[2], sorted_labels[2], range;
+    int *sl[2];
+} g_jk;
+
+int bits_for(int64_t n) {   // bits that hold 0 .. n - 1
+    int b = 1;
+    while (((int64_t)1 << b) < n) b++;
+    return b;
+}
+
+template <typename K, typename Grid>
+int jk_sort_keys(const Columns &c, const int *labels, int64_t n, const Grid &g, int64_t ncell, int lab_bits, int end_bit, SortedSet &s,
+                 DevBuf &keybuf, int nblk) {
+    ABACUS_TRY(keybuf.reserve(2 * (size_t)n * sizeof(K)));
+    K *keys = keybuf.as<K>(), *keys2 = keys + n;
+    ABACUS_LAUNCH("pair_jk_keys", (jk_cell_keys<K, Grid>), dim3(nblk), dim3(256), 0, c.x[0], c.x[1], c.x[2], labels, n, g, lab_bits, keys,
+                  s.idx.as<unsigned int>());
+    size_t tmp_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, s.idx.as<unsigned int>(), s.idx2.as<unsigned int>(), (int)n, 0,
+                                             end_bit, stream());
+    ABACUS_TRY(s.tmp.reserve(tmp_bytes));
+    prof_begin("pair_jk_sort");
+    const hipError_t sorted = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tmp_bytes, keys, keys2, s.idx.as<unsigned int>(),
+                                                                 s.idx2.as<unsigned int>(), (int)n, 0, end_bit, stream());
+    prof_end("pair_jk_sort");
+    if (sorted != hipSuccess) return fail("abacus_paircount_jk: radix sort failed");
+    const int cblk = (int)std::min<int64_t>(ceil_div(ncell + 1, 256), 8192);
+    ABACUS_LAUNCH("pair_jk_starts", jk_cell_starts<K>, dim3(cblk), dim3(256), 0, keys2, n, ncell, lab_bits, s.start.as<int64_t>());
+    return 0;
+}
+
+// The set in (cell, label) order on either grid: s.sx | sy | sz, s.start, s.sw with weights, and g_jk.sl[k].  One stable radix
+// sort for every size (the counting sort of sort_into_cells leaves the order inside a cell to the run); n > 0
+template <typename Grid>
+int sort_into_cells_jk(const Columns &c, const int *labels, int64_t n, const Grid &g, int64_t ncell, int nreg, int k) {
+    SortedSet &s = g_work.S[k];
+    const size_t n1 = (size_t)n;
+    s.n = n;
+    ABACUS_TRY(s.sorted.reserve(3 * n1 * 4));
+    ABACUS_TRY(s.start.reserve((size_t)(ncell + 1) * 8));
+    ABACUS_TRY(s.idx.reserve(n1 * 4));
+    ABACUS_TRY(s.idx2.reserve(n1 * 4));
+    ABACUS_TRY(g_jk.sorted_labels[k].reserve(n1 * 4));
+    s.sx = s.sorted.as<float>(), s.sy = s.sx + n1, s.sz = s.sy + n1, s.sw = nullptr;
+    if (c.w) {
+        ABACUS_TRY(s.wsorted.reserve(n1 * 4));
+        s.sw = s.wsorted.as<float>();
+    }
+    g_jk.sl[k] = g_jk.sorted_labels[k].as<int>();
+    const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 2048);
+    const int lab_bits = bits_for(nreg), end_bit = lab_bits + bits_for(ncell);
+    if (end_bit <= 32) ABACUS_TRY((jk_sort_keys<unsigned int, Grid>(c, labels, n, g, ncell, lab_bits, end_bit, s, g_jk.keys[k], nblk)));
+    else ABACUS_TRY((jk_sort_keys<unsigned long long, Grid>(c, labels, n, g, ncell, lab_bits, end_bit, s, g_jk.keys[k], nblk)));
+    ABACUS_LAUNCH("pair_jk_fill", jk_gather, dim3(nblk), dim3(256), 0, c.x[0], c.x[1], c.x[2], c.w, labels, n, s.idx2.as<unsigned int>(), s.sx,
+                  s.sy, s.sz, s.sw, g_jk.sl[k]);
+    return 0;
+}
+
+struct JkHostOut {
+    uint64_t *nfirst, *nboth;
+    double *wfirst, *wboth;
+};
+
+// what both drivers check before the device is touched
+int jk_check(const char *who, int nreg, int nbins, int nsub, int autocorr, const void *labels1, const void *labels2, int64_t n1, int64_t n2,
+             const JkHostOut &o, bool need_sums) {
+    if (nreg < 1 || nreg > JK_MAX_REG) return fail("%s: nreg = %d must lie in [1, %d]", who, nreg, JK_MAX_REG);
+    if (nsub > JK_MAX_HIST) return fail("%s: %d pi / mu bins exceed the LDS histogram", who, nsub);
+    if ((int64_t)nreg * nbins * nsub > JK_MAX_OUT) return fail("%s: nreg * nbins * sub-bins = %lld exceeds 2^24 output entries", who, (long long)nreg * nbins * nsub);
+    if (!o.nfirst || !o.nboth) return fail("%s: npairs_first / npairs_both is NULL", who);
+    if ((o.wfirst == nullptr) != (o.wboth == nullptr)) return fail("%s: wsum_first and wsum_both go together", who);
+    if (need_sums && !o.wfirst) return fail("%s: wsum_first / wsum_both is NULL", who);
+    if (autocorr && labels2) return fail("%s: labels2 given for an autocorrelation (x2 is NULL)", who);
+    if (n1 > 0 && !labels1) return fail("%s: labels1 is NULL", who);
+    if (!autocorr && n2 > 0 && !labels2) return fail("%s: labels2 is NULL", who);
+    return 0;
+}
+
+// labels in HBM (host labels are uploaded) and range-checked by a device reduction: nothing is sorted or counted with a label
+// outside [0, nreg)
+int jk_stage_labels(const char *who, const int32_t *const src[2], const int64_t ns[2], int nsets, int where, int nreg, const int *dl[2]) {
+    ABACUS_TRY(g_jk.range.reserve(8));
+    const int init[2] = {0x7fffffff, (int)0x80000000};
+    HIP_TRY(hipMemcpyAsync(g_jk.range.p, init, 8, hipMemcpyHostToDevice, stream()));
+    for (int k = 0; k < nsets; k++) {
+        dl[k] = src[k];
+        if (where == 0) {
+            ABACUS_TRY(g_jk.labs[k].reserve((size_t)ns[k] * 4));
+            HIP_TRY(hipMemcpyAsync(g_jk.labs[k].p, src[k], (size_t)ns[k] * 4, hipMemcpyHostToDevice, stream()));
+            dl[k] = g_jk.labs[k].as<int>();
+        }
+        ABACUS_LAUNCH("pair_jk_label_range", jk_label_range, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
+                      dl[k], ns[k], g_jk.range.as<int>());
+    }
+    int range[2];
+    HIP_TRY(hipMemcpyAsync(range, g_jk.range.p, 8, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    if (range[0] < 0 || range[1] >= nreg) return fail("%s: labels span [%d, %d], outside [0, %d)", who, range[0], range[1], nreg);
+    return 0;
+}
+
+// the four output arrays in g_work.out, zeroed: [nreg][ntot] each
+int jk_device_outputs(int nreg, size_t ntot, bool sums, JkOut &d, unsigned long long *flushes) {
+    const size_t cnt = (size_t)nreg * ntot, bytes = (sums ? 4 : 2) * cnt * 8;
+    ABACUS_TRY(g_work.out.reserve(bytes));
+    HIP_TRY(hipMemsetAsync(g_work.out.p, 0, bytes, stream()));
+    d.nfirst = g_work.out.as<unsigned long long>(), d.nboth = d.nfirst + cnt;
+    d.wfirst = sums ? reinterpret_cast<double *>(d.nboth + cnt) : nullptr, d.wboth = sums ? d.wfirst + cnt : nullptr;
+    d.stride = ntot, d.flushes = flushes;
+    return 0;
+}
+JkOut jk_at(const JkOut &d, size_t o) {
+    JkOut r = d;
+    r.nfirst += o, r.nboth += o;
+    if (r.wfirst) r.wfirst += o, r.wboth += o;
+    return r;
+}
+int jk_fetch(const JkHostOut &h, const JkOut &d, size_t cnt) {
+    HIP_TRY(hipMemcpyAsync(h.nfirst, d.nfirst, cnt * 8, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipMemcpyAsync(h.nboth, d.nboth, cnt * 8, hipMemcpyDeviceToHost, stream()));
+    if (h.wfirst) {
+        HIP_TRY(hipMemcpyAsync(h.wfirst, d.wfirst, cnt * 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipMemcpyAsync(h.wboth, d.wboth, cnt * 8, hipMemcpyDeviceToHost, stream()));
+    }
+    return 0;
+}
+void jk_zero(const JkHostOut &h, size_t cnt) {
+    memset(h.nfirst, 0, cnt * 8), memset(h.nboth, 0, cnt * 8);
+    if (h.wfirst) memset(h.wfirst, 0, cnt * 8), memset(h.wboth, 0, cnt * 8);
+}
+
+}  // namespace
+
+static unsigned long long g_jk_flushes = 0;
+static int g_jk_workgroups = 0;
+
+static int paircount_jk_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1,
+                             const int32_t *labels1, int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2,
+                             const int32_t *labels2, int64_t n2, int where, int nreg, float boxsize, const float *bins, int nbins,
+                             float pimax, int npibins, float mu_max, int nmubins, JkHostOut host) {
+    // every argument is checked before the device is touched
+    if (mode < 0 || mode > 2) return fail("%s: unknown mode %d", who, mode);
+    if (!x1 || !y1 || !z1 || !bins || nbins < 1) return fail("%s: null/empty argument", who);
+    if (!(boxsize > 0)) return fail("%s: boxsize must be positive", who);
+    const int autocorr = x2 == nullptr;
+    if (!autocorr && (!y2 || !z2)) return fail("%s: null argument (y2 / z2)", who);
+    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
+    if (nsub < 1) return fail("%s: need at least one pi / mu bin", who);
+    if (autocorr && w2) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
+    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
+    ABACUS_TRY(jk_check(who, nreg, nbins, nsub, autocorr, labels1, labels2, n1, n2, host, true));
+    for (int b = 0; b < nbins; b++)
+        if (!(bins[b + 1] > bins[b])) return fail("%s: bin edges must increase", who);
+    if (bins[nbins] > 0.5f * boxsize || (mode == 1 && pimax > 0.5f * boxsize))
+        return fail("%s: maximum separation exceeds half the box (minimum image not unique)", who);
+    ABACUS_ENTER();
+    const size_t ntot_all = (size_t)nbins * nsub;
+    jk_zero(host, (size_t)nreg * ntot_all);
+    g_last_evaluated = 0, g_jk_flushes = 0, g_jk_workgroups = 0;
+    g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
+    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
+
+    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
+    const float *const srcw[2] = {w1, w2};
+    const int32_t *const srcl[2] = {labels1, labels2};
+    const int64_t ns[2] = {n1, n2};
+    const int nsets = autocorr ? 1 : 2;
+    Work &W = g_work;
+    const int *dl[2] = {nullptr, nullptr};
+    ABACUS_TRY(jk_stage_labels(who, srcl, ns, nsets, where, nreg, dl));
+    Flags fl;
+    ABACUS_TRY(W.flags(fl));
+    unsigned long long *flushes = fl.evaluated + 1;   // the block of flags has room behind the candidate count
+    JkOut dev;
+    ABACUS_TRY(jk_device_outputs(nreg, ntot_all, true, dev, flushes));
+    Columns cols[2];
+    for (int k = 0; k < nsets; k++) ABACUS_TRY(stage_columns("pair_cast", src[k], srcw[k], where, ns[k], nullptr, W.cols[k], W.wts[k], cols[k]));
+    // every run sorts (the grid follows the run's reach) and counts
+    ABACUS_TRY(for_runs(nbins, nsub, JK_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
+        const float *edges = bins + b0;
+        const float reach_xy = edges[nb], reach_z = mode == 1 ? pimax : edges[nb];
+        CellGrid g;
+        g.box = boxsize;
+        g.inv_box = 1.0f / boxsize;
+        auto ncells = [&](float reach) {   // the weighted counter's grid: cells of the full reach
+            const int nc = std::min((int)floorf(boxsize / reach * 0.9999f), 128);
+            return nc < 3 ? 1 : nc;
+        };
+        g.ncx = g.ncy = ncells(reach_xy);
+        g.ncz = ncells(reach_z);
+        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
+        for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells_jk(cols[k], dl[k], ns[k], g, ncell, nreg, k));
+        std::vector<float> e2;
+        ABACUS_TRY(upload_edges(edges, nb, e2));
+        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
+        PairArgs a;
+        WeightArgs wa;
+        fill_sets(a, wa, autocorr, nb, nsub, Outputs{nullptr, nullptr, nullptr});
+        a.mode = mode;
+        a.in_box = 1;
+        a.g = g;
+        a.half = boxsize * 0.5f;
+        a.pimax = pimax;
+        a.dpi = npibins > 0 ? pimax / (float)npibins : 1.0f;
+        a.mu_max = mu_max;
+        a.inv_dmu = nmubins > 0 ? (float)nmubins / mu_max : 1.0f;
+        a.edges2 = W.edges.as<float>();
+        a.lut_sh = a.lut_off = a.lut_ncell = 0;
+        a.no_blocks = 0;
+        const size_t hist_bytes = (size_t)nb * nsub * 24;   // <= JK_MAX_HIST * 24 = 48 KiB beside 6 KiB of static LDS
+        ABACUS_TRY(with_mode(mode, [&](auto M) -> int {
+            const auto kernel = pair_count_jk<decltype(M)::value>;
+            dim3 grid;
+            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+            if (option("pairs_jk_grid") > 0) grid.x = std::min<unsigned int>(grid.x, (unsigned int)option("pairs_jk_grid"));   // tests: many cells per workgroup
+            ABACUS_LAUNCH("pair_count_jk", kernel, grid, dim3(PB), hist_bytes, a, wa, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(dev, o), (int)ncell,
+                          fl.evaluated);
+            g_jk_workgroups = (int)grid.x;
+            return 0;
+        }));
+        HIP_TRY(hipMemcpyAsync(&g_last_evaluated, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = 0;
+        return 0;
+    }));
+    ABACUS_TRY(jk_fetch(host, dev, (size_t)nreg * ntot_all));
+    HIP_TRY(hipMemcpyAsync(&g_jk_flushes, flushes, 8, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+extern "C" int abacus_paircount_jk(int mode, const float *x1, const float *y1, const float *z1, const float *w1, const int32_t *labels1,
+                                   int64_t n1, const float *x2, const float *y2, const float *z2, const float *w2, const int32_t *labels2,
+                                   int64_t n2, int nreg, float boxsize, const float *bins, int nbins, float pimax, int npibins,
+                                   float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both, double *wsum_first,
+                                   double *wsum_both) {
+    return paircount_jk_impl("abacus_paircount_jk", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2, 0, nreg, boxsize, bins,
+                             nbins, pimax, npibins, mu_max, nmubins, JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+}
+
+extern "C" int abacus_paircount_jk_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, const int32_t *labels1,
+                                       int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2, const int32_t *labels2,
+                                       int64_t n2, int pos_dtype, int nreg, float boxsize, const float *bins, int nbins, float pimax,
+                                       int npibins, float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both,
+                                       double *wsum_first, double *wsum_both) {
+    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_jk_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
+    return paircount_jk_impl("abacus_paircount_jk_dev", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2,
+                             pos_dtype == ABACUS_F32 ? 1 : 2, nreg, boxsize, bins, nbins, pimax, npibins, mu_max, nmubins,
+                             JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+}
+
+static int paircount_los_jk_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1,
+                                 const int32_t *labels1, int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2,
+                                 const int32_t *labels2, int64_t n2, int where, int nreg, const double *origin, const float *bins,
+                                 int nbins, float pimax, int npibins, float mu_max, int nmubins, JkHostOut host) {
+    // every argument is checked before the device is touched
+    if (mode < 0 || mode > 2) return fail("%s: unknown mode %d", who, mode);
+    if (!x1 || !y1 || !z1 || !origin || !bins) return fail("%s: null argument", who);
+    if (nbins < 1) return fail("%s: nbins must be at least 1", who);
+    const int autocorr = x2 == nullptr;
+    if (!autocorr && (!y2 || !z2)) return fail("%s: null argument (y2 / z2)", who);
+    if (autocorr && w2) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
+    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
+    if (!(bins[0] >= 0.f)) return fail("%s: bin edges must not be negative", who);
+    for (int b = 0; b < nbins; b++)
+        if (!(bins[b + 1] > bins[b])) return fail("%s: bin edges must increase", who);
+    if (mode == 1 && (!(pimax > 0.f) || npibins < 1)) return fail("%s: pimax must be positive, with at least one pi bin", who);
+    if (mode == 2 && (!(mu_max > 0.f) || nmubins < 1)) return fail("%s: mu_max must be positive, with at least one mu bin", who);
+    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
+    ABACUS_TRY(jk_check(who, nreg, nbins, nsub, autocorr, labels1, labels2, n1, n2, host, false));
+    for (int d = 0; d < 3; d++)
+        if (!std::isfinite(origin[d])) return fail("%s: origin must be finite", who);
+    ABACUS_ENTER();
+    const bool weighted = host.wfirst != nullptr;   // NULL sums: integer counts only
+    const size_t ntot_all = (size_t)nbins * nsub;
+    jk_zero(host, (size_t)nreg * ntot_all);
+    g_last_evaluated = 0, g_jk_flushes = 0, g_jk_workgroups = 0;
+    g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
+    g_los_cells[0] = g_los_cells[1] = g_los_cells[2] = 0;
+    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
+
+    Work &W = g_work;
+    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
+    const float *const srcw[2] = {weighted ? w1 : nullptr, weighted ? w2 : nullptr};
+    const int32_t *const srcl[2] = {labels1, labels2};
+    const int64_t ns[2] = {n1, n2};
+    const int nsets = autocorr ? 1 : 2;
+    const int *dl[2] = {nullptr, nullptr};
+    ABACUS_TRY(jk_stage_labels(who, srcl, ns, nsets, where, nreg, dl));
+    Columns cols[2];
+    Flags fl;
+    ABACUS_TRY(W.flags(fl));
+    unsigned long long *flushes = fl.evaluated + 1;
+    for (int k = 0; k < nsets; k++) {
+        ABACUS_TRY(stage_columns("pair_los_centre", src[k], srcw[k], where, ns[k], origin, W.cols[k], W.wts[k], cols[k]));
+        ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
+                      cols[k].x[0], cols[k].x[1], cols[k].x[2], ns[k], fl.frame);
+    }
+    Frame fr;
+    HIP_TRY(hipMemcpyAsync(&fr, fl.frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    double lo[3], extent[3];
+    for (int d = 0; d < 3; d++) {
+        lo[d] = (double)funkey_host(fr.mn[d]);
+        extent[d] = (double)funkey_host(fr.mx[d]) - lo[d];
+        if (!(extent[d] >= 0.0) || !std::isfinite(extent[d]) || !std::isfinite(lo[d])) return fail("%s: coordinates are not finite", who);
+    }
+    JkOut dev;
+    ABACUS_TRY(jk_device_outputs(nreg, ntot_all, weighted, dev, flushes));
+    unsigned long long evaluated = 0;
+    ABACUS_TRY(for_runs(nbins, nsub, JK_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
+        std::vector<double> e2;
+        ABACUS_TRY(upload_edges(bins + b0, nb, e2));
+        const double reach2 = mode == 1 ? e2[nb] + (double)pimax * (double)pimax : e2[nb];
+        const double reach = std::nextafter(std::sqrt(reach2), HUGE_VAL);   // rounded up
+        OpenGrid og;
+        for (int d = 0; d < 3; d++) {
+            const double fit = std::floor(extent[d] / (reach * 1.0001));    // cell side >= 1.0001 reach (see OpenGrid)
+            og.nc[d] = (int)std::min(128.0, std::max(1.0, fit));
+            og.lo[d] = (float)lo[d];                                         // exact: a float32 coordinate
+            og.inv[d] = extent[d] > 0.0 ? (float)((double)og.nc[d] / extent[d]) : 0.f;
+        }
+        const int64_t ncell = (int64_t)og.nc[0] * og.nc[1] * og.nc[2];
+        for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells_jk(cols[k], dl[k], ns[k], og, ncell, nreg, k));
+        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
+        LosArgs a;
+        fill_sets(a, a, autocorr, nb, nsub, Outputs{nullptr, nullptr, nullptr});
+        for (int d = 0; d < 3; d++) a.nc[d] = og.nc[d];
+        // the pre-test's thresholds (derivation at pair_count_los): rounded away from the accepted range
+        const double hi_d = reach2 * (1.0 + 0x1p-20), lo_d = e2[0] * (1.0 - 0x1p-20);
+        float hi_f = (float)hi_d, lo_f = (float)lo_d;
+        if ((double)hi_f < hi_d) hi_f = std::nextafterf(hi_f, HUGE_VALF);
+        if ((double)lo_f > lo_d) lo_f = std::nextafterf(lo_f, 0.f);
+        a.pre_hi = hi_f;
+        a.pre_lo = mode != 1 && lo_d >= 1e-30 ? lo_f : 0.f;
+        a.pimax = (double)pimax;
+        a.dpi = npibins > 0 ? (double)pimax / npibins : 1.0;
+        a.mu_max = (double)mu_max;
+        a.inv_dmu = nmubins > 0 ? nmubins / (double)mu_max : 1.0;
+        a.edges2 = W.edges.as<double>();
+        const size_t hist_bytes = (size_t)nb * nsub * (weighted ? 24 : 8);
+        ABACUS_TRY(with_mode(mode, [&](auto M) {
+            return with_flag(weighted, [&](auto WT) -> int {
+                const auto kernel = pair_count_los_jk<decltype(M)::value, decltype(WT)::value>;
+                dim3 grid;
+                ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+                if (option("pairs_jk_grid") > 0) grid.x = std::min<unsigned int>(grid.x, (unsigned int)option("pairs_jk_grid"));
+                ABACUS_LAUNCH("pair_count_los_jk", kernel, grid, dim3(PB), hist_bytes, a, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(dev, o), (int)ncell,
+                              fl.evaluated);
+                g_jk_workgroups = (int)grid.x;
+                return 0;
+            });
+        }));
+        unsigned long long ev = 0;
+        HIP_TRY(hipMemcpyAsync(&ev, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        evaluated += ev;
+        g_last_cells[0] = og.nc[0], g_last_cells[1] = og.nc[2], g_last_cells[2] = 0;
+        for (int d = 0; d < 3; d++) g_los_cells[d] = og.nc[d];
+        return 0;
+    }));
+    ABACUS_TRY(jk_fetch(host, dev, (size_t)nreg * ntot_all));
+    HIP_TRY(hipMemcpyAsync(&g_jk_flushes, flushes, 8, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    g_last_evaluated = evaluated;
+    return 0;
+}
+
+extern "C" int abacus_paircount_los_jk(int mode, const float *x1, const float *y1, const float *z1, const float *w1, const int32_t *labels1,
+                                       int64_t n1, const float *x2, const float *y2, const float *z2, const float *w2,
+                                       const int32_t *labels2, int64_t n2, int nreg, const double *origin, const float *bins, int nbins,
+                                       float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both,
+                                       double *wsum_first, double *wsum_both) {
+    return paircount_los_jk_impl("abacus_paircount_los_jk", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2, 0, nreg, origin,
+                                 bins, nbins, pimax, npibins, mu_max, nmubins, JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+}
+
+extern "C" int abacus_paircount_los_jk_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, const int32_t *labels1,
+                                           int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2,
+                                           const int32_t *labels2, int64_t n2, int pos_dtype, int nreg, const double *origin,
+                                           const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
+                                           uint64_t *npairs_first, uint64_t *npairs_both, double *wsum_first, double *wsum_both) {
+    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_los_jk_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
+    return paircount_los_jk_impl("abacus_paircount_los_jk_dev", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2,
+                                 pos_dtype == ABACUS_F32 ? 1 : 2, nreg, origin, bins, nbins, pimax, npibins, mu_max, nmubins,
+                                 JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+}
+
+extern "C" int abacus_paircount_jk_stats(uint64_t *flushes, int *workgroups) {
+    ABACUS_ENTER();
+    if (flushes) *flushes = g_jk_flushes;
+    if (workgroups) *workgroups = g_jk_workgroups;
+    return 0;
+}
+
+extern "C" int abacus_jk_box_labels_dev(const void *x, const void *y, const void *z, int pos_dtype, int64_t n, float boxsize, int nx, int ny,
+                                        int nz, int32_t *labels) {
+    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_jk_box_labels_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
+    if (n < 0 || (n > 0 && (!x || !y || !z || !labels))) return fail("abacus_jk_box_labels_dev: bad argument");
+    if (!(boxsize > 0)) return fail("abacus_jk_box_labels_dev: boxsize must be positive");
+    if (nx < 1 || ny < 1 || nz < 1 || (int64_t)nx * ny * nz > JK_MAX_REG)
+        return fail("abacus_jk_box_labels_dev: the split %d x %d x %d must have 1 .. %d regions", nx, ny, nz, JK_MAX_REG);
+    ABACUS_ENTER();
+    if (n == 0) return 0;
+    const dim3 grid((unsigned int)std::min<int64_t>(ceil_div(n, 256), 2048));
+    const float inv_box = 1.0f / boxsize;
+    if (pos_dtype == ABACUS_F64)
+        ABACUS_LAUNCH("pair_jk_box_labels", jk_box_labels<double>, grid, dim3(256), 0, (const double *)x, (const double *)y, (const double *)z, n,
+                      inv_box, nx, ny, nz, labels);
+    else
+        ABACUS_LAUNCH("pair_jk_box_labels", jk_box_labels<float>, grid, dim3(256), 0, (const float *)x, (const float *)y, (const float *)z, n,
+                      inv_box, nx, ny, nz, labels);
     HIP_TRY(hipStreamSynchronize(stream()));
     return 0;
 }

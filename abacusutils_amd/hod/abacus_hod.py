@@ -605,6 +605,37 @@ class AbacusHOD:
             return np.concatenate((new_wp, new_multi))
         return self._pairs(mock_dict, fn, weights)
 
+    def compute_jackknife(self, mock_dict, statistic, nsplit, *args, weights=None):
+        """(full, delete-one samples, jackknife covariance) of 'wp' | 'xirppi' | 'multipole' for every tracer pair on the
+        periodic box, the regions an `nsplit` (an int or three) split of the box into sub-boxes (analysis/jackknife.py: one
+        pair walk per count instead of one per region).  `*args` are those of the matching `compute_*`; weights: see `_pairs`.
+        The labels are made in HBM when the catalogue is still resident there"""
+        from ..analysis import jackknife as jk
+        if statistic not in ('wp', 'xirppi', 'multipole'):
+            raise ValueError("statistic must be one of 'wp', 'xirppi', 'multipole'")
+        if statistic == 'multipole':
+            rpbins, pimax, sbins, nbins_mu, *rest = args
+            orders, Nthread = (rest + [[0, 2], 8][len(rest):])[:2]
+        else:
+            rpbins, pimax, pi_bin_size, *rest = args
+            Nthread = rest[0] if rest else 8
+        nreg = int(np.prod(jk._split(nsplit)))
+
+        def fn(x1, y1, z1, x2, y2, z2, **w):
+            r1 = jk.box_regions(x1, y1, z1, self.lbox, nsplit)
+            r2 = None if x2 is None else jk.box_regions(x2, y2, z2, self.lbox, nsplit)
+            kw = dict(x2=x2, y2=y2, z2=z2, regions2=r2, **w)
+            if statistic == 'wp':
+                return jk.calc_wp_jk(x1, y1, z1, rpbins, pimax, self.lbox, Nthread, r1, nreg, **kw)
+            if statistic == 'xirppi':
+                return jk.calc_xirppi_jk(x1, y1, z1, rpbins, pimax, pi_bin_size, self.lbox, Nthread, r1, nreg, **kw)
+            sb = sbins if x2 is None else rpbins
+            wp = jk.calc_wp_jk(x1, y1, z1, rpbins, pimax, self.lbox, Nthread, r1, nreg, **kw)
+            multi = jk.calc_multipole_jk(x1, y1, z1, sb, self.lbox, Nthread, r1, nreg, nbins_mu=nbins_mu, orders=orders, **kw)
+            samples = np.hstack((wp[1], multi[1]))
+            return np.concatenate((wp[0], multi[0])), samples, jk.jackknife_covariance(samples)
+        return self._pairs(mock_dict, fn, weights)
+
     def compute_power(self, mock_dict, nbins_k, nbins_mu, k_hMpc_max, logk, poles=[], paste='TSC', num_cells=550,
                       compensated=False, interlaced=False, randoms=None):
         r"""P(k, mu) and/or P_l(k) for every tracer pair (:1338-1472).  Returned keys: '{a}_{b}', '..._modes',

@@ -72,7 +72,8 @@ int abacus_profile_get(const char **names, double *total_ms, int64_t *launches, 
  * keep masks / no mass-sorted key index), hod_deal (the index path through hod_deal and the tile queues),
  * hod_sbindex (1: the index path through the global index, hod_exact_index and hod_emit_bm, instead of the per-superblock index),
  * hod_keepmasks (1: the per-superblock index path keeps the keep masks exact populate by populate instead of writing them on
- * demand), dbg / dbg_fft / dbg_tsc (ablation bit masks).  Default 0 = the production path. */
+ * demand), pairs_jk_grid (at most that many workgroups for the jackknife pair kernels: a small catalogue then walks many cells
+ * per workgroup, as a large one does), dbg / dbg_fft / dbg_tsc (ablation bit masks).  Default 0 = the production path. */
 int abacus_set_option(const char *name, int value);
 int abacus_get_option(const char *name);
 
@@ -554,6 +555,53 @@ int abacus_paircount_los_dev(int mode, const void *x1, const void *y1, const voi
 int abacus_paircount_los_grid(int *ncell /* [3] */);
 /* one device column, observer-centred: dst[i] = float32(src[i] - origin), subtracted in the column's dtype (pos_dtype) */
 int abacus_paircount_los_centre(const void *src, int pos_dtype, int64_t n, double origin, float *dst);
+
+/*
+ * Jackknife pair counts: the per-region counts of a delete-one jackknife from ONE pair walk (no reference code and no
+ * Corrfunc run stands behind this; pinned against the NumPy statement tests/pairs_jk_statement.py).  Every point carries an
+ * int32 label in [0, nreg).  Pairs and bins are exactly those of abacus_paircount_weighted (abacus_paircount_jk) and of
+ * abacus_paircount_los (abacus_paircount_los_jk) for the same columns, weights and binning; per (bin, sub-bin) q, region k:
+ *   first[k][q]  over the pairs (i, j) of q with labels1[i] == k
+ *   both[k][q]   over those with labels1[i] == k and labels2[j] == k   (autocorrelation: labels2 = labels1)
+ * each as an integer count (npairs_*) and as sum of w_i w_j (wsum_*: float64 products and sums, |error| <= n 2^-52 sum|term|),
+ * laid out [nreg][nbins * (1 | npibins | nmubins)].  sum_k first[k][q] is the parent's result (npairs bit for bit); there
+ * are no separation sums.  The count over labels2[j] == k ("second") is no output: membership of a pair is symmetric
+ * under exchange of its points in every mode (d -> -d; l, |dz| and t^2 are unchanged), so it is `first` of the call with the
+ * two sets exchanged - and `first` itself for an autocorrelation; `both` of the two calls agrees exactly in npairs.
+ * Limits, checked on the host before anything is launched (an error code and a message, never a device fault):
+ * 1 <= nreg <= 65535; nreg * nbins * sub-bins <= 2^24; every label in [0, nreg) (a device reduction over the labels runs
+ * before the sort); labels2 must be NULL for an autocorrelation (x2 == NULL), like w2.  Regions without points are fine:
+ * their rows are zero.  wsum_first / wsum_both: required on the box; on the light cone both NULL = integer counts only.
+ * abacus_paircount_stats reports the candidate pairs - the parent's for the same input and grid.
+ * _dev: coordinate columns in HBM (pos_dtype), w1 / w2 float32 and labels1 / labels2 int32 DEVICE pointers.
+ */
+int abacus_paircount_jk(int mode, const float *x1, const float *y1, const float *z1, const float *w1, const int32_t *labels1,
+                        int64_t n1, const float *x2, const float *y2, const float *z2, const float *w2, const int32_t *labels2,
+                        int64_t n2, int nreg, float boxsize, const float *bins, int nbins, float pimax, int npibins,
+                        float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both, double *wsum_first,
+                        double *wsum_both);
+int abacus_paircount_jk_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, const int32_t *labels1,
+                            int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2, const int32_t *labels2,
+                            int64_t n2, int pos_dtype, int nreg, float boxsize, const float *bins, int nbins, float pimax,
+                            int npibins, float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both,
+                            double *wsum_first, double *wsum_both);
+int abacus_paircount_los_jk(int mode, const float *x1, const float *y1, const float *z1, const float *w1, const int32_t *labels1,
+                            int64_t n1, const float *x2, const float *y2, const float *z2, const float *w2,
+                            const int32_t *labels2, int64_t n2, int nreg, const double *origin, const float *bins, int nbins,
+                            float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both,
+                            double *wsum_first, double *wsum_both);
+int abacus_paircount_los_jk_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, const int32_t *labels1,
+                                int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2,
+                                const int32_t *labels2, int64_t n2, int pos_dtype, int nreg, const double *origin,
+                                const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
+                                uint64_t *npairs_first, uint64_t *npairs_both, double *wsum_first, double *wsum_both);
+/* histogram flushes (summed over the workgroups and runs) and workgroups (of the last run) of the last jackknife call */
+int abacus_paircount_jk_stats(uint64_t *flushes, int *workgroups);
+/* labels of an nx x ny x nz split of the periodic box from resident columns (pos_dtype), into the int32 DEVICE array `labels`:
+ * (cx * ny + cy) * nz + cz with c = int(frac(float32(v) * (1 / boxsize)) * n) in float32, the fraction wrapped into [0, 1) as
+ * the counter's cell grid wraps it (a coordinate that rounds to boxsize lands in sub-box 0, not n), c clamped to [0, n - 1] */
+int abacus_jk_box_labels_dev(const void *x, const void *y, const void *z, int pos_dtype, int64_t n, float boxsize, int nx, int ny,
+                             int nz, int32_t *labels);
 
 /* ---------------------------------------------------------------- staging (the step in front of the HOD) ---- */
 /*
