@@ -34,7 +34,7 @@ import numpy as np
 from .. import _lib
 from .._lib import check, ptr
 from . import tpcf_corrfunc as tc
-from .tpcf_corrfunc import _f4
+from .tpcf_corrfunc import _f4, _i4
 
 MODES = {'r': 0, 'rppi': 1, 'smu': 2}
 calls = {'dev': 0, 'host': 0}      # counter calls so far, by where the columns were (tests: the resident path was taken)
@@ -60,10 +60,6 @@ class JKCounts:
         return self.first.npairs.shape[0]
 
 
-def _i4(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-
-
 def _check_labels(name, lab, n):
     if lab is None:
         raise ValueError(f'{name} is needed')
@@ -79,25 +75,18 @@ def _check_labels(name, lab, n):
 
 def _jk_counter(entry, mode, bins, cols, weights, labels, nreg, geom, pimax, npibins, mu_max, nmubins, want_sums=True,
                 host_prep=None):
-    """one call of `abacus_<entry>[_dev]` under the column rules of `tpcf_corrfunc._counter` (host arrays, or - all of them -
-    DeviceArray columns of one dtype; host weights and labels next to resident coordinates are uploaded, resident ones next to
-    host coordinates are refused).  Returns (npairs_first, npairs_both, wsum_first, wsum_both), each (nreg, nbins * nsub)"""
+    """one call of `abacus_<entry>[_dev]` under the column rules of `tpcf_corrfunc._call_on_columns`, which `_counter` follows
+    too.  Returns (npairs_first, npairs_both, wsum_first, wsum_both), each (nreg, nbins * nsub)"""
     mode = MODES.get(mode, mode)
     nb = len(bins) - 1
     nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
     if nb < 1 or nsub < 1:
         raise ValueError('need at least one separation bin and one pi / mu bin')
-    X1, X2 = cols[0], cols[3]
-    W1, W2 = weights
+    X2 = cols[3]
     L1, L2 = labels
-    if X2 is None and W2 is not None:
-        raise ValueError('weights2 given for an autocorrelation')
+    n1, n2 = tc._set_sizes(cols, weights)
     if X2 is None and L2 is not None:
         raise ValueError('labels2 given for an autocorrelation')
-    n1, n2 = len(X1), (0 if X2 is None else len(X2))
-    for name, w, n in (('weights1', W1, n1), ('weights2', W2, n2)):
-        if w is not None and (len(w.shape) != 1 or w.shape[0] != n):
-            raise ValueError(f'{name} has shape {tuple(w.shape)}, expected ({n},)')
     _check_labels('labels1', L1, n1)
     if X2 is not None:
         _check_labels('labels2', L2, n2)
@@ -114,35 +103,7 @@ def _jk_counter(entry, mode, bins, cols, weights, labels, nreg, geom, pimax, npi
                  *dt, int(nreg), *geom, *tail))
         shape = (int(nreg), nb * nsub)
         return nf.reshape(shape), nbo.reshape(shape), None if wf is None else wf.reshape(shape), None if wb is None else wb.reshape(shape)
-    given = [c for c in cols if c is not None]
-    if any(isinstance(c, _lib.DeviceArray) for c in given):
-        if not all(isinstance(c, _lib.DeviceArray) and c.dtype == given[0].dtype for c in given):
-            raise TypeError('device-resident coordinates: every column must be a DeviceArray of one dtype')
-        dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[given[0].dtype]
-        own = []
-
-        def dev(a, cast, what):
-            if a is None:
-                return None
-            if isinstance(a, _lib.DeviceArray):
-                if a.dtype != what:
-                    raise TypeError(f'device-resident weights must be float32, labels int32 (got {a.dtype})')
-                return a
-            own.append(_lib.DeviceArray(cast(a)))
-            return own[-1]
-        try:
-            calls['dev'] += 1
-            return call(getattr(_lib.lib(), f'abacus_{entry}_dev'), lambda c: None if c is None else c.ptr, cols,
-                        (dev(W1, _f4, np.float32), dev(W2, _f4, np.float32)), (dev(L1, _i4, np.int32), dev(L2, _i4, np.int32)), geom, dt)
-        finally:
-            for a in own:
-                a.free()
-    if any(isinstance(a, _lib.DeviceArray) for a in (W1, W2, L1, L2)):
-        raise TypeError('device-resident weights or labels need device-resident coordinates')
-    if host_prep is not None:
-        cols, geom = host_prep(cols, geom)
-    calls['host'] += 1
-    return call(getattr(_lib.lib(), f'abacus_{entry}'), ptr, [_f4(c) for c in cols], (_f4(W1), _f4(W2)), (_i4(L1), _i4(L2)), geom)
+    return tc._call_on_columns(entry, cols, weights, labels, geom, call, host_prep, calls)
 
 
 def _assemble(raw, exchanged, shape):
@@ -187,17 +148,7 @@ def paircount_los_jk(mode, X1, Y1, Z1, bins, labels1, nreg, X2=None, Y2=None, Z2
                      origin=(0.0, 0.0, 0.0), pimax=0.0, npibins=0, mu_max=1.0, nmubins=0, want_sums=True):
     """per-region pair counts on the light cone (`abacus_paircount_los_jk[_dev]`), columns and origin as `_paircount_los`;
     `want_sums` false: integer counts only (wsum None)"""
-    origin = np.ascontiguousarray(origin, dtype=np.float64)
-    if origin.shape != (3,):
-        raise ValueError(f'origin has shape {origin.shape}, expected (3,)')
-    zero = np.zeros(3)
-
-    def centre(cols, geom):     # as in `_paircount_los`: float64 host columns subtract in float64 here
-        host = [None if c is None else np.asarray(c) for c in cols]
-        if not any(c is not None and c.dtype == np.float64 for c in host):
-            return cols, geom
-        return [None if c is None else (c - c.dtype.type(origin[i % 3])).astype(np.float32) if c.dtype == np.float64
-                else _f4(c) - np.float32(origin[i % 3]) for i, c in enumerate(host)], (ptr(zero),)
+    origin, centre = tc._los_origin(origin)
     kw = dict(pimax=pimax, npibins=npibins, mu_max=mu_max, nmubins=nmubins)
     return _count_jk('paircount_los_jk', mode, bins, (X1, Y1, Z1), (X2, Y2, Z2), (W1, W2), (labels1, labels2), nreg, (ptr(origin),),
                      kw, want_sums, host_prep=centre)

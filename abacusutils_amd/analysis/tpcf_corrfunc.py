@@ -27,36 +27,30 @@ def _f4(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
 
 
-def _counter(entry, mode, bins, cols, weights, geom, pimax, npibins, mu_max, nmubins, want_sums=True, want_rsum=True,
-             host_prep=None):
-    """What the three counters below share.  `entry`: the C function `abacus_<entry>` (host columns) or `abacus_<entry>_dev`
-    (resident ones); `bins`: float32 edges; `cols` = (X1, Y1, Z1, X2, Y2, Z2); `weights` = (W1, W2), or None for an entry
-    without weight and sum arguments; `geom`: the ctypes arguments between the columns and the bins (box size | origin).
-    Columns are host arrays (cast to float32) or - all of them - DeviceArray columns of one dtype; a host weight array next
-    to resident coordinates is uploaded (float32), resident weights next to host coordinates are not accepted.
-    `host_prep(cols, geom)` -> (cols, geom), if given, has the last word on host columns, after every check.
-    Returns (npairs, wsum, rsum); the sums are None when not asked for."""
-    nb = len(bins) - 1
-    nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
-    out = np.zeros(nb * nsub, dtype=np.uint64)
-    wsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums else None
-    rsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums and want_rsum else None
+def _i4(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _set_sizes(cols, weights):
+    """(n1, n2) of `cols` = (X1, Y1, Z1, X2, Y2, Z2), after the checks of `weights` = (W1, W2) against them"""
     X1, X2 = cols[0], cols[3]
-    W1, W2 = weights or (None, None)
-    if X2 is None and W2 is not None:
+    if X2 is None and weights[1] is not None:
         raise ValueError('weights2 given for an autocorrelation')
     n1, n2 = len(X1), (0 if X2 is None else len(X2))
-    for name, w, n in (('weights1', W1, n1), ('weights2', W2, n2)):
+    for name, w, n in (('weights1', weights[0], n1), ('weights2', weights[1], n2)):
         if w is not None and (len(w.shape) != 1 or w.shape[0] != n):
             raise ValueError(f'{name} has shape {tuple(w.shape)}, expected ({n},)')
-    tail = (ptr(bins), int(nb), C.c_float(pimax), int(npibins), C.c_float(mu_max), int(nmubins), ptr(out))
-    if weights is not None:
-        tail += (ptr(wsum), ptr(rsum))
+    return n1, n2
 
-    def call(fn, p, cols, w1, w2, geom, *dt):
-        ws = ((p(w1),), (p(w2),)) if weights is not None else ((), ())
-        check(fn(int(mode), *map(p, cols[:3]), *ws[0], C.c_int64(n1), *map(p, cols[3:]), *ws[1], C.c_int64(n2), *dt, *geom, *tail))
-        return out, wsum, rsum
+
+def _call_on_columns(entry, cols, weights, labels, geom, call, host_prep=None, calls=None):
+    """The column rules of every pair counter, plain (`_counter`) and jackknife (`jackknife._jk_counter`).  Columns are host
+    arrays (cast to float32) or - all of them - DeviceArray columns of one dtype.  `weights` = (W1, W2) (float32) and `labels` =
+    (L1, L2) (int32) ride along: a host array next to resident coordinates is uploaded and freed after the call, a resident one
+    next to host coordinates is not accepted.  `host_prep(cols, geom)` -> (cols, geom), if given, has the last word on host
+    columns, after every check.  Returns call(fn, p, cols, weights, labels, geom, *dt): fn is `abacus_<entry>` (host columns)
+    or `abacus_<entry>_dev` (resident ones, dt = (pos_dtype,)), p turns an array into its pointer.  `calls`: a dict that counts
+    the calls by where the columns were."""
     given = [c for c in cols if c is not None]
     if any(isinstance(c, _lib.DeviceArray) for c in given):
         if not all(isinstance(c, _lib.DeviceArray) and c.dtype == given[0].dtype for c in given):
@@ -64,26 +58,54 @@ def _counter(entry, mode, bins, cols, weights, geom, pimax, npibins, mu_max, nmu
         dt = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}[given[0].dtype]
         own = []
 
-        def dev_w(w):
-            if w is None:
+        def dev(a, cast, what):
+            if a is None:
                 return None
-            if isinstance(w, _lib.DeviceArray):
-                if w.dtype != np.float32:
-                    raise TypeError('device-resident weights must be float32')
-                return w
-            own.append(_lib.DeviceArray(_f4(w)))
+            if isinstance(a, _lib.DeviceArray):
+                if a.dtype != what:
+                    raise TypeError(f'device-resident weights must be float32, labels int32 (got {a.dtype})')
+                return a
+            own.append(_lib.DeviceArray(cast(a)))
             return own[-1]
         try:
-            return call(getattr(_lib.lib(), f'abacus_{entry}_dev'), lambda c: None if c is None else c.ptr, cols, dev_w(W1),
-                        dev_w(W2), geom, dt)
+            if calls is not None:
+                calls['dev'] += 1
+            return call(getattr(_lib.lib(), f'abacus_{entry}_dev'), lambda c: None if c is None else c.ptr, cols,
+                        [dev(w, _f4, np.float32) for w in weights], [dev(lab, _i4, np.int32) for lab in labels], geom, dt)
         finally:
             for a in own:
                 a.free()
-    if isinstance(W1, _lib.DeviceArray) or isinstance(W2, _lib.DeviceArray):
-        raise TypeError('device-resident weights need device-resident coordinates')
+    if any(isinstance(a, _lib.DeviceArray) for a in (*weights, *labels)):
+        raise TypeError('device-resident weights or labels need device-resident coordinates')
     if host_prep is not None:
         cols, geom = host_prep(cols, geom)
-    return call(getattr(_lib.lib(), f'abacus_{entry}'), ptr, [_f4(c) for c in cols], _f4(W1), _f4(W2), geom)
+    if calls is not None:
+        calls['host'] += 1
+    return call(getattr(_lib.lib(), f'abacus_{entry}'), ptr, [_f4(c) for c in cols], [_f4(w) for w in weights],
+                [_i4(lab) for lab in labels], geom)
+
+
+def _counter(entry, mode, bins, cols, weights, geom, pimax, npibins, mu_max, nmubins, want_sums=True, want_rsum=True,
+             host_prep=None):
+    """What the three counters below share.  `entry`: the C function `abacus_<entry>[_dev]`; `bins`: float32 edges; `cols` =
+    (X1, Y1, Z1, X2, Y2, Z2); `weights` = (W1, W2), or None for an entry without weight and sum arguments; `geom`: the ctypes
+    arguments between the columns and the bins (box size | origin).  Columns, weights and `host_prep` as `_call_on_columns`
+    takes them.  Returns (npairs, wsum, rsum); the sums are None when not asked for."""
+    nb = len(bins) - 1
+    nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
+    out = np.zeros(nb * nsub, dtype=np.uint64)
+    wsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums else None
+    rsum = np.zeros(nb * nsub, dtype=np.float64) if want_sums and want_rsum else None
+    n1, n2 = _set_sizes(cols, weights or (None, None))
+    tail = (ptr(bins), int(nb), C.c_float(pimax), int(npibins), C.c_float(mu_max), int(nmubins), ptr(out))
+    if weights is not None:
+        tail += (ptr(wsum), ptr(rsum))
+
+    def call(fn, p, cols, w, lab, geom, *dt):
+        ws = ((p(w[0]),), (p(w[1]),)) if weights is not None else ((), ())
+        check(fn(int(mode), *map(p, cols[:3]), *ws[0], C.c_int64(n1), *map(p, cols[3:]), *ws[1], C.c_int64(n2), *dt, *geom, *tail))
+        return out, wsum, rsum
+    return _call_on_columns(entry, cols, weights or (None, None), (), geom, call, host_prep)
 
 
 def _paircount(mode, X1, Y1, Z1, boxsize, bins, X2=None, Y2=None, Z2=None, pimax=0.0, npibins=0, mu_max=1.0,
@@ -313,6 +335,14 @@ def _paircount_los(mode, X1, Y1, Z1, bins, X2=None, Y2=None, Z2=None, W1=None, W
     nsub = 1 if mode == 0 else (npibins if mode == 1 else nmubins)
     if nb < 1 or nsub < 1:
         raise ValueError('need at least one separation bin and one pi / mu bin')
+    origin, centre = _los_origin(origin)
+    return _counter('paircount_los', mode, bins, (X1, Y1, Z1, X2, Y2, Z2), (W1, W2), (ptr(origin),), pimax, npibins, mu_max,
+                    nmubins, want_sums=want_sums, want_rsum=want_rsum, host_prep=centre)
+
+
+def _los_origin(origin):
+    """the origin of a light-cone call as the C ABI takes it, and the `host_prep` of its counter (`_paircount_los`,
+    `jackknife.paircount_los_jk`)"""
     origin = np.ascontiguousarray(origin, dtype=np.float64)
     if origin.shape != (3,):
         raise ValueError(f'origin has shape {origin.shape}, expected (3,)')
@@ -325,8 +355,7 @@ def _paircount_los(mode, X1, Y1, Z1, bins, X2=None, Y2=None, Z2=None, W1=None, W
         # float64 columns: the subtraction in float64, one rounding to float32 - on the host, the C ABI takes float32 arrays
         return [None if c is None else (c - c.dtype.type(origin[i % 3])).astype(np.float32) if c.dtype == np.float64
                 else _f4(c) - np.float32(origin[i % 3]) for i, c in enumerate(host)], (ptr(zero),)
-    return _counter('paircount_los', mode, bins, (X1, Y1, Z1, X2, Y2, Z2), (W1, W2), (ptr(origin),), pimax, npibins, mu_max,
-                    nmubins, want_sums=want_sums, want_rsum=want_rsum, host_prep=centre)
+    return origin, centre
 
 
 def DD_los(autocorr, nthreads, binfile, X1, Y1, Z1, X2=None, Y2=None, Z2=None, origin=(0.0, 0.0, 0.0), **kw):

@@ -22,10 +22,11 @@
 //                             cell_fill / cell_gather / cell_starts (counting sort below 200 000 points, radix sort above)
 //   unweighted, periodic      pair_count (first generation: the comparator of the tests), pair_count2, pair_count3 (default)
 //   weighted and light cone   one walk in two bodies: pair_count_w (periodic, float32), pair_count_los (open grid, float64)
-//   host side                 one set of work buffers, stage_columns, sort_into_cells, launch helpers, the two drivers
-//                             paircount_impl and paircount_los_impl over one run loop, the C ABI
+//   host helpers              one set of work buffers, stage_columns, sort_into_cells, launch helpers, the run loop
 //   jackknife                 pair_count_jk / pair_count_los_jk (the two walks with per-region histograms), the label-aware
-//                             sort, the drivers paircount_jk_impl / paircount_los_jk_impl, abacus_jk_box_labels_dev
+//                             sort, the per-region outputs
+//   the two drivers           count_box (periodic) and count_los (open grid), each the plain and - with labels - the jackknife
+//                             counter; validation, grids, kernel arguments and statistics in one place each; the C ABI
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -1404,115 +1405,51 @@ void fill_sets(Args &a, Sums &s, int autocorr, int nbins, int nsub, const Output
     s.w1 = S1.sw, s.w2 = T.sw, s.wsum = d.wsum, s.rsum = d.rsum;
 }
 
-}  // namespace
+// The launches of a run, one function per walk; the two drivers (below the jackknife kernels) choose among them.  Each stands
+// behind the instantiation of its family's sort: the code object lists kernels in the order of their instantiation, and the
+// launches keep that order whichever driver calls them.
+template int sort_into_cells<FramedGrid>(const Columns &, int64_t, const FramedGrid &, int64_t, SortedSet &, DevBuf &);
 
-static unsigned long long g_last_evaluated = 0;   // candidate pairs of the last call (not of the first two generations)
-static int g_last_cells[3] = {0, 0, 0};
+int launch_weighted(const PairArgs &a, const WeightArgs &wa, bool rsum, const Flags &fl, int64_t ncell) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
+    return with_mode(a.mode, [&](auto M) {
+        return with_flag(rsum, [&](auto RS) -> int {
+            const auto kernel = pair_count_w<decltype(M)::value, decltype(RS)::value>;
+            dim3 grid;
+            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+            ABACUS_LAUNCH("pair_count_w", kernel, grid, dim3(PB), hist_bytes, a, wa, (int)ncell, fl.evaluated);
+            return 0;
+        });
+    });
+}
 
-// weighted: also wsum (and rsum unless NULL) per bin, by pair_count_w; w1 / w2 (host memory when where = 0, else device memory)
-// may be NULL: unit weights
-static int paircount_impl(int mode, const void *x1, const void *y1, const void *z1, int64_t n1, const void *x2, const void *y2,
-                          const void *z2, int64_t n2, int where, float boxsize, const float *bins, int nbins, float pimax,
-                          int npibins, float mu_max, int nmubins, uint64_t *npairs, int weighted = 0, const float *w1 = nullptr,
-                          const float *w2 = nullptr, double *wsum = nullptr, double *rsum = nullptr) {
-    ABACUS_ENTER();
-    if (mode < 0 || mode > 2) return fail("abacus_paircount: unknown mode %d", mode);
-    if (!x1 || !y1 || !z1 || !bins || !npairs || nbins < 1) return fail("abacus_paircount: null/empty argument");
-    if (!(boxsize > 0)) return fail("abacus_paircount: boxsize must be positive");
-    const int autocorr = x2 == nullptr;
-    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
-    if (nsub < 1) return fail("abacus_paircount: need at least one pi / mu bin");
-    const int max_hist = weighted ? W_MAX_HIST : MAX_HIST;
-    if (nsub > max_hist) return fail("abacus_paircount: %d pi / mu bins exceed the LDS histogram", nsub);
-    if (weighted && !wsum) return fail("abacus_paircount_weighted: wsum is NULL");
-    if (weighted && autocorr && w2) return fail("abacus_paircount_weighted: w2 given for an autocorrelation (x2 is NULL)");
-    if (n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("abacus_paircount: too many points");
-    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
-    const float *const srcw[2] = {w1, w2};
-    const int64_t ns[2] = {n1, n2};
-    const int nsets = autocorr ? 1 : 2;
+// The unweighted periodic count of a run by the generation asked for (pairs_gen; 1, 2: the comparators of the tests); R_used:
+// the stencil of pair_count3, 0 when an older kernel ran
+int launch_unweighted(PairArgs &a, int gen, int R, const std::vector<float> &e2, const Flags &fl, int64_t ncell, int &R_used) {
     Work &W = g_work;
-    // every run stages, sorts (the grid follows the run's reach) and counts
-    return for_runs(nbins, nsub, max_hist, [&](int b0, int nb, size_t o) -> int {
-        const float *edges = bins + b0;
-        const float rmax = edges[nb];
-        for (int b = 0; b < nb; b++)
-            if (!(edges[b + 1] > edges[b])) return fail("abacus_paircount: bin edges must increase");
-        const float reach_xy = rmax, reach_z = mode == 1 ? pimax : rmax;
-        if (reach_xy > 0.5f * boxsize || reach_z > 0.5f * boxsize)
-            return fail("abacus_paircount: maximum separation exceeds half the box (minimum image not unique)");
-        const size_t ntot = (size_t)nb * nsub;
-        const Outputs host = Outputs{npairs, wsum, rsum}.at(o);
-        host.zero(ntot);
-        if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
-
-        CellGrid g;
-        g.box = boxsize;
-        g.inv_box = 1.0f / boxsize;
-        // cells of size >= reach / R: R = 2 (125-cell stencil of cells an eighth the volume: 1.7x fewer candidate pairs) when
-        // the catalogue is dense enough to keep a wave busy with a small cell, else R = 1
-        const int gen = option("pairs_gen") ? option("pairs_gen") : 3;   // comparators: 1, 2 = the older kernels
-        auto ncells = [&](float reach, int R, int cap) {
-            int nc = (int)floorf(boxsize / reach * (float)R * 0.9999f);   // cell size strictly >= reach / R
-            nc = std::min(nc, cap);
-            return nc < 3 ? 1 : nc;
-        };
-        const bool v1 = gen == 1 && !weighted;   // first-generation kernel (comparator of the tests)
-        int R = 1;
-        if (!v1 && !weighted) {   // the weighted kernel walks 27 cells of the full reach
-            const double nmax = (double)std::max(n1, autocorr ? n1 : n2);
-            const double per_cell = nmax * ((double)reach_xy / boxsize) * ((double)reach_xy / boxsize) * ((double)reach_z / boxsize);
-            if (gen >= 3 && per_cell > 12.0 && ncells(reach_xy, 2, 192) >= 5 && ncells(reach_z, 2, 192) >= 5) R = 2;
-        }
-        g.ncx = g.ncy = ncells(reach_xy, R, R == 2 ? 192 : 128);
-        g.ncz = ncells(reach_z, R, R == 2 ? 192 : 128);
-        // the cap may leave cells larger than reach / R: still correct (a cell >= reach / R is all the stencil needs)
-        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-        const bool use3 = !v1 && !weighted && gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1;
-
-        Flags fl;
-        ABACUS_TRY(W.flags(fl));
-        for (int k = 0; k < nsets; k++) {
-            Columns c;
-            ABACUS_TRY(stage_columns("pair_cast", src[k], srcw[k], where, ns[k], nullptr, W.cols[k], W.wts[k], c));
-            ABACUS_TRY(sort_into_cells(c, ns[k], FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[k], W.scratch));
-        }
-        const SortedSet &S1 = W.S[0], &T = W.S[nsets - 1];
-
-        int nwork = 0, *d_wc = nullptr, *d_wo = nullptr;
-        if (v1) {   // first-generation kernel: host-built work list, one workgroup per 256 points of a non-empty cell
-            std::vector<int64_t> start1((size_t)ncell + 1);
-            HIP_TRY(hipMemcpyAsync(start1.data(), S1.start.p, (size_t)(ncell + 1) * 8, hipMemcpyDeviceToHost, stream()));
-            HIP_TRY(hipStreamSynchronize(stream()));
-            std::vector<int> wc, wo;
-            for (int64_t c = 0; c < ncell; c++)
-                for (int64_t off = 0; off < start1[c + 1] - start1[c]; off += PB) wc.push_back((int)c), wo.push_back((int)off);
-            nwork = (int)wc.size();
-            ABACUS_TRY(W.list.reserve((size_t)std::max(nwork, 1) * 8));
-            d_wc = W.list.as<int>(), d_wo = d_wc + std::max(nwork, 1);
-            HIP_TRY(hipMemcpyAsync(d_wc, wc.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
-            HIP_TRY(hipMemcpyAsync(d_wo, wo.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
-            HIP_TRY(hipStreamSynchronize(stream()));
-        }
-
-        std::vector<float> e2;
-        ABACUS_TRY(upload_edges(edges, nb, e2));
-        Outputs dev;
-        ABACUS_TRY(device_outputs(ntot, weighted != 0, dev));
-        PairArgs a;
-        WeightArgs wa;
-        fill_sets(a, wa, autocorr, nb, nsub, dev);
-        a.mode = mode;
-        a.in_box = 1;   // (no kernel reads it: pair_count2 takes the device flag)
-        a.g = g;
-        a.half = boxsize * 0.5f;
-        a.pimax = pimax;
-        a.dpi = npibins > 0 ? pimax / (float)npibins : 1.0f;
-        a.mu_max = mu_max;
-        a.inv_dmu = nmubins > 0 ? (float)nmubins / mu_max : 1.0f;
-        a.edges2 = W.edges.as<float>();
+    const CellGrid &g = a.g;
+    const int nb = a.nbins;
+    const size_t ntot = (size_t)nb * a.nsub;
+    R_used = 0;
+    if (gen == 1) {   // first-generation kernel: host-built work list, one workgroup per 256 points of a non-empty cell
+        std::vector<int64_t> start1((size_t)ncell + 1);
+        HIP_TRY(hipMemcpyAsync(start1.data(), W.S[0].start.p, (size_t)(ncell + 1) * 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        std::vector<int> wc, wo;
+        for (int64_t c = 0; c < ncell; c++)
+            for (int64_t off = 0; off < start1[c + 1] - start1[c]; off += PB) wc.push_back((int)c), wo.push_back((int)off);
+        const int nwork = (int)wc.size();
+        ABACUS_TRY(W.list.reserve((size_t)std::max(nwork, 1) * 8));
+        int *d_wc = W.list.as<int>(), *d_wo = d_wc + std::max(nwork, 1);
+        HIP_TRY(hipMemcpyAsync(d_wc, wc.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
+        HIP_TRY(hipMemcpyAsync(d_wo, wo.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
+        return 0;
+    }
+    if (gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1) {
+        R_used = R;
         // cells of the bin table: the coarsest 2^m per octave (m = 2 .. 8) that keep the inner edges apart, at most 8192 cells
-        a.lut_sh = a.lut_off = a.lut_ncell = 0;
         a.no_blocks = option("pairs_noblocks");
         if (!option("pairs_nolut") && e2[0] >= 0.f) {
             auto fbits = [](float v) {
@@ -1530,249 +1467,55 @@ static int paircount_impl(int mode, const void *x1, const void *y1, const void *
                 if (ok) a.lut_sh = sh, a.lut_off = (int)c0, a.lut_ncell = (int)(c1 - c0 + 1);
             }
         }
-        if (weighted) {
-            const size_t hist_bytes = ntot * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
-            ABACUS_TRY(with_mode(mode, [&](auto M) {
-                return with_flag(rsum != nullptr, [&](auto RS) -> int {
-                    const auto kernel = pair_count_w<decltype(M)::value, decltype(RS)::value>;
-                    dim3 grid;
-                    ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-                    ABACUS_LAUNCH("pair_count_w", kernel, grid, dim3(PB), hist_bytes, a, wa, (int)ncell, fl.evaluated);
-                    return 0;
-                });
-            }));
-        } else if (v1) {
-            if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
-        } else if (use3) {
-            const bool lut = a.lut_ncell > 0;
-            const size_t hist_bytes = ((ntot + 1) & ~(size_t)1) * sizeof(unsigned int) + (size_t)a.lut_ncell * sizeof(uint2);
-            ABACUS_TRY(with_mode(mode, [&](auto M) {
-                return with_flag(lut, [&](auto LUT) -> int {
-                    const auto kernel = pair_count3<decltype(M)::value, decltype(LUT)::value>;
-                    if (hist_bytes > 48 * 1024)
-                        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-                    dim3 grid;   // persistent waves: as many workgroups as are resident at once
-                    ABACUS_TRY(resident_grid(kernel, P3_WAVES * 64, hist_bytes, ceil_div(ncell, P3_WAVES), grid));
-                    ABACUS_LAUNCH("pair_count", kernel, grid, dim3(P3_WAVES * 64), hist_bytes, a, fl.frame, (int)ncell, R, fl.evaluated);
-                    return 0;
-                });
-            }));
-        } else {
-            int ncu = 256;
-            ABACUS_TRY(cu_count(ncu));
-            const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * 8));
-            const size_t hist_bytes = ntot * sizeof(unsigned int);
-            // a few points per cell: stage all neighbour cells together (one round per slice instead of 27)
-            const bool agg = (double)T.n / (double)ncell < 12.0;
-            ABACUS_TRY(with_mode(mode, [&](auto M) {
-                return with_flag(agg, [&](auto AGG) -> int {
-                    ABACUS_LAUNCH("pair_count", (pair_count2<decltype(M)::value, decltype(AGG)::value>), grid, dim3(PB), hist_bytes, a,
-                                  (const int *)fl.outside, (int)ncell);
-                    return 0;
-                });
-            }));
-        }
-        ABACUS_TRY(fetch_outputs(host, dev, ntot));
-        g_last_evaluated = 0;
-        HIP_TRY(hipMemcpyAsync(&g_last_evaluated, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = use3 ? R : 0;
-        return 0;
+        const bool lut = a.lut_ncell > 0;
+        const size_t hist_bytes = ((ntot + 1) & ~(size_t)1) * sizeof(unsigned int) + (size_t)a.lut_ncell * sizeof(uint2);
+        return with_mode(a.mode, [&](auto M) {
+            return with_flag(lut, [&](auto LUT) -> int {
+                const auto kernel = pair_count3<decltype(M)::value, decltype(LUT)::value>;
+                if (hist_bytes > 48 * 1024)
+                    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
+                dim3 grid;   // persistent waves: as many workgroups as are resident at once
+                ABACUS_TRY(resident_grid(kernel, P3_WAVES * 64, hist_bytes, ceil_div(ncell, P3_WAVES), grid));
+                ABACUS_LAUNCH("pair_count", kernel, grid, dim3(P3_WAVES * 64), hist_bytes, a, fl.frame, (int)ncell, R, fl.evaluated);
+                return 0;
+            });
+        });
+    }
+    int ncu = 256;
+    ABACUS_TRY(cu_count(ncu));
+    const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * 8));
+    const size_t hist_bytes = ntot * sizeof(unsigned int);
+    // a few points per cell: stage all neighbour cells together (one round per slice instead of 27)
+    const bool agg = (double)W.S[a.autocorr ? 0 : 1].n / (double)ncell < 12.0;
+    return with_mode(a.mode, [&](auto M) {
+        return with_flag(agg, [&](auto AGG) -> int {
+            ABACUS_LAUNCH("pair_count", (pair_count2<decltype(M)::value, decltype(AGG)::value>), grid, dim3(PB), hist_bytes, a,
+                          (const int *)fl.outside, (int)ncell);
+            return 0;
+        });
     });
 }
 
-extern "C" int abacus_paircount(int mode, const float *x1, const float *y1, const float *z1, int64_t n1,
-                                const float *x2, const float *y2, const float *z2, int64_t n2, float boxsize,
-                                const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
-                                uint64_t *npairs) {
-    return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, 0, boxsize, bins, nbins, pimax, npibins, mu_max, nmubins, npairs);
-}
+template int sort_into_cells<OpenGrid>(const Columns &, int64_t, const OpenGrid &, int64_t, SortedSet &, DevBuf &);
 
-extern "C" int abacus_paircount_dev(int mode, const void *x1, const void *y1, const void *z1, int64_t n1, const void *x2,
-                                    const void *y2, const void *z2, int64_t n2, int pos_dtype, float boxsize, const float *bins,
-                                    int nbins, float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, pos_dtype == ABACUS_F32 ? 1 : 2, boxsize, bins, nbins, pimax,
-                          npibins, mu_max, nmubins, npairs);
-}
-
-extern "C" int abacus_paircount_weighted(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
-                                         const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,
-                                         float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max,
-                                         int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
-    return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, 0, boxsize, bins, nbins, pimax, npibins, mu_max, nmubins, npairs, 1,
-                          w1, w2, wsum, rsum);
-}
-
-extern "C" int abacus_paircount_weighted_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
-                                             const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2,
-                                             int pos_dtype, float boxsize, const float *bins, int nbins, float pimax, int npibins,
-                                             float mu_max, int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64)
-        return fail("abacus_paircount_weighted_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    return paircount_impl(mode, x1, y1, z1, n1, x2, y2, z2, n2, pos_dtype == ABACUS_F32 ? 1 : 2, boxsize, bins, nbins, pimax,
-                          npibins, mu_max, nmubins, npairs, 1, w1, w2, wsum, rsum);
-}
-
-extern "C" int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z, int *stencil_R) {
-    ABACUS_ENTER();
-    if (candidates) *candidates = g_last_evaluated;
-    if (ncell_xy) *ncell_xy = g_last_cells[0];
-    if (ncell_z) *ncell_z = g_last_cells[1];
-    if (stencil_R) *stencil_R = g_last_cells[2];
-    return 0;
-}
-
-// ---------------------------------------------------------------- light cones: abacus_paircount_los ----
-static int g_los_cells[3] = {0, 0, 0};
-
-static float funkey_host(unsigned int k) {
-    const unsigned int u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float v;
-    memcpy(&v, &u, 4);
-    return v;
-}
-
-// where = 0: host float32 arrays (and host weights); 1: device float32; 2: device float64 (device weights)
-static int paircount_los_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
-                              const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int where,
-                              const double *origin, const float *bins, int nbins, float pimax, int npibins, float mu_max,
-                              int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
-    // every argument is checked before the device is touched
-    if (mode < 0 || mode > 2) return fail("%s: unknown mode %d", who, mode);
-    if (!x1 || !y1 || !z1 || !origin || !bins || !npairs) return fail("%s: null argument", who);
-    if (nbins < 1) return fail("%s: nbins must be at least 1", who);
-    const int autocorr = x2 == nullptr;
-    if (!autocorr && (!y2 || !z2)) return fail("%s: null argument (y2 / z2)", who);
-    if (autocorr && w2) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
-    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
-    if (!(bins[0] >= 0.f)) return fail("%s: bin edges must not be negative", who);
-    for (int b = 0; b < nbins; b++)
-        if (!(bins[b + 1] > bins[b])) return fail("%s: bin edges must increase", who);
-    if (mode == 1 && (!(pimax > 0.f) || npibins < 1)) return fail("%s: pimax must be positive, with at least one pi bin", who);
-    if (mode == 2 && (!(mu_max > 0.f) || nmubins < 1)) return fail("%s: mu_max must be positive, with at least one mu bin", who);
-    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
-    if (nsub > W_MAX_HIST) return fail("%s: %d pi / mu bins exceed the LDS histogram", who, nsub);
-    for (int d = 0; d < 3; d++)
-        if (!std::isfinite(origin[d])) return fail("%s: origin must be finite", who);
-    ABACUS_ENTER();
-    const bool weighted = wsum != nullptr, rs = weighted && rsum != nullptr;   // wsum == NULL: integer counts only
-    const Outputs result{npairs, wsum, rs ? rsum : nullptr};
-    result.zero((size_t)nbins * nsub);
-    g_last_evaluated = 0;
-    g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
-    g_los_cells[0] = g_los_cells[1] = g_los_cells[2] = 0;
-    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
-
-    // observer-centred float32 columns of both sets in HBM, and their bounding box: one reduction, 24 bytes to the host
-    Work &W = g_work;
-    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
-    const float *const srcw[2] = {weighted ? w1 : nullptr, weighted ? w2 : nullptr};
-    const int64_t ns[2] = {n1, n2};
-    const int nsets = autocorr ? 1 : 2;
-    Columns cols[2];
-    Flags fl;
-    ABACUS_TRY(W.flags(fl));
-    for (int k = 0; k < nsets; k++) {
-        ABACUS_TRY(stage_columns("pair_los_centre", src[k], srcw[k], where, ns[k], origin, W.cols[k], W.wts[k], cols[k]));
-        ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
-                      cols[k].x[0], cols[k].x[1], cols[k].x[2], ns[k], fl.frame);
-    }
-    Frame fr;
-    HIP_TRY(hipMemcpyAsync(&fr, fl.frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
-    double lo[3], extent[3];
-    for (int d = 0; d < 3; d++) {
-        lo[d] = (double)funkey_host(fr.mn[d]);
-        extent[d] = (double)funkey_host(fr.mx[d]) - lo[d];
-        if (!(extent[d] >= 0.0) || !std::isfinite(extent[d]) || !std::isfinite(lo[d])) return fail("%s: coordinates are not finite", who);
-    }
-
-    // the columns above and the bounding box serve every run; a run sorts them into a grid of its own reach and counts
-    unsigned long long evaluated = 0;
-    ABACUS_TRY(for_runs(nbins, nsub, W_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
-        const size_t ntot = (size_t)nb * nsub;
-        std::vector<double> e2;
-        ABACUS_TRY(upload_edges(bins + b0, nb, e2));
-        const double reach2 = mode == 1 ? e2[nb] + (double)pimax * (double)pimax : e2[nb];
-        const double reach = std::nextafter(std::sqrt(reach2), HUGE_VAL);   // rounded up
-        OpenGrid og;
-        for (int d = 0; d < 3; d++) {
-            const double fit = std::floor(extent[d] / (reach * 1.0001));    // cell side >= 1.0001 reach (see OpenGrid)
-            og.nc[d] = (int)std::min(128.0, std::max(1.0, fit));
-            og.lo[d] = (float)lo[d];                                         // exact: a float32 coordinate
-            og.inv[d] = extent[d] > 0.0 ? (float)((double)og.nc[d] / extent[d]) : 0.f;
-        }
-        const int64_t ncell = (int64_t)og.nc[0] * og.nc[1] * og.nc[2];
-        for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells(cols[k], ns[k], og, ncell, W.S[k], W.scratch));
-
-        Outputs dev;
-        ABACUS_TRY(device_outputs(ntot, true, dev));
-        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
-        LosArgs a;
-        fill_sets(a, a, autocorr, nb, nsub, dev);
-        for (int d = 0; d < 3; d++) a.nc[d] = og.nc[d];
-        // the pre-test's thresholds (derivation at the kernel): rounded away from the accepted range
-        const double hi_d = reach2 * (1.0 + 0x1p-20), lo_d = e2[0] * (1.0 - 0x1p-20);
-        float hi_f = (float)hi_d, lo_f = (float)lo_d;
-        if ((double)hi_f < hi_d) hi_f = std::nextafterf(hi_f, HUGE_VALF);
-        if ((double)lo_f > lo_d) lo_f = std::nextafterf(lo_f, 0.f);
-        a.pre_hi = hi_f;
-        a.pre_lo = mode != 1 && lo_d >= 1e-30 ? lo_f : 0.f;
-        a.pimax = (double)pimax;
-        a.dpi = npibins > 0 ? (double)pimax / npibins : 1.0;
-        a.mu_max = (double)mu_max;
-        a.inv_dmu = nmubins > 0 ? nmubins / (double)mu_max : 1.0;
-        a.edges2 = W.edges.as<double>();
-        const size_t hist_bytes = ntot * (4 + (weighted ? 8 : 0) + (rs ? 8 : 0));
-        auto launch = [&](auto M, auto WT, auto RS) -> int {
-            const auto kernel = pair_count_los<decltype(M)::value, decltype(WT)::value, decltype(RS)::value>;
-            dim3 grid;
-            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-            ABACUS_LAUNCH("pair_count_los", kernel, grid, dim3(PB), hist_bytes, a, (int)ncell, fl.evaluated);
-            return 0;
-        };
-        ABACUS_TRY(with_mode(mode, [&](auto M) {
-            if (rs) return launch(M, std::true_type(), std::true_type());
-            if (weighted) return launch(M, std::true_type(), std::false_type());
-            return launch(M, std::false_type(), std::false_type());
-        }));
-        unsigned long long ev = 0;
-        ABACUS_TRY(fetch_outputs(result.at(o), dev, ntot));
-        HIP_TRY(hipMemcpyAsync(&ev, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        evaluated += ev;
-        g_last_cells[0] = og.nc[0], g_last_cells[1] = og.nc[2], g_last_cells[2] = 0;
-        for (int d = 0; d < 3; d++) g_los_cells[d] = og.nc[d];
+// weighted: with sums of w w; rs: and of the separation
+int launch_los(int mode, const LosArgs &a, bool weighted, bool rs, const Flags &fl, int64_t ncell) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * (4 + (weighted ? 8 : 0) + (rs ? 8 : 0));
+    auto launch = [&](auto M, auto WT, auto RS) -> int {
+        const auto kernel = pair_count_los<decltype(M)::value, decltype(WT)::value, decltype(RS)::value>;
+        dim3 grid;
+        ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+        ABACUS_LAUNCH("pair_count_los", kernel, grid, dim3(PB), hist_bytes, a, (int)ncell, fl.evaluated);
         return 0;
-    }));
-    g_last_evaluated = evaluated;
-    return 0;
+    };
+    return with_mode(mode, [&](auto M) {
+        if (rs) return launch(M, std::true_type(), std::true_type());
+        if (weighted) return launch(M, std::true_type(), std::false_type());
+        return launch(M, std::false_type(), std::false_type());
+    });
 }
 
-extern "C" int abacus_paircount_los(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
-                                    const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,
-                                    const double *origin, const float *bins, int nbins, float pimax, int npibins, float mu_max,
-                                    int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
-    return paircount_los_impl("abacus_paircount_los", mode, x1, y1, z1, w1, n1, x2, y2, z2, w2, n2, 0, origin, bins, nbins, pimax,
-                              npibins, mu_max, nmubins, npairs, wsum, rsum);
-}
-
-extern "C" int abacus_paircount_los_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
-                                        const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int pos_dtype,
-                                        const double *origin, const float *bins, int nbins, float pimax, int npibins,
-                                        float mu_max, int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_los_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    return paircount_los_impl("abacus_paircount_los_dev", mode, x1, y1, z1, w1, n1, x2, y2, z2, w2, n2, pos_dtype == ABACUS_F32 ? 1 : 2,
-                              origin, bins, nbins, pimax, npibins, mu_max, nmubins, npairs, wsum, rsum);
-}
-
-extern "C" int abacus_paircount_los_grid(int *ncell) {
-    ABACUS_ENTER();
-    if (!ncell) return fail("abacus_paircount_los_grid: null argument");
-    for (int d = 0; d < 3; d++) ncell[d] = g_los_cells[d];
-    return 0;
-}
+}  // namespace
 
 // a device column, observer-centred: dst = float32(src - origin), the subtraction in the column's dtype (the estimators of
 // analysis/tpcf_corrfunc.py centre a sample once and count it against several others)
@@ -2367,104 +2110,418 @@ void jk_zero(const JkHostOut &h, size_t cnt) {
     if (h.wfirst) memset(h.wfirst, 0, cnt * 8), memset(h.wboth, 0, cnt * 8);
 }
 
-}  // namespace
+// The jackknife launches of a run, like those of the plain walks above; out: the run's columns of the [nreg][ntot] block.
+// They take fewer workgroups on request (pairs_jk_grid, tests: many cells per workgroup) and report how many they took.
+void cap_jk_grid(dim3 &grid) {
+    if (option("pairs_jk_grid") > 0) grid.x = std::min<unsigned int>(grid.x, (unsigned int)option("pairs_jk_grid"));
+}
 
-static unsigned long long g_jk_flushes = 0;
-static int g_jk_workgroups = 0;
+template int sort_into_cells_jk<CellGrid>(const Columns &, const int *, int64_t, const CellGrid &, int64_t, int, int);
 
-static int paircount_jk_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1,
-                             const int32_t *labels1, int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2,
-                             const int32_t *labels2, int64_t n2, int where, int nreg, float boxsize, const float *bins, int nbins,
-                             float pimax, int npibins, float mu_max, int nmubins, JkHostOut host) {
-    // every argument is checked before the device is touched
-    if (mode < 0 || mode > 2) return fail("%s: unknown mode %d", who, mode);
-    if (!x1 || !y1 || !z1 || !bins || nbins < 1) return fail("%s: null/empty argument", who);
-    if (!(boxsize > 0)) return fail("%s: boxsize must be positive", who);
-    const int autocorr = x2 == nullptr;
-    if (!autocorr && (!y2 || !z2)) return fail("%s: null argument (y2 / z2)", who);
-    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
-    if (nsub < 1) return fail("%s: need at least one pi / mu bin", who);
-    if (autocorr && w2) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
-    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
-    ABACUS_TRY(jk_check(who, nreg, nbins, nsub, autocorr, labels1, labels2, n1, n2, host, true));
-    for (int b = 0; b < nbins; b++)
-        if (!(bins[b + 1] > bins[b])) return fail("%s: bin edges must increase", who);
-    if (bins[nbins] > 0.5f * boxsize || (mode == 1 && pimax > 0.5f * boxsize))
-        return fail("%s: maximum separation exceeds half the box (minimum image not unique)", who);
-    ABACUS_ENTER();
-    const size_t ntot_all = (size_t)nbins * nsub;
-    jk_zero(host, (size_t)nreg * ntot_all);
-    g_last_evaluated = 0, g_jk_flushes = 0, g_jk_workgroups = 0;
-    g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
-    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
+int launch_jk(const PairArgs &a, const WeightArgs &wa, const int *lab1, const int *lab2, const JkOut &out, const Flags &fl, int64_t ncell,
+              int &workgroups) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 24;   // <= JK_MAX_HIST * 24 = 48 KiB beside 6 KiB of static LDS
+    return with_mode(a.mode, [&](auto M) -> int {
+        const auto kernel = pair_count_jk<decltype(M)::value>;
+        dim3 grid;
+        ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+        cap_jk_grid(grid);
+        ABACUS_LAUNCH("pair_count_jk", kernel, grid, dim3(PB), hist_bytes, a, wa, lab1, lab2, out, (int)ncell, fl.evaluated);
+        workgroups = (int)grid.x;
+        return 0;
+    });
+}
 
-    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
-    const float *const srcw[2] = {w1, w2};
-    const int32_t *const srcl[2] = {labels1, labels2};
-    const int64_t ns[2] = {n1, n2};
-    const int nsets = autocorr ? 1 : 2;
-    Work &W = g_work;
-    const int *dl[2] = {nullptr, nullptr};
-    ABACUS_TRY(jk_stage_labels(who, srcl, ns, nsets, where, nreg, dl));
-    Flags fl;
-    ABACUS_TRY(W.flags(fl));
-    unsigned long long *flushes = fl.evaluated + 1;   // the block of flags has room behind the candidate count
-    JkOut dev;
-    ABACUS_TRY(jk_device_outputs(nreg, ntot_all, true, dev, flushes));
-    Columns cols[2];
-    for (int k = 0; k < nsets; k++) ABACUS_TRY(stage_columns("pair_cast", src[k], srcw[k], where, ns[k], nullptr, W.cols[k], W.wts[k], cols[k]));
-    // every run sorts (the grid follows the run's reach) and counts
-    ABACUS_TRY(for_runs(nbins, nsub, JK_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
-        const float *edges = bins + b0;
-        const float reach_xy = edges[nb], reach_z = mode == 1 ? pimax : edges[nb];
-        CellGrid g;
-        g.box = boxsize;
-        g.inv_box = 1.0f / boxsize;
-        auto ncells = [&](float reach) {   // the weighted counter's grid: cells of the full reach
-            const int nc = std::min((int)floorf(boxsize / reach * 0.9999f), 128);
-            return nc < 3 ? 1 : nc;
-        };
-        g.ncx = g.ncy = ncells(reach_xy);
-        g.ncz = ncells(reach_z);
-        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-        for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells_jk(cols[k], dl[k], ns[k], g, ncell, nreg, k));
-        std::vector<float> e2;
-        ABACUS_TRY(upload_edges(edges, nb, e2));
-        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
-        PairArgs a;
-        WeightArgs wa;
-        fill_sets(a, wa, autocorr, nb, nsub, Outputs{nullptr, nullptr, nullptr});
-        a.mode = mode;
-        a.in_box = 1;
-        a.g = g;
-        a.half = boxsize * 0.5f;
-        a.pimax = pimax;
-        a.dpi = npibins > 0 ? pimax / (float)npibins : 1.0f;
-        a.mu_max = mu_max;
-        a.inv_dmu = nmubins > 0 ? (float)nmubins / mu_max : 1.0f;
-        a.edges2 = W.edges.as<float>();
-        a.lut_sh = a.lut_off = a.lut_ncell = 0;
-        a.no_blocks = 0;
-        const size_t hist_bytes = (size_t)nb * nsub * 24;   // <= JK_MAX_HIST * 24 = 48 KiB beside 6 KiB of static LDS
-        ABACUS_TRY(with_mode(mode, [&](auto M) -> int {
-            const auto kernel = pair_count_jk<decltype(M)::value>;
+template int sort_into_cells_jk<OpenGrid>(const Columns &, const int *, int64_t, const OpenGrid &, int64_t, int, int);
+
+int launch_los_jk(int mode, const LosArgs &a, bool weighted, const int *lab1, const int *lab2, const JkOut &out, const Flags &fl,
+                  int64_t ncell, int &workgroups) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * (weighted ? 24 : 8);
+    return with_mode(mode, [&](auto M) {
+        return with_flag(weighted, [&](auto WT) -> int {
+            const auto kernel = pair_count_los_jk<decltype(M)::value, decltype(WT)::value>;
             dim3 grid;
             ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-            if (option("pairs_jk_grid") > 0) grid.x = std::min<unsigned int>(grid.x, (unsigned int)option("pairs_jk_grid"));   // tests: many cells per workgroup
-            ABACUS_LAUNCH("pair_count_jk", kernel, grid, dim3(PB), hist_bytes, a, wa, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(dev, o), (int)ncell,
-                          fl.evaluated);
-            g_jk_workgroups = (int)grid.x;
+            cap_jk_grid(grid);
+            ABACUS_LAUNCH("pair_count_los_jk", kernel, grid, dim3(PB), hist_bytes, a, lab1, lab2, out, (int)ncell, fl.evaluated);
+            workgroups = (int)grid.x;
             return 0;
-        }));
-        HIP_TRY(hipMemcpyAsync(&g_last_evaluated, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        g_last_cells[0] = g.ncx, g_last_cells[1] = g.ncz, g_last_cells[2] = 0;
-        return 0;
-    }));
-    ABACUS_TRY(jk_fetch(host, dev, (size_t)nreg * ntot_all));
-    HIP_TRY(hipMemcpyAsync(&g_jk_flushes, flushes, 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
+        });
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ the two drivers ----
+// A call as an entry point hands it on.  count_box (periodic) and count_los (open grid) serve the twelve entries; with a
+// JkSpec they are the jackknife counters, without one the plain ones.  Inside a run they part only for the sort (labels ride
+// along or not), the launch, and the device outputs (a block per run, or one [nreg][ntot] block of which a run takes columns).
+struct PointSet {
+    const void *x[3];
+    const float *w;   // NULL: unit weights
+    int64_t n;
+};
+struct Binning {
+    int mode;
+    const float *bins;
+    int nbins;
+    float pimax;
+    int npibins;
+    float mu_max;
+    int nmubins;
+    int nsub() const { return mode == 0 ? 1 : (mode == 1 ? npibins : nmubins); }
+};
+struct JkSpec {
+    const int32_t *labels[2];
+    int nreg;
+    JkHostOut out;
+};
+struct PairCall {
+    const char *who;     // the entry point that was called, for its messages
+    PointSet set[2];     // set[1].x[0] == NULL: autocorrelation
+    int where;           // 0: host float32 arrays (and host weights, labels); 1: device float32; 2: device float64; < 0: neither
+    Binning bin;
+    Outputs out;         // of a plain call
+    const JkSpec *jk;    // NULL: a plain call
+    int autocorr() const { return set[1].x[0] == nullptr; }
+    bool empty() const { return set[0].n == 0 || (!autocorr() && set[1].n == 0); }
+};
+int where_of(int pos_dtype) { return pos_dtype == ABACUS_F32 ? 1 : (pos_dtype == ABACUS_F64 ? 2 : -1); }
+
+// Validation, before the device is touched.  check_box and check_los hold the rules of their family; both start with
+// check_sets_and_bins and end the output rules with check_outputs.
+int check_sets_and_bins(const PairCall &c, bool other_null) {
+    const char *who = c.who;
+    const Binning &b = c.bin;
+    const PointSet &s1 = c.set[0], &s2 = c.set[1];
+    if (c.where < 0) return fail("%s: pos_dtype must be ABACUS_F32 or ABACUS_F64", who);
+    if (b.mode < 0 || b.mode > 2) return fail("%s: unknown mode %d", who, b.mode);
+    if (!s1.x[0] || !s1.x[1] || !s1.x[2] || !b.bins || other_null || (!c.jk && !c.out.npairs)) return fail("%s: null argument", who);
+    if (b.nbins < 1) return fail("%s: nbins must be at least 1", who);
+    if (!c.autocorr() && (!s2.x[1] || !s2.x[2])) return fail("%s: null argument (y2 / z2)", who);
+    if (c.autocorr() && s2.w) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
+    if (s1.n < 0 || s2.n < 0 || s1.n >= ((int64_t)1 << 31) || s2.n >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
+    for (int k = 0; k < b.nbins; k++)
+        if (!(b.bins[k + 1] > b.bins[k])) return fail("%s: bin edges must increase", who);
     return 0;
+}
+int check_outputs(const PairCall &c, int plain_hist, bool need_sums) {
+    const int nsub = c.bin.nsub();
+    if (!c.jk) return nsub > plain_hist ? fail("%s: %d pi / mu bins exceed the LDS histogram", c.who, nsub) : 0;
+    return jk_check(c.who, c.jk->nreg, c.bin.nbins, nsub, c.autocorr(), c.jk->labels[0], c.jk->labels[1], c.set[0].n, c.set[1].n, c.jk->out,
+                    need_sums);
+}
+int check_box(const PairCall &c, float boxsize, bool weighted) {
+    const Binning &b = c.bin;
+    ABACUS_TRY(check_sets_and_bins(c, false));
+    if (!(boxsize > 0)) return fail("%s: boxsize must be positive", c.who);
+    if (b.nsub() < 1) return fail("%s: need at least one pi / mu bin", c.who);
+    ABACUS_TRY(check_outputs(c, weighted ? W_MAX_HIST : MAX_HIST, true));
+    if (!c.jk && weighted && !c.out.wsum) return fail("%s: wsum is NULL", c.who);
+    // the edges increase: the last one is the reach of every run
+    if (b.bins[b.nbins] > 0.5f * boxsize || (b.mode == 1 && b.pimax > 0.5f * boxsize))
+        return fail("%s: maximum separation exceeds half the box (minimum image not unique)", c.who);
+    return 0;
+}
+int check_los(const PairCall &c, const double *origin) {
+    const Binning &b = c.bin;
+    ABACUS_TRY(check_sets_and_bins(c, origin == nullptr));
+    if (!(b.bins[0] >= 0.f)) return fail("%s: bin edges must not be negative", c.who);
+    if (b.mode == 1 && (!(b.pimax > 0.f) || b.npibins < 1)) return fail("%s: pimax must be positive, with at least one pi bin", c.who);
+    if (b.mode == 2 && (!(b.mu_max > 0.f) || b.nmubins < 1)) return fail("%s: mu_max must be positive, with at least one mu bin", c.who);
+    ABACUS_TRY(check_outputs(c, W_MAX_HIST, false));
+    for (int d = 0; d < 3; d++)
+        if (!std::isfinite(origin[d])) return fail("%s: origin must be finite", c.who);
+    return 0;
+}
+
+// Bookkeeping of the last call (abacus_paircount_stats, abacus_paircount_los_grid, abacus_paircount_jk_stats): zero when a call
+// starts, so what an empty or a refused-on-the-device call leaves is zero in all of them
+struct Stats {
+    unsigned long long evaluated = 0, flushes = 0;   // candidate pairs (not of the first two generations); jackknife flushes
+    int cells[3] = {0, 0, 0};                        // cells in xy, in z, stencil half-width R (0: not pair_count3)
+    int los_cells[3] = {0, 0, 0};
+    int workgroups = 0;
+} g_stats;
+
+// A run's candidate count and, behind it in the block of flags, the flush count of the jackknife kernels (over the call so
+// far; 0 from any other kernel) come to the host with the run's synchronise; `sum`: the candidates add up over the runs (light
+// cone), else the last run's stand.  workgroups: of a jackknife launch
+int record_run(const Flags &fl, bool sum, int ncxy, int ncz, int R, const int *los_nc, int workgroups) {
+    unsigned long long ctr[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(ctr, fl.evaluated, 16, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    g_stats.evaluated = (sum ? g_stats.evaluated : 0) + ctr[0];
+    g_stats.flushes = ctr[1];
+    g_stats.cells[0] = ncxy, g_stats.cells[1] = ncz, g_stats.cells[2] = R;
+    for (int d = 0; d < 3 && los_nc; d++) g_stats.los_cells[d] = los_nc[d];
+    g_stats.workgroups = workgroups;
+    return 0;
+}
+
+// What the periodic kernels read beside the sets; the bin table and the job blocks are pair_count3's and stay off here
+void fill_box_args(PairArgs &a, const Binning &b, const CellGrid &g) {
+    a.mode = b.mode;
+    a.in_box = 1;   // (no kernel reads it: pair_count2 takes the device flag)
+    a.g = g;
+    a.half = g.box * 0.5f;
+    a.pimax = b.pimax;
+    a.dpi = b.npibins > 0 ? b.pimax / (float)b.npibins : 1.0f;
+    a.mu_max = b.mu_max;
+    a.inv_dmu = b.nmubins > 0 ? (float)b.nmubins / b.mu_max : 1.0f;
+    a.edges2 = g_work.edges.as<float>();
+    a.lut_sh = a.lut_off = a.lut_ncell = 0;
+    a.no_blocks = 0;
+}
+
+// The periodic grid of a run and its stencil half-width R.  Jackknife and weighted counts walk the 27 cells of the full reach.
+// The unweighted kernels take cells of size >= reach / R: R = 2 (125-cell stencil of cells an eighth the volume: 1.7x fewer
+// candidate pairs) when the catalogue is dense enough to keep a wave busy with a small cell, else R = 1
+int periodic_grid(float boxsize, float reach_xy, float reach_z, bool full_reach, int gen, double nmax, CellGrid &g) {
+    auto ncells = [&](float reach, int R, int cap) {
+        int nc = (int)floorf(boxsize / reach * (float)R * 0.9999f);   // cell size strictly >= reach / R
+        nc = std::min(nc, cap);
+        return nc < 3 ? 1 : nc;
+    };
+    int R = 1;
+    if (!full_reach && gen >= 3) {
+        const double per_cell = nmax * ((double)reach_xy / boxsize) * ((double)reach_xy / boxsize) * ((double)reach_z / boxsize);
+        if (per_cell > 12.0 && ncells(reach_xy, 2, 192) >= 5 && ncells(reach_z, 2, 192) >= 5) R = 2;
+    }
+    g.box = boxsize;
+    g.inv_box = 1.0f / boxsize;
+    g.ncx = g.ncy = ncells(reach_xy, R, R == 2 ? 192 : 128);
+    g.ncz = ncells(reach_z, R, R == 2 ? 192 : 128);
+    // the cap may leave cells larger than reach / R: still correct (a cell >= reach / R is all the stencil needs)
+    return R;
+}
+
+// The periodic driver.  weighted: the entry takes weights and returns wsum (and rsum unless NULL), by pair_count_w
+int count_box(const PairCall &c, float boxsize, bool weighted) {
+    ABACUS_TRY(check_box(c, boxsize, weighted));
+    ABACUS_ENTER();
+    const Binning &b = c.bin;
+    const JkSpec *jk = c.jk;
+    const int mode = b.mode, autocorr = c.autocorr(), nsets = autocorr ? 1 : 2, nsub = b.nsub();
+    const size_t ntot_all = (size_t)b.nbins * nsub;
+    if (jk) jk_zero(jk->out, (size_t)jk->nreg * ntot_all);
+    else c.out.zero(ntot_all);
+    g_stats = Stats{};
+    if (c.empty()) return 0;
+
+    Work &W = g_work;
+    const int64_t ns[2] = {c.set[0].n, c.set[1].n};
+    const int *dl[2] = {nullptr, nullptr};
+    if (jk) ABACUS_TRY(jk_stage_labels(c.who, jk->labels, ns, nsets, c.where, jk->nreg, dl));
+    Flags fl;
+    ABACUS_TRY(W.flags(fl));
+    JkOut jdev = {};
+    if (jk) ABACUS_TRY(jk_device_outputs(jk->nreg, ntot_all, true, jdev, fl.evaluated + 1));   // the flush count: behind the candidates
+    Columns cols[2];
+    for (int k = 0; k < nsets; k++)
+        ABACUS_TRY(stage_columns("pair_cast", c.set[k].x, c.set[k].w, c.where, ns[k], nullptr, W.cols[k], W.wts[k], cols[k]));
+    const int gen = option("pairs_gen") ? option("pairs_gen") : 3;
+    // the columns serve every run; a run sorts them into a grid of its own reach and counts
+    ABACUS_TRY(for_runs(b.nbins, nsub, jk ? JK_MAX_HIST : (weighted ? W_MAX_HIST : MAX_HIST), [&](int b0, int nb, size_t o) -> int {
+        const float *edges = b.bins + b0;
+        const float reach_xy = edges[nb], reach_z = mode == 1 ? b.pimax : edges[nb];
+        const size_t ntot = (size_t)nb * nsub;
+        CellGrid g;
+        const int R = periodic_grid(boxsize, reach_xy, reach_z, jk || weighted, gen, (double)std::max(ns[0], autocorr ? ns[0] : ns[1]), g);
+        const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
+        // the frame and the outside flag belong to a run's grid; the jackknife kernels keep their flush count over the call
+        if (jk) HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
+        else if (b0 > 0) ABACUS_TRY(W.flags(fl));
+        for (int k = 0; k < nsets; k++) {
+            if (jk) ABACUS_TRY(sort_into_cells_jk(cols[k], dl[k], ns[k], g, ncell, jk->nreg, k));
+            else ABACUS_TRY(sort_into_cells(cols[k], ns[k], FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[k], W.scratch));
+        }
+        std::vector<float> e2;
+        ABACUS_TRY(upload_edges(edges, nb, e2));
+        Outputs dev = {};
+        if (!jk) ABACUS_TRY(device_outputs(ntot, weighted, dev));
+        PairArgs a;
+        WeightArgs wa;
+        fill_sets(a, wa, autocorr, nb, nsub, dev);
+        fill_box_args(a, b, g);
+        int R_used = 0, workgroups = 0;
+        if (jk) ABACUS_TRY(launch_jk(a, wa, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(jdev, o), fl, ncell, workgroups));
+        else if (weighted) ABACUS_TRY(launch_weighted(a, wa, c.out.rsum != nullptr, fl, ncell));
+        else ABACUS_TRY(launch_unweighted(a, gen, R, e2, fl, ncell, R_used));
+        if (!jk) ABACUS_TRY(fetch_outputs(c.out.at(o), dev, ntot));
+        return record_run(fl, false, g.ncx, g.ncz, R_used, nullptr, workgroups);
+    }));
+    if (jk) {
+        ABACUS_TRY(jk_fetch(jk->out, jdev, (size_t)jk->nreg * ntot_all));
+        HIP_TRY(hipStreamSynchronize(stream()));
+    }
+    return 0;
+}
+
+float funkey_host(unsigned int k) {
+    const unsigned int u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+
+// The observer-centred frame of a light-cone call: float32 columns of both sets in HBM and their bounding box (one reduction,
+// 24 bytes to the host).  They serve every run.
+struct LosFrame {
+    Columns cols[2];
+    double lo[3], extent[3];
+};
+int los_frame(const PairCall &c, bool weighted, const double *origin, const Flags &fl, LosFrame &f) {
+    Work &W = g_work;
+    for (int k = 0; k < (c.autocorr() ? 1 : 2); k++) {
+        const PointSet &s = c.set[k];
+        ABACUS_TRY(stage_columns("pair_los_centre", s.x, weighted ? s.w : nullptr, c.where, s.n, origin, W.cols[k], W.wts[k], f.cols[k]));
+        ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(s.n, 256), 1024)), dim3(256), 0,
+                      f.cols[k].x[0], f.cols[k].x[1], f.cols[k].x[2], s.n, fl.frame);
+    }
+    Frame fr;
+    HIP_TRY(hipMemcpyAsync(&fr, fl.frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    for (int d = 0; d < 3; d++) {
+        f.lo[d] = (double)funkey_host(fr.mn[d]);
+        f.extent[d] = (double)funkey_host(fr.mx[d]) - f.lo[d];
+        if (!(f.extent[d] >= 0.0) || !std::isfinite(f.extent[d]) || !std::isfinite(f.lo[d])) return fail("%s: coordinates are not finite", c.who);
+    }
+    return 0;
+}
+
+// the open grid of a run: cells of the frame's box that hold the run's reach (reach2: its square)
+OpenGrid open_grid(const LosFrame &f, double reach2) {
+    const double reach = std::nextafter(std::sqrt(reach2), HUGE_VAL);   // rounded up
+    OpenGrid og;
+    for (int d = 0; d < 3; d++) {
+        const double fit = std::floor(f.extent[d] / (reach * 1.0001));    // cell side >= 1.0001 reach (see OpenGrid)
+        og.nc[d] = (int)std::min(128.0, std::max(1.0, fit));
+        og.lo[d] = (float)f.lo[d];                                         // exact: a float32 coordinate
+        og.inv[d] = f.extent[d] > 0.0 ? (float)((double)og.nc[d] / f.extent[d]) : 0.f;
+    }
+    return og;
+}
+
+// what the light-cone kernels read beside the sets: grid, binning and the pre-test's thresholds (derivation at LosArgs), rounded
+// away from the accepted range [e2_lo, reach2)
+void fill_los_args(LosArgs &a, const Binning &b, const OpenGrid &og, double reach2, double e2_lo) {
+    for (int d = 0; d < 3; d++) a.nc[d] = og.nc[d];
+    const double hi_d = reach2 * (1.0 + 0x1p-20), lo_d = e2_lo * (1.0 - 0x1p-20);
+    float hi_f = (float)hi_d, lo_f = (float)lo_d;
+    if ((double)hi_f < hi_d) hi_f = std::nextafterf(hi_f, HUGE_VALF);
+    if ((double)lo_f > lo_d) lo_f = std::nextafterf(lo_f, 0.f);
+    a.pre_hi = hi_f;
+    a.pre_lo = b.mode != 1 && lo_d >= 1e-30 ? lo_f : 0.f;
+    a.pimax = (double)b.pimax;
+    a.dpi = b.npibins > 0 ? (double)b.pimax / b.npibins : 1.0;
+    a.mu_max = (double)b.mu_max;
+    a.inv_dmu = b.nmubins > 0 ? b.nmubins / (double)b.mu_max : 1.0;
+    a.edges2 = g_work.edges.as<double>();
+}
+
+// The open driver.  plain: wsum == NULL: integer counts only (rsum is then ignored); jackknife: the same with both sums NULL
+int count_los(const PairCall &c, const double *origin) {
+    ABACUS_TRY(check_los(c, origin));
+    ABACUS_ENTER();
+    const Binning &b = c.bin;
+    const JkSpec *jk = c.jk;
+    const int mode = b.mode, autocorr = c.autocorr(), nsets = autocorr ? 1 : 2, nsub = b.nsub();
+    const bool weighted = jk ? jk->out.wfirst != nullptr : c.out.wsum != nullptr, rs = !jk && weighted && c.out.rsum != nullptr;
+    const Outputs result{c.out.npairs, c.out.wsum, rs ? c.out.rsum : nullptr};
+    const size_t ntot_all = (size_t)b.nbins * nsub;
+    if (jk) jk_zero(jk->out, (size_t)jk->nreg * ntot_all);
+    else result.zero(ntot_all);
+    g_stats = Stats{};
+    if (c.empty()) return 0;
+
+    Work &W = g_work;
+    const int64_t ns[2] = {c.set[0].n, c.set[1].n};
+    const int *dl[2] = {nullptr, nullptr};
+    if (jk) ABACUS_TRY(jk_stage_labels(c.who, jk->labels, ns, nsets, c.where, jk->nreg, dl));
+    Flags fl;
+    ABACUS_TRY(W.flags(fl));
+    LosFrame fr;
+    ABACUS_TRY(los_frame(c, weighted, origin, fl, fr));
+    JkOut jdev = {};
+    if (jk) ABACUS_TRY(jk_device_outputs(jk->nreg, ntot_all, weighted, jdev, fl.evaluated + 1));
+    // a run sorts the frame's columns into a grid of its own reach and counts
+    ABACUS_TRY(for_runs(b.nbins, nsub, jk ? JK_MAX_HIST : W_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
+        const size_t ntot = (size_t)nb * nsub;
+        std::vector<double> e2;
+        ABACUS_TRY(upload_edges(b.bins + b0, nb, e2));
+        const double reach2 = mode == 1 ? e2[nb] + (double)b.pimax * (double)b.pimax : e2[nb];
+        const OpenGrid og = open_grid(fr, reach2);
+        const int64_t ncell = (int64_t)og.nc[0] * og.nc[1] * og.nc[2];
+        for (int k = 0; k < nsets; k++) {
+            if (jk) ABACUS_TRY(sort_into_cells_jk(fr.cols[k], dl[k], ns[k], og, ncell, jk->nreg, k));
+            else ABACUS_TRY(sort_into_cells(fr.cols[k], ns[k], og, ncell, W.S[k], W.scratch));
+        }
+        Outputs dev = {};
+        if (!jk) ABACUS_TRY(device_outputs(ntot, true, dev));
+        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
+        LosArgs a;
+        fill_sets(a, a, autocorr, nb, nsub, dev);
+        fill_los_args(a, b, og, reach2, e2[0]);
+        int workgroups = 0;
+        if (jk) ABACUS_TRY(launch_los_jk(mode, a, weighted, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(jdev, o), fl, ncell, workgroups));
+        else ABACUS_TRY(launch_los(mode, a, weighted, rs, fl, ncell));
+        if (!jk) ABACUS_TRY(fetch_outputs(result.at(o), dev, ntot));
+        return record_run(fl, true, og.nc[0], og.nc[2], 0, og.nc, workgroups);
+    }));
+    if (jk) {
+        ABACUS_TRY(jk_fetch(jk->out, jdev, (size_t)jk->nreg * ntot_all));
+        HIP_TRY(hipStreamSynchronize(stream()));
+    }
+    return 0;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------- the C ABI ----
+#define SETS(w1, w2) {{{x1, y1, z1}, w1, n1}, {{x2, y2, z2}, w2, n2}}
+#define BINNING {mode, bins, nbins, pimax, npibins, mu_max, nmubins}
+#define JK_SPEC const JkSpec jk = {{labels1, labels2}, nreg, {npairs_first, npairs_both, wsum_first, wsum_both}}
+
+extern "C" int abacus_paircount(int mode, const float *x1, const float *y1, const float *z1, int64_t n1,
+                                const float *x2, const float *y2, const float *z2, int64_t n2, float boxsize,
+                                const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
+                                uint64_t *npairs) {
+    return count_box({"abacus_paircount", SETS(nullptr, nullptr), 0, BINNING, {npairs, nullptr, nullptr}, nullptr}, boxsize, false);
+}
+
+extern "C" int abacus_paircount_dev(int mode, const void *x1, const void *y1, const void *z1, int64_t n1, const void *x2,
+                                    const void *y2, const void *z2, int64_t n2, int pos_dtype, float boxsize, const float *bins,
+                                    int nbins, float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs) {
+    return count_box({"abacus_paircount_dev", SETS(nullptr, nullptr), where_of(pos_dtype), BINNING, {npairs, nullptr, nullptr}, nullptr},
+                     boxsize, false);
+}
+
+extern "C" int abacus_paircount_weighted(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
+                                         const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,
+                                         float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                                         int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    return count_box({"abacus_paircount_weighted", SETS(w1, w2), 0, BINNING, {npairs, wsum, rsum}, nullptr}, boxsize, true);
+}
+
+extern "C" int abacus_paircount_weighted_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                                             const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2,
+                                             int pos_dtype, float boxsize, const float *bins, int nbins, float pimax, int npibins,
+                                             float mu_max, int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    return count_box({"abacus_paircount_weighted_dev", SETS(w1, w2), where_of(pos_dtype), BINNING, {npairs, wsum, rsum}, nullptr}, boxsize,
+                     true);
+}
+
+extern "C" int abacus_paircount_los(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
+                                    const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,
+                                    const double *origin, const float *bins, int nbins, float pimax, int npibins, float mu_max,
+                                    int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    return count_los({"abacus_paircount_los", SETS(w1, w2), 0, BINNING, {npairs, wsum, rsum}, nullptr}, origin);
+}
+
+extern "C" int abacus_paircount_los_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, int64_t n1,
+                                        const void *x2, const void *y2, const void *z2, const float *w2, int64_t n2, int pos_dtype,
+                                        const double *origin, const float *bins, int nbins, float pimax, int npibins,
+                                        float mu_max, int nmubins, uint64_t *npairs, double *wsum, double *rsum) {
+    return count_los({"abacus_paircount_los_dev", SETS(w1, w2), where_of(pos_dtype), BINNING, {npairs, wsum, rsum}, nullptr}, origin);
 }
 
 extern "C" int abacus_paircount_jk(int mode, const float *x1, const float *y1, const float *z1, const float *w1, const int32_t *labels1,
@@ -2472,8 +2529,8 @@ extern "C" int abacus_paircount_jk(int mode, const float *x1, const float *y1, c
                                    int64_t n2, int nreg, float boxsize, const float *bins, int nbins, float pimax, int npibins,
                                    float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both, double *wsum_first,
                                    double *wsum_both) {
-    return paircount_jk_impl("abacus_paircount_jk", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2, 0, nreg, boxsize, bins,
-                             nbins, pimax, npibins, mu_max, nmubins, JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+    JK_SPEC;
+    return count_box({"abacus_paircount_jk", SETS(w1, w2), 0, BINNING, {}, &jk}, boxsize, true);
 }
 
 extern "C" int abacus_paircount_jk_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, const int32_t *labels1,
@@ -2481,127 +2538,8 @@ extern "C" int abacus_paircount_jk_dev(int mode, const void *x1, const void *y1,
                                        int64_t n2, int pos_dtype, int nreg, float boxsize, const float *bins, int nbins, float pimax,
                                        int npibins, float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both,
                                        double *wsum_first, double *wsum_both) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_jk_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    return paircount_jk_impl("abacus_paircount_jk_dev", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2,
-                             pos_dtype == ABACUS_F32 ? 1 : 2, nreg, boxsize, bins, nbins, pimax, npibins, mu_max, nmubins,
-                             JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
-}
-
-static int paircount_los_jk_impl(const char *who, int mode, const void *x1, const void *y1, const void *z1, const float *w1,
-                                 const int32_t *labels1, int64_t n1, const void *x2, const void *y2, const void *z2, const float *w2,
-                                 const int32_t *labels2, int64_t n2, int where, int nreg, const double *origin, const float *bins,
-                                 int nbins, float pimax, int npibins, float mu_max, int nmubins, JkHostOut host) {
-    // every argument is checked before the device is touched
-    if (mode < 0 || mode > 2) return fail("%s: unknown mode %d", who, mode);
-    if (!x1 || !y1 || !z1 || !origin || !bins) return fail("%s: null argument", who);
-    if (nbins < 1) return fail("%s: nbins must be at least 1", who);
-    const int autocorr = x2 == nullptr;
-    if (!autocorr && (!y2 || !z2)) return fail("%s: null argument (y2 / z2)", who);
-    if (autocorr && w2) return fail("%s: w2 given for an autocorrelation (x2 is NULL)", who);
-    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31)) return fail("%s: point counts must lie in [0, 2^31)", who);
-    if (!(bins[0] >= 0.f)) return fail("%s: bin edges must not be negative", who);
-    for (int b = 0; b < nbins; b++)
-        if (!(bins[b + 1] > bins[b])) return fail("%s: bin edges must increase", who);
-    if (mode == 1 && (!(pimax > 0.f) || npibins < 1)) return fail("%s: pimax must be positive, with at least one pi bin", who);
-    if (mode == 2 && (!(mu_max > 0.f) || nmubins < 1)) return fail("%s: mu_max must be positive, with at least one mu bin", who);
-    const int nsub = mode == 0 ? 1 : (mode == 1 ? npibins : nmubins);
-    ABACUS_TRY(jk_check(who, nreg, nbins, nsub, autocorr, labels1, labels2, n1, n2, host, false));
-    for (int d = 0; d < 3; d++)
-        if (!std::isfinite(origin[d])) return fail("%s: origin must be finite", who);
-    ABACUS_ENTER();
-    const bool weighted = host.wfirst != nullptr;   // NULL sums: integer counts only
-    const size_t ntot_all = (size_t)nbins * nsub;
-    jk_zero(host, (size_t)nreg * ntot_all);
-    g_last_evaluated = 0, g_jk_flushes = 0, g_jk_workgroups = 0;
-    g_last_cells[0] = g_last_cells[1] = g_last_cells[2] = 0;
-    g_los_cells[0] = g_los_cells[1] = g_los_cells[2] = 0;
-    if (n1 == 0 || (!autocorr && n2 == 0)) return 0;
-
-    Work &W = g_work;
-    const void *const src[2][3] = {{x1, y1, z1}, {x2, y2, z2}};
-    const float *const srcw[2] = {weighted ? w1 : nullptr, weighted ? w2 : nullptr};
-    const int32_t *const srcl[2] = {labels1, labels2};
-    const int64_t ns[2] = {n1, n2};
-    const int nsets = autocorr ? 1 : 2;
-    const int *dl[2] = {nullptr, nullptr};
-    ABACUS_TRY(jk_stage_labels(who, srcl, ns, nsets, where, nreg, dl));
-    Columns cols[2];
-    Flags fl;
-    ABACUS_TRY(W.flags(fl));
-    unsigned long long *flushes = fl.evaluated + 1;
-    for (int k = 0; k < nsets; k++) {
-        ABACUS_TRY(stage_columns("pair_los_centre", src[k], srcw[k], where, ns[k], origin, W.cols[k], W.wts[k], cols[k]));
-        ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
-                      cols[k].x[0], cols[k].x[1], cols[k].x[2], ns[k], fl.frame);
-    }
-    Frame fr;
-    HIP_TRY(hipMemcpyAsync(&fr, fl.frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
-    double lo[3], extent[3];
-    for (int d = 0; d < 3; d++) {
-        lo[d] = (double)funkey_host(fr.mn[d]);
-        extent[d] = (double)funkey_host(fr.mx[d]) - lo[d];
-        if (!(extent[d] >= 0.0) || !std::isfinite(extent[d]) || !std::isfinite(lo[d])) return fail("%s: coordinates are not finite", who);
-    }
-    JkOut dev;
-    ABACUS_TRY(jk_device_outputs(nreg, ntot_all, weighted, dev, flushes));
-    unsigned long long evaluated = 0;
-    ABACUS_TRY(for_runs(nbins, nsub, JK_MAX_HIST, [&](int b0, int nb, size_t o) -> int {
-        std::vector<double> e2;
-        ABACUS_TRY(upload_edges(bins + b0, nb, e2));
-        const double reach2 = mode == 1 ? e2[nb] + (double)pimax * (double)pimax : e2[nb];
-        const double reach = std::nextafter(std::sqrt(reach2), HUGE_VAL);   // rounded up
-        OpenGrid og;
-        for (int d = 0; d < 3; d++) {
-            const double fit = std::floor(extent[d] / (reach * 1.0001));    // cell side >= 1.0001 reach (see OpenGrid)
-            og.nc[d] = (int)std::min(128.0, std::max(1.0, fit));
-            og.lo[d] = (float)lo[d];                                         // exact: a float32 coordinate
-            og.inv[d] = extent[d] > 0.0 ? (float)((double)og.nc[d] / extent[d]) : 0.f;
-        }
-        const int64_t ncell = (int64_t)og.nc[0] * og.nc[1] * og.nc[2];
-        for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells_jk(cols[k], dl[k], ns[k], og, ncell, nreg, k));
-        HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
-        LosArgs a;
-        fill_sets(a, a, autocorr, nb, nsub, Outputs{nullptr, nullptr, nullptr});
-        for (int d = 0; d < 3; d++) a.nc[d] = og.nc[d];
-        // the pre-test's thresholds (derivation at pair_count_los): rounded away from the accepted range
-        const double hi_d = reach2 * (1.0 + 0x1p-20), lo_d = e2[0] * (1.0 - 0x1p-20);
-        float hi_f = (float)hi_d, lo_f = (float)lo_d;
-        if ((double)hi_f < hi_d) hi_f = std::nextafterf(hi_f, HUGE_VALF);
-        if ((double)lo_f > lo_d) lo_f = std::nextafterf(lo_f, 0.f);
-        a.pre_hi = hi_f;
-        a.pre_lo = mode != 1 && lo_d >= 1e-30 ? lo_f : 0.f;
-        a.pimax = (double)pimax;
-        a.dpi = npibins > 0 ? (double)pimax / npibins : 1.0;
-        a.mu_max = (double)mu_max;
-        a.inv_dmu = nmubins > 0 ? nmubins / (double)mu_max : 1.0;
-        a.edges2 = W.edges.as<double>();
-        const size_t hist_bytes = (size_t)nb * nsub * (weighted ? 24 : 8);
-        ABACUS_TRY(with_mode(mode, [&](auto M) {
-            return with_flag(weighted, [&](auto WT) -> int {
-                const auto kernel = pair_count_los_jk<decltype(M)::value, decltype(WT)::value>;
-                dim3 grid;
-                ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-                if (option("pairs_jk_grid") > 0) grid.x = std::min<unsigned int>(grid.x, (unsigned int)option("pairs_jk_grid"));
-                ABACUS_LAUNCH("pair_count_los_jk", kernel, grid, dim3(PB), hist_bytes, a, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(dev, o), (int)ncell,
-                              fl.evaluated);
-                g_jk_workgroups = (int)grid.x;
-                return 0;
-            });
-        }));
-        unsigned long long ev = 0;
-        HIP_TRY(hipMemcpyAsync(&ev, fl.evaluated, 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        evaluated += ev;
-        g_last_cells[0] = og.nc[0], g_last_cells[1] = og.nc[2], g_last_cells[2] = 0;
-        for (int d = 0; d < 3; d++) g_los_cells[d] = og.nc[d];
-        return 0;
-    }));
-    ABACUS_TRY(jk_fetch(host, dev, (size_t)nreg * ntot_all));
-    HIP_TRY(hipMemcpyAsync(&g_jk_flushes, flushes, 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
-    g_last_evaluated = evaluated;
-    return 0;
+    JK_SPEC;
+    return count_box({"abacus_paircount_jk_dev", SETS(w1, w2), where_of(pos_dtype), BINNING, {}, &jk}, boxsize, true);
 }
 
 extern "C" int abacus_paircount_los_jk(int mode, const float *x1, const float *y1, const float *z1, const float *w1, const int32_t *labels1,
@@ -2609,8 +2547,8 @@ extern "C" int abacus_paircount_los_jk(int mode, const float *x1, const float *y
                                        const int32_t *labels2, int64_t n2, int nreg, const double *origin, const float *bins, int nbins,
                                        float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs_first, uint64_t *npairs_both,
                                        double *wsum_first, double *wsum_both) {
-    return paircount_los_jk_impl("abacus_paircount_los_jk", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2, 0, nreg, origin,
-                                 bins, nbins, pimax, npibins, mu_max, nmubins, JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+    JK_SPEC;
+    return count_los({"abacus_paircount_los_jk", SETS(w1, w2), 0, BINNING, {}, &jk}, origin);
 }
 
 extern "C" int abacus_paircount_los_jk_dev(int mode, const void *x1, const void *y1, const void *z1, const float *w1, const int32_t *labels1,
@@ -2618,16 +2556,33 @@ extern "C" int abacus_paircount_los_jk_dev(int mode, const void *x1, const void 
                                            const int32_t *labels2, int64_t n2, int pos_dtype, int nreg, const double *origin,
                                            const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
                                            uint64_t *npairs_first, uint64_t *npairs_both, double *wsum_first, double *wsum_both) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_los_jk_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    return paircount_los_jk_impl("abacus_paircount_los_jk_dev", mode, x1, y1, z1, w1, labels1, n1, x2, y2, z2, w2, labels2, n2,
-                                 pos_dtype == ABACUS_F32 ? 1 : 2, nreg, origin, bins, nbins, pimax, npibins, mu_max, nmubins,
-                                 JkHostOut{npairs_first, npairs_both, wsum_first, wsum_both});
+    JK_SPEC;
+    return count_los({"abacus_paircount_los_jk_dev", SETS(w1, w2), where_of(pos_dtype), BINNING, {}, &jk}, origin);
+}
+#undef SETS
+#undef BINNING
+#undef JK_SPEC
+
+extern "C" int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z, int *stencil_R) {
+    ABACUS_ENTER();
+    if (candidates) *candidates = g_stats.evaluated;
+    if (ncell_xy) *ncell_xy = g_stats.cells[0];
+    if (ncell_z) *ncell_z = g_stats.cells[1];
+    if (stencil_R) *stencil_R = g_stats.cells[2];
+    return 0;
+}
+
+extern "C" int abacus_paircount_los_grid(int *ncell) {
+    ABACUS_ENTER();
+    if (!ncell) return fail("abacus_paircount_los_grid: null argument");
+    for (int d = 0; d < 3; d++) ncell[d] = g_stats.los_cells[d];
+    return 0;
 }
 
 extern "C" int abacus_paircount_jk_stats(uint64_t *flushes, int *workgroups) {
     ABACUS_ENTER();
-    if (flushes) *flushes = g_jk_flushes;
-    if (workgroups) *workgroups = g_jk_workgroups;
+    if (flushes) *flushes = g_stats.flushes;
+    if (workgroups) *workgroups = g_stats.workgroups;
     return 0;
 }
 

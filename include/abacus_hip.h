@@ -487,6 +487,18 @@ int abacus_expand_poles_to_3d(const double *k_ell, const double *P_ell, int nk, 
  * float32 coordinates).  mode 0: DD(r), 1: DD(rp,pi) with pi bins of width pimax/npibins, 2: DD(s,mu) with
  * nmubins in [0,mu_max).  x2 == NULL -> autocorrelation (ordered pairs, no self pairs).
  * npairs: nbins * (1 | npibins | nmubins) uint64.
+ *
+ * Every pair-count entry of this section (abacus_paircount* - plain, weighted, _los, _jk, their _dev forms) validates all of
+ * its arguments before the device is touched: a refused call returns non-zero without initialising or launching anything,
+ * and its message (abacus_last_error) starts with the name of the entry that was called.  Common rules: mode 0 .. 2; the
+ * columns of set 1, bins (and origin / npairs where taken) not NULL; nbins >= 1; y2 and z2 given with x2; w2 (labels2) NULL
+ * for an autocorrelation; 0 <= n1, n2 < 2^31; strictly increasing bin edges; pos_dtype ABACUS_F32 or ABACUS_F64.  Periodic
+ * entries: boxsize > 0, at least one pi / mu bin in modes 1 / 2, and neither the last edge nor (mode 1) pimax above half the
+ * box.  An empty set returns zeros.
+ * The bookkeeping entries (abacus_paircount_stats, abacus_paircount_los_grid, abacus_paircount_jk_stats) describe the last
+ * pair-count call that passed validation, whichever entry it was: all of them are zero after a call with an empty set or one
+ * that failed on the device, and those a call does not produce (the open grid after a periodic call, the jackknife figures
+ * after a plain one) are zero too.
  */
 int abacus_paircount(int mode, const float *x1, const float *y1, const float *z1, int64_t n1, const float *x2,
                      const float *y2, const float *z2, int64_t n2, float boxsize, const float *bins, int nbins,

@@ -272,6 +272,42 @@ def test_los_statement(mode, auto, weighted, options):
     assert len(np.unique(la)) == 6
 
 
+@functools.lru_cache(maxsize=None)
+def _los_runs_case(mode):
+    """the cone of tests/test_pairs_los_gpu.py, five azimuth sectors across it, 70 separation bins: more than one launch holds"""
+    kw = dict(chi=(1500.0, 1600.0), spread=0.04, clump=0.3)
+    a = shell_points(2000, 101, **kw)
+    b = None if mode == 'r' else shell_points(1500, 102, **kw)
+
+    def sectors(cols):
+        phi = np.arctan2(np.asarray(cols[1]) - ORIGIN[1], np.asarray(cols[0]) - ORIGIN[0])
+        return np.clip(((phi - (np.pi / 4 - 0.08)) / 0.16 * 5).astype(np.int32), 0, 4)
+    la, lb = sectors(a), (None if b is None else sectors(b))
+    w1 = _weights(2000, 103) if mode == 'r' else None
+    bins = np.linspace(0.0, 35.0, 71)
+    sub = dict(pimax=40.0, npibins=40) if mode == 'rppi' else {}
+    return a, la, b, lb, w1, bins, sub, jks.counts(jks.los(bins, ORIGIN, **sub), mode, a, la, 5, b, lb, w1, None)
+
+
+@pytest.mark.parametrize('mode,first_run', [('r', 63), ('rppi', 51)])
+def test_los_many_bins_are_counted_in_runs(mode, first_run, options):
+    """70 separation bins on the light cone: mode r (autocorrelation, signed weights) in runs of 63 + 7 bins, mode rppi (cross
+    count, 40 pi bins, integer counts only) in runs of 51 + 19 - each run writes its own columns of the [nreg][ntot] block.
+    Every region has pairs on both sides of the boundary, in `first` and in `both`"""
+    a, la, b, lb, w1, bins, sub, want = _los_runs_case(mode)
+    nsub = sub.get('npibins', 1)
+    for term in ('first', 'both'):
+        per_bin = want[term]['npairs'].reshape(5, 70, nsub).sum(axis=2)
+        assert np.all(per_bin[:, first_run:].sum(axis=1) > 0) and np.all(per_bin[:, :first_run].sum(axis=1) > 0)
+    total = want['total']['npairs'].reshape(70, nsub).sum(axis=1)
+    assert total[first_run - 1] > 0 and total[first_run] > 0
+    for grid in (0, 5):
+        options.set('pairs_jk_grid', grid)
+        got = _jk().paircount_los_jk(mode, *a, bins, la, 5, *(b or jks.NONE3), labels2=lb, W1=w1, origin=ORIGIN,
+                                     want_sums=mode == 'r', **sub)
+        _compare(got, want, f'los runs {mode} grid={grid}', weighted=mode == 'r')
+
+
 def test_los_device_columns():
     from abacusutils_amd import _lib
     a, la, b, lb, w1, w2, bins, kw, want = _los_case('smu', False, True)

@@ -205,3 +205,89 @@ def test_host_box_regions():
     np.testing.assert_array_equal(lab3, lab * 7)
     with pytest.raises(ValueError):
         jk.box_regions(x, z, z, L, (2, 0, 1))
+
+
+def _abi():
+    import ctypes as C
+    from abacusutils_amd import _lib
+    return C, _lib.lib(), _lib.ptr
+
+
+def _refused(L, entry, rc, text, what):
+    msg = L.abacus_last_error().decode()
+    assert rc != 0, (entry, what)
+    assert text in msg and f'{entry}:' in msg, (entry, what, msg)
+
+
+def test_jackknife_c_abi_validates_before_the_device():
+    """every rule of abacus_paircount_jk / abacus_paircount_los_jk and their _dev forms (include/abacus_hip.h) answers with an
+    error of its own that names the entry called, with or without a GPU: nothing touches the device for a refused call"""
+    C, L, ptr = _abi()
+    x = np.linspace(0.0, 9.0, 10).astype(np.float32)
+    w, lab = np.ones(10, np.float32), (np.arange(10) % 4).astype(np.int32)
+    origin = np.zeros(3)
+    bins = np.array([0.5, 1.0, 2.0], np.float32)
+    cnt = [np.zeros(64, np.uint64), np.zeros(64, np.uint64)]
+    sums = [np.zeros(64), np.zeros(64)]
+
+    def call(entry, mode=1, x1=x, x2=None, y2=None, z2=None, w2=None, lab1=lab, lab2=None, n1=10, n2=0, pos_dtype=0, nreg=4, box=100.0,
+             org=origin, b=bins, nb=2, pimax=4.0, npi=4, mu_max=1.0, nmu=4, nfirst=cnt[0], wfirst=sums[0], wboth=sums[1]):
+        dt = (pos_dtype,) if entry.endswith('_dev') else ()
+        geom = (ptr(org),) if '_los_' in entry else (C.c_float(box),)
+        return getattr(L, entry)(mode, ptr(x1), ptr(x), ptr(x), ptr(w), ptr(lab1), C.c_int64(n1), ptr(x2), ptr(y2), ptr(z2), ptr(w2),
+                                 ptr(lab2), C.c_int64(n2), *dt, nreg, *geom, ptr(b), nb, C.c_float(pimax), npi, C.c_float(mu_max), nmu,
+                                 ptr(nfirst), ptr(cnt[1]), ptr(wfirst), ptr(wboth))
+    both = [(dict(mode=3), 'unknown mode'), (dict(x1=None), 'null'), (dict(b=None), 'null'), (dict(nb=0), 'nbins'),
+            (dict(x2=x, n2=10, lab2=lab), 'y2 / z2'), (dict(x2=x, y2=x, n2=10, lab2=lab), 'y2 / z2'),
+            (dict(w2=w), 'w2 given for an autocorrelation'), (dict(lab2=lab), 'labels2 given for an autocorrelation'),
+            (dict(lab1=None), 'labels1 is NULL'), (dict(x2=x, y2=x, z2=x, n2=10), 'labels2 is NULL'), (dict(n1=-1), 'point counts'),
+            (dict(x2=x, y2=x, z2=x, n2=-1, lab2=lab), 'point counts'), (dict(n1=1 << 31), 'point counts'),
+            (dict(nreg=0), 'nreg'), (dict(nreg=65536), 'nreg'), (dict(nreg=60000, npi=200), '2^24'),
+            (dict(nfirst=None), 'npairs_first'), (dict(wboth=None), 'go together'), (dict(wfirst=None), 'go together'),
+            (dict(npi=3000), 'exceed the LDS histogram'),
+            (dict(b=np.array([0.5, 2.0, 2.0], np.float32)), 'increase'), (dict(b=np.array([2.0, 1.0, 3.0], np.float32)), 'increase'),
+            (dict(b=np.array([0.5, np.nan, 3.0], np.float32)), 'increase')]
+    box = both + [(dict(box=0.0), 'boxsize'), (dict(npi=0), 'pi / mu bin'), (dict(mode=2, nmu=0), 'pi / mu bin'),
+                  (dict(wfirst=None, wboth=None), 'wsum_first / wsum_both is NULL'),
+                  (dict(b=np.array([0.5, 1.0, 51.0], np.float32)), 'half the box'), (dict(pimax=50.5), 'half the box')]
+    los = both + [(dict(npi=0), 'pimax'), (dict(pimax=0.0), 'pimax'), (dict(mode=2, nmu=0), 'mu_max'), (dict(mode=2, mu_max=0.0), 'mu_max'),
+                  (dict(org=None), 'null'), (dict(b=np.array([-1.0, 1.0, 3.0], np.float32)), 'negative'),
+                  (dict(org=np.array([0.0, np.inf, 0.0])), 'origin'), (dict(org=np.array([np.nan, 0.0, 0.0])), 'origin')]
+    for family, rules in (('abacus_paircount_jk', box), ('abacus_paircount_los_jk', los)):
+        for entry in (family, family + '_dev'):
+            for kw, text in rules:
+                _refused(L, entry, call(entry, **kw), text, kw)
+        _refused(L, family + '_dev', call(family + '_dev', pos_dtype=7), 'pos_dtype', 'pos_dtype')
+
+
+def test_box_c_abi_validates_before_the_device():
+    """the same for abacus_paircount and abacus_paircount_weighted: the rules they had, and those of the other counters they
+    lacked (point counts below zero, y2 / z2 NULL beside x2)"""
+    C, L, ptr = _abi()
+    x = np.linspace(0.0, 9.0, 10).astype(np.float32)
+    w = np.ones(10, np.float32)
+    bins = np.array([0.5, 1.0, 2.0], np.float32)
+    out, ws, rs = np.zeros(64, np.uint64), np.zeros(64), np.zeros(64)
+
+    def call(entry, mode=1, x1=x, x2=None, y2=None, z2=None, w2=None, n1=10, n2=0, pos_dtype=0, box=100.0, b=bins, nb=2, pimax=4.0,
+             npi=4, mu_max=1.0, nmu=4, npairs=out, wsum=ws):
+        weighted = 'weighted' in entry
+        dt = (pos_dtype,) if entry.endswith('_dev') else ()
+        w12, sums = (((ptr(w),), (ptr(w2),)), (ptr(wsum), ptr(rs))) if weighted else (((), ()), ())
+        return getattr(L, entry)(mode, ptr(x1), ptr(x), ptr(x), *w12[0], C.c_int64(n1), ptr(x2), ptr(y2), ptr(z2), *w12[1], C.c_int64(n2),
+                                 *dt, C.c_float(box), ptr(b), nb, C.c_float(pimax), npi, C.c_float(mu_max), nmu, ptr(npairs), *sums)
+    rules = [(dict(mode=3), 'unknown mode'), (dict(x1=None), 'null'), (dict(b=None), 'null'), (dict(npairs=None), 'null'),
+             (dict(nb=0), 'nbins'), (dict(box=0.0), 'boxsize'), (dict(box=-1.0), 'boxsize'), (dict(npi=0), 'pi / mu bin'),
+             (dict(mode=2, nmu=0), 'pi / mu bin'), (dict(npi=9000), 'exceed the LDS histogram'), (dict(n1=1 << 31), 'point counts'),
+             (dict(b=np.array([0.5, 2.0, 2.0], np.float32)), 'increase'), (dict(b=np.array([2.0, 1.0, 3.0], np.float32)), 'increase'),
+             (dict(b=np.array([0.5, 1.0, 51.0], np.float32)), 'half the box'), (dict(pimax=50.5), 'half the box'),
+             # inherited from the other three drivers
+             (dict(n1=-1), 'point counts'), (dict(x2=x, y2=x, z2=x, n2=-1), 'point counts'),
+             (dict(x2=x, n2=10), 'y2 / z2'), (dict(x2=x, y2=x, n2=10), 'y2 / z2')]
+    weighted_rules = [(dict(wsum=None), 'wsum is NULL'), (dict(w2=w), 'w2 given for an autocorrelation'),
+                      (dict(npi=3000), 'exceed the LDS histogram')]
+    for family in ('abacus_paircount', 'abacus_paircount_weighted'):
+        for entry in (family, family + '_dev'):
+            for kw, text in rules + (weighted_rules if 'weighted' in family else []):
+                _refused(L, entry, call(entry, **kw), text, kw)
+        _refused(L, family + '_dev', call(family + '_dev', pos_dtype=7), 'pos_dtype', 'pos_dtype')
