@@ -636,6 +636,34 @@ class AbacusHOD:
             return np.concatenate((wp[0], multi[0])), samples, jk.jackknife_covariance(samples)
         return self._pairs(mock_dict, fn, weights)
 
+    def compute_vpf(self, mock_dict, rmax, nbins, nspheres, numpN=6, seed=42):
+        """{tracer: the void probability function and count probabilities P_0 .. P_{numpN - 1}} of `nspheres` random spheres
+        per tracer (analysis/spheres.py: `vpf`, Corrfunc.theory.vpf's result); the galaxies stay in HBM when `mock_dict` is the
+        untouched result of the latest run_hod, only the centres are uploaded"""
+        from ..analysis.spheres import vpf
+        return {tr: vpf(rmax, nbins, nspheres, numpN, seed, *self._xyz(mock_dict, tr), periodic=True, boxsize=self.lbox)
+                for tr in mock_dict.keys()}
+
+    def compute_knn(self, mock_dict, radii, ks, nquery, seed=42, pimax=None, data_queries=False):
+        """{tracer: the kNN-CDFs (len(ks), len(radii)) of `nquery` random centres} (analysis/spheres.py: `knn_cdf`); pimax: the
+        (rp, pi) form.  data_queries: also '{a}_{b}' for every ORDERED tracer pair - the galaxies of a as queries around the
+        galaxies of b, a galaxy not counting itself when a is b"""
+        from ..analysis.spheres import knn_cdf
+        out = {tr: knn_cdf(*self._xyz(mock_dict, tr), self.lbox, radii, ks, nquery=nquery, seed=seed, pimax=pimax)
+               for tr in mock_dict.keys()}
+        if data_queries:
+            for a in mock_dict.keys():
+                for b in mock_dict.keys():
+                    data = self._xyz(mock_dict, b)
+                    if a == b:
+                        out[a + '_' + b] = knn_cdf(*data, self.lbox, radii, ks, pimax=pimax)
+                        continue
+                    queries = self._xyz(mock_dict, a)
+                    if isinstance(data[0], np.ndarray) != isinstance(queries[0], np.ndarray):   # one side only in HBM
+                        data, queries = [mock_dict[b][c] for c in 'xyz'], [mock_dict[a][c] for c in 'xyz']
+                    out[a + '_' + b] = knn_cdf(*data, self.lbox, radii, ks, *queries, pimax=pimax)
+        return out
+
     def compute_power(self, mock_dict, nbins_k, nbins_mu, k_hMpc_max, logk, poles=[], paste='TSC', num_cells=550,
                       compensated=False, interlaced=False, randoms=None):
         r"""P(k, mu) and/or P_l(k) for every tracer pair (:1338-1472).  Returned keys: '{a}_{b}', '..._modes',

@@ -615,6 +615,39 @@ int abacus_paircount_jk_stats(uint64_t *flushes, int *workgroups);
 int abacus_jk_box_labels_dev(const void *x, const void *y, const void *z, int pos_dtype, int64_t n, float boxsize, int nx, int ny,
                              int nz, int32_t *labels);
 
+/*
+ * Counts in spheres: for every query point the number of data points inside each of nr radii, on the periodic box - the
+ * primitive under the void probability function and the count probabilities P_N(r) (Corrfunc.theory.vpf), the k-nearest-
+ * neighbour CDFs (P(N(<r) >= k)) and counts-in-cells.  No reference code and no Corrfunc run stands behind this: the
+ * conventions below are the contract, pinned against the NumPy statement tests/spheres_statement.py, whose column sums are
+ * tied to the pair counter's cumulative counts.
+ *   inputs   data (x, y, z), n points; queries (qx, qy, qz), nq points, or qx == NULL: the data are the queries (qy, qz and nq
+ *            are then ignored); float32 radii r_1 < ... < r_nr; pimax = 0: spheres, pimax > 0: cylinders along z;
+ *   pair     float32, the expressions of abacus_paircount: d = q - p per component, one -+boxsize when |d| > boxsize / 2;
+ *            r2 = dx dx + dy dy + dz dz left to right, no FMA; cylinders: r2 = dx dx + dy dy and the pair needs |dz| < pimax;
+ *   inside   a data point is inside radius j iff r2 < e2[j], e2[j] = r_j * r_j as a float32 product.  Strict: N(<r_j) is the
+ *            cumulative sum of the pair counter's [lo, hi) bins over the edges (0, r_1 .. r_nr);
+ *   self     when the data are the queries a point does not count itself - by identity, not by distance: a coincident twin counts;
+ *   hist     [nr][kmax + 1] uint64: hist[j][k] = queries with exactly k points inside r_j for k < kmax, hist[j][kmax] = those
+ *            with kmax or more; every row sums to the number of queries;
+ *   counts   NULL, or [nq][nr] uint32 (n rows when the data are the queries): N(<r_j) per query, in the CALLER's query order.
+ * Checked before the device is touched (the message starts with the entry's name): 1 <= nr <= 32; kmax >= 1;
+ * nr * (kmax + 1) <= 8192; radii positive and increasing; r_nr and pimax at most boxsize / 2; pimax >= 0; boxsize > 0;
+ * 0 <= n, nq < 2^31; x, y, z, radii, hist (and qy, qz beside qx) not NULL; pos_dtype ABACUS_F32 or ABACUS_F64.
+ * Empty cases: n = 0 gives hist[:][0] = nq and zero counts; nq = 0 gives zeros.
+ * _dev: the columns of both sets in HBM, of ONE dtype (pos_dtype; float64 is cast to float32 on the device); radii, hist and
+ * counts are host pointers in both forms.  Coordinates may lie in any interval, as for abacus_paircount_dev.
+ * abacus_spherecount_stats: candidate (query, data) pairs evaluated and the cells per dimension in xy / z of the last call
+ * (the figures abacus_paircount_stats reports for it, like for every counter of this section).
+ */
+int abacus_spherecount(const float *x, const float *y, const float *z, int64_t n, const float *qx, const float *qy,
+                       const float *qz, int64_t nq, float boxsize, const float *radii, int nr, float pimax, int kmax,
+                       uint64_t *hist, uint32_t *counts);
+int abacus_spherecount_dev(const void *x, const void *y, const void *z, int64_t n, const void *qx, const void *qy, const void *qz,
+                           int64_t nq, int pos_dtype, float boxsize, const float *radii, int nr, float pimax, int kmax,
+                           uint64_t *hist, uint32_t *counts);
+int abacus_spherecount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z);
+
 /* ---------------------------------------------------------------- staging (the step in front of the HOD) ---- */
 /*
  * Data-parallel pieces of AbacusHOD.staging() (hod/abacus_hod.py:253-704); host arrays in and out, staging runs once.
