@@ -737,6 +737,21 @@ class AbacusHOD:
         clustering['mu_binc'] = power['mu_mid'][0]
         return clustering
 
+    def compute_bispectrum(self, mock_dict, kedges, num_cells=256, paste='TSC', compensated=True, interlaced=True):
+        """The auto bispectrum B(k1, k2, k3) of every tracer in the periodic box (no reference counterpart;
+        `analysis.bispectrum.calc_bispectrum`): {tracer: its result dict}.  `kedges`: the edges of at most 32 k-shells, the top one at
+        most 2 pi / Lbox * num_cells / 3.  The columns are taken from HBM when `mock_dict` is the untouched result of the latest
+        run_hod; a 'w' column weights its tracer (B and P are then raw, `Q` and `B_shot` None).  No cross bispectra."""
+        from ..analysis.bispectrum import _check_args, calc_bispectrum
+        _check_args(num_cells, self.lbox, kedges)
+        out = {}
+        for tr in mock_dict.keys():
+            cols = self._xyz(mock_dict, tr)
+            pos = list(cols) if not isinstance(cols[0], np.ndarray) else np.stack([np.asarray(c) for c in cols], axis=1)
+            out[tr] = calc_bispectrum(pos, self.lbox, kedges, nmesh=num_cells, w=mock_dict[tr].get('w', None), paste=paste,
+                                      compensated=compensated, interlaced=interlaced)
+        return out
+
     def apply_zcv(self, mock_dict, config, load_presaved=False):
         """signature of hod/abacus_hod.py:1474; not built (needs ZeNBu and classy).  `abacusutils_amd.hod.zcv` produces the spectra that
         the reference's `tools_cv.run_zcv` combines"""

@@ -957,6 +957,40 @@ int abacus_lc_compensate_dev(void *spec_padded, int n, const float *W_host);
  * else float32): per-workgroup partial sums, then one workgroup over them, both in a fixed order - the same bits on every run */
 int abacus_lc_sum_w2n_dev(const float *w, const void *nbar, int nbar_f64, int64_t np, double *out_host);
 
+/* ---------------------------------------------------------------- bispectrum ------------------------------ */
+/*
+ * Bispectrum of a periodic box on DEVICE pointers (csrc/zcv.hip, behind the light-cone section; Python: analysis/bispectrum.py); every
+ * call enqueues on the library stream.  replaces: nothing in the reference, which has no three-point statistic.  Estimator: the FFT
+ * form of Scoccimarro 2015.  From a padded spectrum delta(k), normalised as get_field_fft normalises (abacus_zcv_spectrum_dev), and
+ * nb shells with the edges kedges[0 .. nb]:
+ *   dk = float32(2 pi / Lbox); mode numbers: index i -> i below n/2, i - n from n/2 on (x, y), 0 .. n/2 on z;
+ *   |k| = dk * sqrt(float32(ix^2 + iy^2 + iz^2)), the square root and the product correctly rounded float32 operations;
+ *   a mode belongs to shell b iff float32(kedges[b]) <= |k| < float32(kedges[b + 1]), compared in float32;
+ *   D_b(x) = sum_{k in shell b} delta(k) e^{ikx} (no normalisation of the inverse), I_b(x) the same with delta -> 1;
+ *   T[i][j][l] = sum_x D_i D_j D_l and G[i] = sum_x D_i^2 over the n^3 cells (the caller divides by n^3).
+ * The sums close triangles modulo n, so float32(kedges[nb]) <= dk n / 3 is required (with a slack of 2^-22 for the float32 roundings of
+ * dk and the edge, and with what the rule stands for checked exactly: the mode (ceil(n / 3), 0, 0) is in no shell): every component of
+ * every mode used is then below n / 3, the Nyquist planes are in no shell and every masked spectrum is Hermitian as written.  "Padded meshes" as in the recon
+ * section: n * n rows of abacus_slab_pitch(n) floats, abacus_zcv_spectrum_bytes(n) bytes, aligned to 16 bytes.  Limits, checked
+ * before the device is touched, every message starting with the entry's name: n even, 2 .. 32767; 1 <= nb <= 32; edges finite,
+ * positive and increasing in float32; no null argument.
+ */
+/* fails, naming the largest mesh that fits, when the nb shell meshes + the spectrum + the work area of one deposit and transform (two
+ * padded meshes) + the copies and deposit lists of np particles do not fit the free device memory */
+int abacus_bk_check_memory(int n, int nb, int64_t np);
+/* spec_padded (not modified; NULL: the I fields) -> bk_shell_mask: ONE pass in which every mode is read once and written to all nb
+ * meshes, the mode inside its shell's mesh and 0 in the others (8 + 8 nb bytes per mode; the floats of a row beyond its n/2 + 1 modes
+ * are not written) -> nb in-place C2R.  meshes: a HOST array of nb device pointers to padded meshes, all different and none the
+ * spectrum; each holds D_b (or I_b) in its first n floats per row afterwards.  hipFFT may take a work area. */
+int abacus_bk_shells_dev(const void *spec_padded, int n, double Lbox, const double *kedges, int nb, float *const *meshes);
+/* T_host[nb][nb][nb] and G_host[nb] in float64 from nb padded real meshes (a HOST array of device pointers; not modified; the pad
+ * columns of a row never enter).  bk_triple: the sums as a GEMM S[(i, j)][l] = sum_x (D_i D_j)(x) D_l(x) on v_mfma_f32_16x16x4_f32 -
+ * the products D_i D_j and the accumulation in float32 for 128 cells (K of the MFMA chain), then added to float64 sums; one
+ * float64 partial per workgroup, added by a second kernel in a fixed order: no atomics, the same bits on every run.  nb <= 16: the full
+ * (i, j, l) cube in 16 tiles of 16 x 16.  nb > 16: the four block triples in ascending order, the other entries are their mirror
+ * images under a permutation of (i, j, l). */
+int abacus_bk_triple_dev(const float *const *meshes, int n, int nb, double *T_host, double *G_host);
+
 /* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
  * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
  * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
