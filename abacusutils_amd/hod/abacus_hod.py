@@ -752,6 +752,17 @@ class AbacusHOD:
                                       compensated=compensated, interlaced=interlaced)
         return out
 
+    def compute_3pcf(self, mock_dict, rbins, lmax, randoms=None, seed=42):
+        """The three-point correlation function multipoles zeta_l(r1, r2) of every tracer in the periodic box (no reference
+        counterpart; `analysis.threepcf.calc_3pcf`): {tracer: its result dict}.  `rbins`: the edges of at most 32 radial bins, the
+        last at most Lbox / 2; lmax <= 10.  randoms: None - the natural multipoles of the data alone, which contain the 1 + xi
+        terms - or an int (that many random centres of `seed`) or three columns: the connected zeta from D - R.  The columns are
+        taken from HBM when `mock_dict` is the untouched result of the latest run_hod; a 'w' column weights its tracer.  Auto
+        only: no cross three-point functions between tracers."""
+        from ..analysis.threepcf import calc_3pcf
+        return {tr: calc_3pcf(*self._xyz(mock_dict, tr), self.lbox, rbins, lmax, w=mock_dict[tr].get('w', None), randoms=randoms,
+                              seed=seed) for tr in mock_dict.keys()}
+
     def apply_zcv(self, mock_dict, config, load_presaved=False):
         """signature of hod/abacus_hod.py:1474; not built (needs ZeNBu and classy).  `abacusutils_amd.hod.zcv` produces the spectra that
         the reference's `tools_cv.run_zcv` combines"""

@@ -648,6 +648,46 @@ int abacus_spherecount_dev(const void *x, const void *y, const void *z, int64_t 
                            uint64_t *hist, uint32_t *counts);
 int abacus_spherecount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z);
 
+/*
+ * Three-point correlation function multipoles zeta_l(r1, r2) of one catalogue on the periodic box, by the multipole algorithm of
+ * Slepian & Eisenstein (2015): per primary the spherical-harmonic sums of its neighbours per radial bin, then their Gram matrix
+ * per l - O(N k) for k neighbours instead of the O(N k^2) triplet count.  No reference code and no Corrfunc run stands behind
+ * this: the conventions below are the contract, pinned against the NumPy statement tests/threepcf_statement.py (a brute-force
+ * form over triplets, and the algorithm itself in float64 and float32).
+ *   catalogue  set 1 (x, y, z, w, n) with set 2 (x2 .. w2, n2) APPENDED by the library (x2 == NULL: set 1 alone), so resident data
+ *              and a set of randoms need no concatenation by the caller; weights float32, NULL = 1, and may be negative (D - R);
+ *   pair       ordered (i, j), i != j by identity; float32, the expressions of the periodic counters and no others: d = p_i - p_j
+ *              per component, one -+boxsize when |d| > boxsize / 2; r2 = dx dx + dy dy + dz dz left to right, no FMA; the pair
+ *              is in bin b exactly when abacus_paircount_weighted mode 0 puts it there for the same nbins + 1 float32 edges
+ *              (e2[b] <= r2 < e2[b + 1], e2 = edge * edge in float32);
+ *   direction  u = d / sqrt(r2) in float32.  A pair with r2 == 0 (a coincident twin) has no direction: it enters neither zeta nor
+ *              wself - it IS a pair of its bin in npairs, as in the weighted counter;
+ *   zeta       [lmax + 1][nbins][nbins] float64: zeta[l][b1][b2] = sum_i w_i sum_{j in b1(i)} sum_{k in b2(i), k != j} w_j w_k
+ *              P_l(u_ij . u_ik).  One triangle is computed and mirrored: zeta[l][b1][b2] and zeta[l][b2][b1] are bit-equal;
+ *   wself      [nbins] float64: wself[b] = sum_i w_i sum_{j in b(i)} w_j^2, the j = k term the algorithm removes from the
+ *              diagonal (P_l(1) = 1 for every l), returned as a diagnostic;
+ *   npairs     [nbins] uint64, bit for bit the npairs of abacus_paircount_weighted mode 0 for the appended catalogue.
+ * Precision: directions, harmonics and a primary's harmonic sums a[bin][component] are float32; the Gram products, the factor
+ * w_i and everything summed over primaries are float64.  The float32 sums are LDS atomics and the float64 sums over workgroups
+ * global atomics: the order of both depends on the run, so zeta and wself are reproducible to the rounding of those sums
+ * (tests: within 4 x the float32 statement's own error), not bit for bit; npairs is exact.
+ * Checked before the device is touched (the message starts with the entry's name): 1 <= nbins <= 32; 0 <= lmax <= 10; edges
+ * non-negative and increasing, the last at most boxsize / 2; boxsize > 0; 0 <= n, n2 and n + n2 < 2^31; y2 and z2 given with x2
+ * and only with it, w2 only with x2; x, y, z, bins, zeta, wself, npairs not NULL; pos_dtype ABACUS_F32 or ABACUS_F64.
+ * Every output element is written by every successful call; an empty catalogue returns zeros.
+ * _dev: the columns of both sets in HBM, of ONE dtype (pos_dtype; float64 is cast to float32 on the device), w / w2 float32
+ * DEVICE pointers; bins and the outputs are host pointers in both forms.  Coordinates may lie in any interval.
+ * abacus_threepcf_stats: candidate pairs evaluated, counted pairs (the sum of npairs) and cells per dimension of the last call
+ * (1: fewer than three cells of the last edge fit, the box is one cell).
+ */
+int abacus_threepcf(const float *x, const float *y, const float *z, const float *w, int64_t n, const float *x2, const float *y2,
+                    const float *z2, const float *w2, int64_t n2, float boxsize, const float *bins, int nbins, int lmax,
+                    double *zeta, double *wself, uint64_t *npairs);
+int abacus_threepcf_dev(const void *x, const void *y, const void *z, const float *w, int64_t n, const void *x2, const void *y2,
+                        const void *z2, const float *w2, int64_t n2, int pos_dtype, float boxsize, const float *bins, int nbins,
+                        int lmax, double *zeta, double *wself, uint64_t *npairs);
+int abacus_threepcf_stats(uint64_t *candidates, uint64_t *counted, int *ncell);
+
 /* ---------------------------------------------------------------- staging (the step in front of the HOD) ---- */
 /*
  * Data-parallel pieces of AbacusHOD.staging() (hod/abacus_hod.py:253-704); host arrays in and out, staging runs once.
