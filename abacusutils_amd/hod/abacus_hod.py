@@ -763,6 +763,22 @@ class AbacusHOD:
         return {tr: calc_3pcf(*self._xyz(mock_dict, tr), self.lbox, rbins, lmax, w=mock_dict[tr].get('w', None), randoms=randoms,
                               seed=seed) for tr in mock_dict.keys()}
 
+    def compute_delta_sigma(self, mock_dict, parts, rp_bins, tracers=None, particle_mass=1.0):
+        """The excess surface density Delta Sigma(R) of the matter around every tracer (no reference counterpart;
+        `analysis.lensing.delta_sigma`): {tracer: its result dict}.  `parts`: the `analysis.lensing.ProjectedParticles` of the
+        matter particles' x and y columns, built once for the fit; `rp_bins`: at most 32 bins whose last edge is at most its
+        rmax.  tracers: None (all) or the names to compute.  The galaxies' x and y are taken from HBM when `mock_dict` is the
+        untouched result of the latest run_hod; a 'w' column weights its tracer.  The line of sight is z: redshift-space
+        distortions move galaxies along z only, which a projection over the whole box does not see.  For another axis pass
+        real-space columns to `analysis.lensing.delta_sigma` yourself - the x or y of a mock with RSD along z are real-space
+        columns, its z is not."""
+        from ..analysis.lensing import delta_sigma
+        out = {}
+        for tr in (mock_dict.keys() if tracers is None else tracers):
+            x, y, _ = self._xyz(mock_dict, tr)
+            out[tr] = delta_sigma(parts, x, y, rp_bins, weights=mock_dict[tr].get('w', None), particle_mass=particle_mass)
+        return out
+
     def apply_zcv(self, mock_dict, config, load_presaved=False):
         """signature of hod/abacus_hod.py:1474; not built (needs ZeNBu and classy).  `abacusutils_amd.hod.zcv` produces the spectra that
         the reference's `tools_cv.run_zcv` combines"""

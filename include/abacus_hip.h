@@ -73,7 +73,8 @@ int abacus_profile_get(const char **names, double *total_ms, int64_t *launches, 
  * hod_sbindex (1: the index path through the global index, hod_exact_index and hod_emit_bm, instead of the per-superblock index),
  * hod_keepmasks (1: the per-superblock index path keeps the keep masks exact populate by populate instead of writing them on
  * demand), pairs_jk_grid (at most that many workgroups for the jackknife pair kernels: a small catalogue then walks many cells
- * per workgroup, as a large one does), dbg / dbg_fft / dbg_tsc (ablation bit masks).  Default 0 = the production path. */
+ * per workgroup, as a large one does), lens_shared_rows (lens_walk adds into one set of LDS rows per workgroup instead of a
+ * column per lane), dbg / dbg_fft / dbg_tsc (ablation bit masks).  Default 0 = the production path. */
 int abacus_set_option(const char *name, int value);
 int abacus_get_option(const char *name);
 
@@ -647,6 +648,49 @@ int abacus_spherecount_dev(const void *x, const void *y, const void *z, int64_t 
                            int64_t nq, int pos_dtype, float boxsize, const float *radii, int nr, float pimax, int kmax,
                            uint64_t *hist, uint32_t *counts);
 int abacus_spherecount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z);
+
+/*
+ * Galaxy-galaxy lensing on the periodic box: the projected mass sums around galaxies, from which the excess surface density
+ * Delta Sigma(R) follows (analysis/lensing.py).  The line of sight is a box axis and the projection runs along the whole box,
+ * so both sets are pairs of TRANSVERSE columns.  The particles are sorted once into a 2-D periodic cell grid and stay in HBM
+ * behind a handle; every profile call sorts only its galaxies.  No reference code stands behind this: the conventions below are
+ * the contract, pinned against the NumPy statement tests/lensing_statement.py, whose cumulative counts are the cylinder counts of
+ * abacus_spherecount with pimax = boxsize / 2.
+ *   inputs   particles (px, py), n points, float32 masses pm or NULL (unit mass); galaxies (gx, gy), ng points, float32 weights gw
+ *            or NULL (unit weight; a weight may be negative); nb + 1 float32 edges 0 < R_0 < ... < R_nb;
+ *   pair     per (galaxy, particle), float32, the expressions of abacus_spherecount's cylinders and no dz test: d = g - p per
+ *            component, one -+boxsize when |d| > boxsize / 2; r2 = dx dx + dy dy left to right, no FMA; e2[j] = R_j * R_j as a
+ *            float32 product;
+ *   rows     nb + 1 of them: row 0 is the inner disc r2 < e2[0], row b + 1 is bin b, e2[b] <= r2 < e2[b + 1]; a pair with
+ *            r2 >= e2[nb] is dropped;
+ *   npairs   [nb + 1] uint64, exact;
+ *   wsum     [nb + 1] float64: the sum of (double)gw * (double)pm over the row's pairs (the product of two float32 values is
+ *            exact in float64; the order of the additions is not fixed).  With unit weights and masses wsum[r] == npairs[r].
+ * abacus_lens_create[_dev] sorts the particles into a grid sized for a reach of rmax (cells of side >= rmax, at least three per
+ * dimension or one), keeps the packed (x, y) and the masses in cell order in HBM - 8 bytes per particle, 12 with masses - and
+ * remembers sum(pm) in float64 (n without masses): abacus_lens_mass.  One handle serves any number of profile calls, with any
+ * edges whose last edge is at most its rmax.  abacus_lens_free releases it (NULL: nothing to do); a freed handle is refused.
+ * Checked before the device is touched (the message starts with the entry's name): 1 <= nb <= 32; edges positive and
+ * increasing; R_nb <= rmax <= boxsize / 2; boxsize > 0; 0 <= n, ng < 2^31; the handle, the columns of a non-empty set, edges,
+ * npairs and wsum not NULL; pos_dtype ABACUS_F32 or ABACUS_F64.
+ * Empty sets: n = 0 gives zeros, ng = 0 gives zeros.
+ * _dev: the two columns in HBM, of ONE dtype (pos_dtype; float64 is cast to float32 on the device), pm / gw float32 DEVICE
+ * pointers; edges, npairs and wsum are host pointers in both forms.  Coordinates may lie in any interval, as for
+ * abacus_paircount_dev.
+ * abacus_lens_stats: candidate (galaxy, particle) pairs evaluated and the cells per dimension of the last profile call (zeros
+ * after a call with an empty set).
+ */
+typedef struct abacus_lens abacus_lens;
+int abacus_lens_create(const float *px, const float *py, const float *pm, int64_t n, float boxsize, float rmax, abacus_lens **handle);
+int abacus_lens_create_dev(const void *px, const void *py, const float *pm, int64_t n, int pos_dtype, float boxsize, float rmax,
+                           abacus_lens **handle);
+int abacus_lens_profile(abacus_lens *handle, const float *gx, const float *gy, const float *gw, int64_t ng, const float *edges, int nb,
+                        uint64_t *npairs, double *wsum);
+int abacus_lens_profile_dev(abacus_lens *handle, const void *gx, const void *gy, const float *gw, int64_t ng, int pos_dtype,
+                            const float *edges, int nb, uint64_t *npairs, double *wsum);
+int abacus_lens_mass(abacus_lens *handle, double *mass, int64_t *n);
+int abacus_lens_free(abacus_lens *handle);
+int abacus_lens_stats(uint64_t *candidates, int *ncell);
 
 /*
  * Three-point correlation function multipoles zeta_l(r1, r2) of one catalogue on the periodic box, by the multipole algorithm of
