@@ -244,14 +244,14 @@ def calc_power(pos, Lbox, kbins=None, mubins=None, k_max=None, logk=False, paste
     if np.dtype(dtype) == np.float64 and not interlaced:
         # float64 meshes and transform (csrc/gfft.hip in double precision); the interlaced branch of the reference ignores dtype
         # (get_field_fft :1048-1052) and so falls through to the float32 path below, like there
-        f64 = pos.dtype == np.float64 or (pos2 is not None and pos2.dtype == np.float64)
-        cast = _pos_f8 if f64 else _pos_f4
-        p1 = cast(pos)
-        p2 = None if pos2 is None else cast(pos2)
+        # each set in its own dtype (two get_field_fft calls in the reference): a float32 set beside a float64 one keeps its
+        # float32 cloud weights
+        p1, f64a = _pos_any(pos)
+        p2, f64b = (None, False) if pos2 is None else _pos_any(pos2)
         outs = _alloc_outputs(len(ke) - 1, len(me) - 1, len(poles_arr))
         check(_lib.lib().abacus_power_f64(
-            ptr(p1), int(f64), C.c_int64(len(p1)), ptr(_w_like(w, f64)), ptr(p2), C.c_int64(0 if p2 is None else len(p2)),
-            ptr(_w_like(w2, f64)), C.c_double(Lbox), int(nmesh), code, ptr(_f4(W)), ptr(ke), len(ke) - 1, ptr(me), len(me) - 1,
+            ptr(p1), int(f64a) | int(f64b) << 1, C.c_int64(len(p1)), ptr(_w_like(w, f64a)), ptr(p2), C.c_int64(0 if p2 is None else len(p2)),
+            ptr(_w_like(w2, f64b)), C.c_double(Lbox), int(nmesh), code, ptr(_f4(W)), ptr(ke), len(ke) - 1, ptr(me), len(me) - 1,
             ptr(poles_arr), len(poles_arr), *[ptr(o) for o in outs]))
         return _power_table(outs, me, kbins, mubins, poles_arr, squeeze_mu_axis, return_mubins, meta)
 

@@ -2103,16 +2103,19 @@ int abacus_power_f64(void *pos, int pos_f64, int64_t n, const void *w, void *pos
     if (!pos) return fail("abacus_power_f64: null positions");
     const float *W_dev;
     ABACUS_TRY(upload_W(W_host, nmesh, &W_dev));
+    // each set in its own dtype, like the reference's two get_field_fft calls (:1248, :1264): a float32 set beside a float64 one
+    // keeps its float32 cloud weights
+    const int f64a = pos_f64 & 1, f64b = (pos_f64 >> 1) & 1;
     void *pd, *wd, *pd2 = nullptr, *wd2 = nullptr;
-    ABACUS_TRY(stage_particles_any(pos, pos_f64, n, w, g_ctx.pos, g_ctx.w, &pd, &wd));
+    ABACUS_TRY(stage_particles_any(pos, f64a, n, w, g_ctx.pos, g_ctx.w, &pd, &wd));
     tsc_wrapped_reset();
-    ABACUS_TRY(field64_dev(pd, pos_f64, n, wd, Lbox, nmesh, paste, 0.0, 0, true, W_dev));
+    ABACUS_TRY(field64_dev(pd, f64a, n, wd, Lbox, nmesh, paste, 0.0, 0, true, W_dev));
     const bool wrapped1 = paste == 0 && tsc_wrapped_seen();
     bool wrapped2 = false;
     if (pos2) {
-        ABACUS_TRY(stage_particles_any(pos2, pos_f64, n2, w2, g_ctx.pos2, g_ctx.w2, &pd2, &wd2));
+        ABACUS_TRY(stage_particles_any(pos2, f64b, n2, w2, g_ctx.pos2, g_ctx.w2, &pd2, &wd2));
         tsc_wrapped_reset();
-        ABACUS_TRY(field64_dev(pd2, pos_f64, n2, wd2, Lbox, nmesh, paste, 0.0, 1, true, W_dev));
+        ABACUS_TRY(field64_dev(pd2, f64b, n2, wd2, Lbox, nmesh, paste, 0.0, 1, true, W_dev));
         wrapped2 = paste == 0 && tsc_wrapped_seen();
     }
     const int pr = pitch_r64(nmesh), kzlen = nmesh / 2 + 1;
@@ -2120,8 +2123,8 @@ int abacus_power_f64(void *pos, int pos_f64, int64_t n, const void *w, void *pos
     ABACUS_TRY(g_ctx.helper_in.reserve((size_t)total * 4));
     ABACUS_LAUNCH("f64_raw_power", f64_raw_power, dim3(helper_grid(total)), dim3(256), 0, (const double2 *)g_ctx.mesh[0].as<double2>(),
                   (const double2 *)(pos2 ? g_ctx.mesh[1].as<double2>() : nullptr), nmesh, pr / 2, g_ctx.helper_in.as<float>());
-    if (wrapped1) HIP_TRY(hipMemcpyAsync(pos, pd, (size_t)n * 3 * (pos_f64 ? 8 : 4), hipMemcpyDeviceToHost, stream()));
-    if (wrapped2) HIP_TRY(hipMemcpyAsync(pos2, pd2, (size_t)n2 * 3 * (pos_f64 ? 8 : 4), hipMemcpyDeviceToHost, stream()));
+    if (wrapped1) HIP_TRY(hipMemcpyAsync(pos, pd, (size_t)n * 3 * (f64a ? 8 : 4), hipMemcpyDeviceToHost, stream()));
+    if (wrapped2) HIP_TRY(hipMemcpyAsync(pos2, pd2, (size_t)n2 * 3 * (f64b ? 8 : 4), hipMemcpyDeviceToHost, stream()));
     // bin_kmu on the raw power (its default float32 edge arithmetic, :787-789), times L^3 (:792-795)
     return bin_real_grid(g_ctx.helper_in.as<float>(), nmesh, kzlen, 1.0f, Lbox, 2.0 * M_PI / Lbox, Lbox * Lbox * Lbox, kedges, Nk, muedges, Nmu,
                          poles, Np, power, N_mode, binned_poles, N_mode_poles, k_avg);

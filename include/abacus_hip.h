@@ -245,6 +245,8 @@ int abacus_field_fft(float *pos, int64_t n, const float *w, double Lbox, int nme
  * are float64 - the cloud weights are evaluated in the dtype of the positions (analysis/tsc.py:400).  The mesh is deposited,
  * normalised and transformed in float64 (csrc/gfft.hip: even sizes up to 2560 with factors 2, 3, 5, 7, 11, 13 - what fits the 160-KiB LDS tile in double; hipFFT's D2Z otherwise); field:
  * (nmesh,)*3 float64, out_c128: (nmesh, nmesh, nmesh/2+1) complex128; abacus_power_f64 returns what bin_kmu returns, times L^3.
+ * abacus_power_f64 takes pos_f64 as a mask, one bit per particle set (bit 0: pos and w, bit 1: pos2 and w2): each set is
+ * deposited in its own dtype, like the reference's two get_field_fft calls.
  */
 int abacus_field_f64(void *pos, int pos_f64, int64_t n, const void *w, double Lbox, int nmesh, int paste, double offset, double *field);
 int abacus_field_fft_f64(void *pos, int pos_f64, int64_t n, const void *w, double Lbox, int nmesh, int paste, const float *W,
