@@ -79,6 +79,7 @@ def lib():
         L.abacus_last_error.restype = C.c_char_p
         L.abacus_get_stream.restype = C.c_void_p
         L.abacus_power_geometry_ms.restype = C.c_double
+        L.abacus_pairvel.restype = L.abacus_pairvel_dev.restype = C.c_int    # analysis/pairwise_velocity.py
         _lib = L
     return _lib
 

@@ -22,6 +22,7 @@
 //                             cell_fill / cell_gather / cell_starts (counting sort below 200 000 points, radix sort above)
 //   unweighted, periodic      pair_count (first generation: the comparator of the tests), pair_count2, pair_count3 (default)
 //   weighted and light cone   one walk in two bodies: pair_count_w (periodic, float32), pair_count_los (open grid, float64)
+//   pairwise velocities       pair_vel: the walk of pair_count_w with the velocities of both sets, five float64 velocity sums per bin
 //   host helpers              one set of work buffers, stage_columns, sort_into_cells, launch helpers, the run loop
 //   jackknife                 pair_count_jk / pair_count_los_jk (the two walks with per-region histograms), the label-aware
 //                             sort, the per-region outputs
@@ -205,6 +206,14 @@ __global__ void cell_gather(const float4 *__restrict__ packed, int64_t n, const 
         const float4 p = packed[idx[s]];   // one memory sector per point instead of three (x, y, z live in separate arrays)
         sx[s] = p.x, sy[s] = p.y, sz[s] = p.z;
         if (W) sw[s] = p.w;
+    }
+}
+// ... their velocities behind them, by the same sorted index (abacus_pairvel) ...
+__global__ void vel_gather(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz, int64_t n,
+                           const unsigned int *__restrict__ idx, float *__restrict__ svx, float *__restrict__ svy, float *__restrict__ svz) {
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned int i = idx[s];
+        svx[s] = vx[i], svy[s] = vy[i], svz[s] = vz[i];
     }
 }
 // ... and the first point of every cell: start[c] = number of keys below c (c = 0 .. ncell)
@@ -1014,6 +1023,165 @@ __global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, in
         }
 }
 
+// Pairwise velocity sums (abacus_pairvel; halotools' mean_radial_velocity_vs_r / radial_pvd_vs_r / mean_los_velocity_vs_rp /
+// los_pvd_vs_rp are moments of them).  The walk, the membership tests and the bin of pair_count_w, untouched - npairs and wsum are
+// that counter's - with the velocities of both sets riding along; a fix to one walk belongs in all of them
+// (profiles/pairs_shared_walk/README.md).  Per counted pair: u = v_i - v_j in float32, then float64, left to right, no FMA
+// (this file is built with contraction off):
+//   s2 = dx dx + dy dy + dz dz, t = ux dx + uy dy + uz dz, vr = s2 > 0 ? t / sqrt(s2) : 0 (negative: approaching),
+//   uu = ux ux + uy uy + uz uz, vz = uz sign(dz) (the minimum-image float32 dz; sign(0) = 0)
+// and with ww = (double)w_i (double)w_j five sums beside npairs and wsum: ww vr, ww vr^2, ww uu, ww vz, ww uz^2.
+//   * The float64 arithmetic stands behind the membership test: a candidate costs what it costs in pair_count_w.
+//   * LDS: 7760 bytes static (the slice of set 1 with its weights and velocities, the edge and neighbour tables) and 52 bytes
+//     per histogram entry (a count and six doubles).  V_MAX_HIST = 1024 entries are 53 248 bytes: 61 008 per workgroup, two
+//     workgroups (122 016 bytes) in the CU's 163 840; a third would need <= 901 entries.  A launch allocates what its binning
+//     needs, so the usual r binning of a few dozen entries is bound by registers, not LDS.  Larger binnings are counted in
+//     runs (for_runs).
+//   * MODE 0: the last bin's seven sums per lane in registers, added once at the end, as pair_count_w keeps its three.  TOP =
+//     false (option pairvel_lds_top, the comparator of profiles/pairvel/README.md) sends them through the LDS atomics too.
+constexpr int V_MAX_HIST = 1024;
+
+struct VelArgs {
+    const float *v1[3], *v2[3];   // velocities in cell order
+    double *vsum;                 // [5][nbins * nsub]: vr1 | vr2 | u2 | vz1 | vz2
+};
+
+template <int MODE, bool TOP>
+__global__ __launch_bounds__(PB) void pair_vel(PairArgs a, WeightArgs wa, VelArgs va, int ncell, unsigned long long *__restrict__ evaluated) {
+    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB], ivx[PB], ivy[PB], ivz[PB];
+    __shared__ float e2[64];
+    __shared__ int64_t nb_j0[27];
+    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
+    extern __shared__ __align__(8) double hs[];   // 6 x nh sums: w w | the five velocity sums; then nh counts
+    const int tid = threadIdx.x;
+    const int nh = a.nbins * a.nsub;
+    unsigned int *hc = reinterpret_cast<unsigned int *>(hs + 6 * nh);
+    for (int q = tid; q < 6 * nh; q += PB) hs[q] = 0.0;
+    for (int q = tid; q < nh; q += PB) hc[q] = 0u;
+    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
+    __syncthreads();
+    const float lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
+    const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
+    const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
+    double top[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // MODE 0: the last bin, per lane
+    unsigned long long top_n = 0, n_eval = 0;
+    for (int c1 = blockIdx.x; c1 < ncell; c1 += gridDim.x) {
+        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
+        if (cbeg == cend) continue;
+        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
+        if (tid < 64) {
+            int len = 0;
+            int64_t j0 = 0;
+            if (tid < nnb) {
+                const int cz = c1 % a.g.ncz, cy = (c1 / a.g.ncz) % a.g.ncy, cx = c1 / (a.g.ncz * a.g.ncy);
+                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
+                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
+                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
+                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
+                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
+                j0 = a.start2[c2];
+                len = (int)(a.start2[c2 + 1] - j0);
+            }
+            int incl = len;
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) {
+                const int v = __shfl_up(incl, d, 64);
+                if (tid >= d) incl += v;
+            }
+            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
+            if (tid == nnb - 1) nb_pre[nnb] = incl;
+        }
+        __syncthreads();
+        const int M = nb_pre[nnb];
+        for (int64_t i0 = cbeg; i0 < cend; i0 += PB) {
+            const int ni = (int)min((int64_t)PB, cend - i0);
+            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
+            if (tid < ni) {
+                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
+                iw[tid] = wa.w1 ? wa.w1[i0 + tid] : 1.0f;
+                ivx[tid] = va.v1[0][i0 + tid], ivy[tid] = va.v1[1][i0 + tid], ivz[tid] = va.v1[2][i0 + tid];
+            }
+            __syncthreads();
+            for (int base = 0; base < M; base += PB) {
+                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
+                const int v = base + tid;
+                if (v >= M) continue;
+                int sg = 0;
+                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[nnb]: ends at a non-empty cell
+                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
+                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
+                const float vxj = va.v2[0][jj], vyj = va.v2[1][jj], vzj = va.v2[2][jj];
+                const double wj = wa.w2 ? (double)wa.w2[jj] : 1.0;
+                for (int i = 0; i < ni; i++) {
+                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
+                    const float dx = min_image(ix[i] - xj, a.half, a.g.box);
+                    const float dy = min_image(iy[i] - yj, a.half, a.g.box);
+                    const float dz = min_image(iz[i] - zj, a.half, a.g.box);
+                    float r2;
+                    int sub = 0;
+                    if (MODE == 1) {
+                        const float adz = fabsf(dz);
+                        if (adz >= a.pimax) continue;
+                        r2 = dx * dx + dy * dy;
+                        if (r2 < lo2 || r2 >= hi2) continue;
+                        sub = (int)(adz / a.dpi);
+                        if (sub >= a.nsub) continue;
+                    } else {
+                        r2 = dx * dx + dy * dy + dz * dz;
+                        if (r2 < lo2 || r2 >= hi2) continue;
+                    }
+                    if (MODE == 2) {
+                        const float sep = sqrtf(r2);
+                        const float mu = sep > 0.f ? fabsf(dz) / sep : 0.f;
+                        if (mu >= a.mu_max) continue;
+                        sub = (int)(mu * a.inv_dmu);
+                        if (sub >= a.nsub) continue;
+                    }
+                    // a counted pair: the float64 part
+                    const float fux = ivx[i] - vxj, fuy = ivy[i] - vyj, fuz = ivz[i] - vzj;
+                    const double ddx = (double)dx, ddy = (double)dy, ddz = (double)dz;
+                    const double ux = (double)fux, uy = (double)fuy, uz = (double)fuz;
+                    const double s2 = ddx * ddx + ddy * ddy + ddz * ddz;
+                    const double t = ux * ddx + uy * ddy + uz * ddz;
+                    const double vr = s2 > 0.0 ? t / sqrt(s2) : 0.0;
+                    const double uu = ux * ux + uy * uy + uz * uz;
+                    const double vz = dz > 0.f ? uz : (dz < 0.f ? -uz : 0.0);
+                    const double ww = (double)iw[i] * wj;
+                    const double term[6] = {ww, ww * vr, ww * (vr * vr), ww * uu, ww * vz, ww * (uz * uz)};
+                    if (MODE == 0 && TOP && r2 >= top2) {
+                        top_n++;
+#pragma unroll
+                        for (int k = 0; k < 6; k++) top[k] += term[k];
+                        continue;
+                    }
+                    int b = a.nbins - 1;
+                    while (r2 < e2[b]) b--;
+                    const int q = b * a.nsub + sub;
+                    atomicAdd(&hc[q], 1u);
+#pragma unroll
+                    for (int k = 0; k < 6; k++) atomicAdd(&hs[k * nh + q], term[k]);
+                }
+            }
+        }
+    }
+    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
+    if (MODE == 0 && TOP && top_n) {
+        // a lane's share of a workgroup's last-bin pairs stays far below 2^32
+        const int q = a.nbins - 1;
+        atomicAdd(&hc[q], (unsigned int)top_n);
+#pragma unroll
+        for (int k = 0; k < 6; k++) atomicAdd(&hs[k * nh + q], top[k]);
+    }
+    __syncthreads();
+    for (int q = tid; q < nh; q += PB)
+        if (hc[q]) {
+            atomicAdd(&a.npairs[q], (unsigned long long)hc[q]);
+            atomicAdd(&wa.wsum[q], hs[q]);
+#pragma unroll
+            for (int k = 0; k < 5; k++) atomicAdd(&va.vsum[k * nh + q], hs[(k + 1) * nh + q]);
+        }
+}
+
 // Light cones: pair counts with a PAIRWISE line of sight on an OPEN grid (abacus_paircount_los, Corrfunc.mocks' DDrppi_mocks /
 // DDsmu_mocks on Cartesian columns).  No reference code and no Corrfunc run stands behind this; the conventions are restated
 // here and pinned against the NumPy statement tests/pairs_los_statement.py.
@@ -1188,8 +1356,9 @@ __global__ __launch_bounds__(PB) void pair_count_los(LosArgs a, int ncell, unsig
 
 // ------------------------------------------------------------------------------------------------------------- host side ----
 struct SortedSet {
-    DevBuf sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wsorted;
+    DevBuf sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wsorted, vsorted;
     float *sx, *sy, *sz, *sw;   // sw: the weights in cell order (weighted counts with weights for this set), else NULL
+    float *sv[3];               // the velocities in cell order (sort_into_cells with velocities), else stale
     int64_t n;
 };
 
@@ -1206,6 +1375,7 @@ struct Flags {
 struct Work {
     SortedSet S[2];
     DevBuf cols[2], wts[2];   // staged float32 columns and weights of the two sets
+    DevBuf vcols[2];          // and their staged velocities (abacus_pairvel)
     DevBuf scratch, edges, out, list, flag;
     int flags(Flags &f) {
         ABACUS_TRY(flag.reserve(64));
@@ -1265,9 +1435,11 @@ int count_cells(const Columns &c, int64_t n, const Grid &g, SortedSet &s, int nb
     return 0;
 }
 
-// The set in cell order on either grid (ncell cells): s.sx | sy | sz, s.start and - with weights - s.sw
+// The set in cell order on either grid (ncell cells): s.sx | sy | sz, s.start and - with weights - s.sw.  vel (NULL: none): three
+// float32 device columns that follow their points into s.sv; such a set takes the radix sort at every size, whose sorted index
+// says where a point went (the counting sort hands out slots by atomics and keeps no index).  n > 0 with vel.
 template <typename Grid>
-int sort_into_cells(const Columns &c, int64_t n, const Grid &g, int64_t ncell, SortedSet &s, DevBuf &scratch) {
+int sort_into_cells(const Columns &c, int64_t n, const Grid &g, int64_t ncell, SortedSet &s, DevBuf &scratch, const float *const *vel = nullptr) {
     const size_t n1 = (size_t)std::max<int64_t>(n, 1);
     s.n = n;
     ABACUS_TRY(s.sorted.reserve(3 * n1 * 4));
@@ -1286,7 +1458,7 @@ int sort_into_cells(const Columns &c, int64_t n, const Grid &g, int64_t ncell, S
     }
     // large inputs: stable radix sort of (cell id, index) + gather + a search per cell (10^7 points: 0.6 ms against 2.2 ms of
     // the counting sort below, whose two passes are a global atomic per point each)
-    if (n >= 200000 && n < ((int64_t)1 << 31) && !option("pairs_countsort")) {
+    if (vel || (n >= 200000 && n < ((int64_t)1 << 31) && !option("pairs_countsort"))) {
         ABACUS_TRY(s.keys2.reserve(n1 * 4));
         ABACUS_TRY(s.idx.reserve(n1 * 4));
         ABACUS_TRY(s.idx2.reserve(n1 * 4));
@@ -1310,6 +1482,12 @@ int sort_into_cells(const Columns &c, int64_t n, const Grid &g, int64_t ncell, S
         else
             ABACUS_LAUNCH("pair_cell_fill", cell_gather<false>, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(),
                           s.sx, s.sy, s.sz, s.sw);
+        if (vel) {
+            ABACUS_TRY(s.vsorted.reserve(3 * n1 * 4));
+            for (int d = 0; d < 3; d++) s.sv[d] = s.vsorted.as<float>() + (size_t)d * n1;
+            ABACUS_LAUNCH("pair_vel_gather", vel_gather, dim3(nblk), dim3(256), 0, vel[0], vel[1], vel[2], n, s.idx2.as<unsigned int>(), s.sv[0],
+                          s.sv[1], s.sv[2]);
+        }
         const int cblk = (int)std::min<int64_t>(ceil_div(ncell + 1, 256), 8192);
         ABACUS_LAUNCH("pair_cell_starts", cell_starts, dim3(cblk), dim3(256), 0, s.keys2.as<unsigned int>(), n, ncell, s.start.as<int64_t>());
         return 0;
@@ -1377,25 +1555,31 @@ int upload_edges(const float *edges, int nb, std::vector<Q> &e2) {
 struct Outputs {
     uint64_t *npairs;
     double *wsum, *rsum;   // NULL: not asked for
-    Outputs at(size_t o) const { return Outputs{npairs + o, wsum ? wsum + o : nullptr, rsum ? rsum + o : nullptr}; }
+    double *vsum = nullptr;   // abacus_pairvel: five velocity sums, [5][vstride] with this block's entries at the front of each row
+    size_t vstride = 0;
+    Outputs at(size_t o) const { return Outputs{npairs + o, wsum ? wsum + o : nullptr, rsum ? rsum + o : nullptr, vsum ? vsum + o : nullptr, vstride}; }
     void zero(size_t ntot) const {
         memset(npairs, 0, ntot * sizeof(uint64_t));
         if (wsum) memset(wsum, 0, ntot * sizeof(double));
         if (rsum) memset(rsum, 0, ntot * sizeof(double));
+        if (vsum) memset(vsum, 0, 5 * vstride * sizeof(double));
     }
 };
-int device_outputs(size_t ntot, bool sums, Outputs &d) {
-    const size_t bytes = (sums ? 3 : 1) * ntot * 8;
+int device_outputs(size_t ntot, bool sums, bool vel, Outputs &d) {
+    const size_t bytes = ((sums ? 3 : 1) + (vel ? 5 : 0)) * ntot * 8;
     ABACUS_TRY(g_work.out.reserve(bytes));
     HIP_TRY(hipMemsetAsync(g_work.out.p, 0, bytes, stream()));
     d.npairs = g_work.out.as<uint64_t>();
     d.wsum = sums ? g_work.out.as<double>() + ntot : nullptr, d.rsum = sums ? d.wsum + ntot : nullptr;
+    d.vsum = vel ? g_work.out.as<double>() + (sums ? 3 : 1) * ntot : nullptr, d.vstride = ntot;
     return 0;
 }
 int fetch_outputs(const Outputs &h, const Outputs &d, size_t ntot) {
     HIP_TRY(hipMemcpyAsync(h.npairs, d.npairs, ntot * 8, hipMemcpyDeviceToHost, stream()));
     if (h.wsum) HIP_TRY(hipMemcpyAsync(h.wsum, d.wsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
     if (h.rsum) HIP_TRY(hipMemcpyAsync(h.rsum, d.rsum, ntot * 8, hipMemcpyDeviceToHost, stream()));
+    for (int k = 0; k < 5 && h.vsum; k++)
+        HIP_TRY(hipMemcpyAsync(h.vsum + k * h.vstride, d.vsum + k * d.vstride, ntot * 8, hipMemcpyDeviceToHost, stream()));
     return 0;
 }
 
@@ -1413,7 +1597,7 @@ void fill_sets(Args &a, Sums &s, int autocorr, int nbins, int nsub, const Output
 // The launches of a run, one function per walk; the two drivers (below the jackknife kernels) choose among them.  Each stands
 // behind the instantiation of its family's sort: the code object lists kernels in the order of their instantiation, and the
 // launches keep that order whichever driver calls them.
-template int sort_into_cells<FramedGrid>(const Columns &, int64_t, const FramedGrid &, int64_t, SortedSet &, DevBuf &);
+template int sort_into_cells<FramedGrid>(const Columns &, int64_t, const FramedGrid &, int64_t, SortedSet &, DevBuf &, const float *const *);
 
 int launch_weighted(const PairArgs &a, const WeightArgs &wa, bool rsum, const Flags &fl, int64_t ncell) {
     const size_t hist_bytes = (size_t)a.nbins * a.nsub * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
@@ -1501,7 +1685,7 @@ int launch_unweighted(PairArgs &a, int gen, int R, const std::vector<float> &e2,
     });
 }
 
-template int sort_into_cells<OpenGrid>(const Columns &, int64_t, const OpenGrid &, int64_t, SortedSet &, DevBuf &);
+template int sort_into_cells<OpenGrid>(const Columns &, int64_t, const OpenGrid &, int64_t, SortedSet &, DevBuf &, const float *const *);
 
 // weighted: with sums of w w; rs: and of the separation
 int launch_los(int mode, const LosArgs &a, bool weighted, bool rs, const Flags &fl, int64_t ncell) {
@@ -2327,6 +2511,7 @@ struct PointSet {
     const void *x[3];
     const float *w;   // NULL: unit weights
     int64_t n;
+    const void *v[3];   // velocity columns of a velocity call (PairCall::vel), in the dtype of x
 };
 struct Binning {
     int mode;
@@ -2350,6 +2535,7 @@ struct PairCall {
     Binning bin;
     Outputs out;         // of a plain call
     const JkSpec *jk;    // NULL: a plain call
+    bool vel = false;    // abacus_pairvel: the sets carry velocities, out.vsum takes their sums (a plain, weighted call otherwise)
     int autocorr() const { return set[1].x[0] == nullptr; }
     bool empty() const { return set[0].n == 0 || (!autocorr() && set[1].n == 0); }
 };
@@ -2383,8 +2569,15 @@ int check_box(const PairCall &c, float boxsize, bool weighted) {
     ABACUS_TRY(check_sets_and_bins(c, false));
     if (!(boxsize > 0)) return fail("%s: boxsize must be positive", c.who);
     if (b.nsub() < 1) return fail("%s: need at least one pi / mu bin", c.who);
-    ABACUS_TRY(check_outputs(c, weighted ? W_MAX_HIST : MAX_HIST, true));
+    ABACUS_TRY(check_outputs(c, c.vel ? V_MAX_HIST : (weighted ? W_MAX_HIST : MAX_HIST), true));
     if (!c.jk && weighted && !c.out.wsum) return fail("%s: wsum is NULL", c.who);
+    if (c.vel) {
+        const PointSet &s1 = c.set[0], &s2 = c.set[1];
+        if (!s1.v[0] || !s1.v[1] || !s1.v[2]) return fail("%s: null velocity column (set 1)", c.who);
+        if (!c.autocorr() && !s2.v[0] && !s2.v[1] && !s2.v[2]) return fail("%s: velocities given for set 1 of a cross count but not for set 2", c.who);
+        if (!c.autocorr() && (!s2.v[0] || !s2.v[1] || !s2.v[2])) return fail("%s: null velocity column (set 2)", c.who);
+        if (!c.out.vsum) return fail("%s: vsum is NULL", c.who);
+    }
     // the edges increase: the last one is the reach of every run
     if (b.bins[b.nbins] > 0.5f * boxsize || (b.mode == 1 && b.pimax > 0.5f * boxsize))
         return fail("%s: maximum separation exceeds half the box (minimum image not unique)", c.who);
@@ -2463,7 +2656,24 @@ int periodic_grid(float boxsize, float reach_xy, float reach_z, bool full_reach,
     return R;
 }
 
-// The periodic driver.  weighted: the entry takes weights and returns wsum (and rsum unless NULL), by pair_count_w
+// pair_vel stands behind every instantiation above, so the kernels before it keep their order in the code object
+int launch_vel(const PairArgs &a, const WeightArgs &wa, const VelArgs &va, const Flags &fl, int64_t ncell) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 52;   // <= V_MAX_HIST * 52 = 52 KiB beside 7.6 KiB of static LDS
+    return with_mode(a.mode, [&](auto M) {
+        return with_flag(a.mode != 0 || !option("pairvel_lds_top"), [&](auto TOP) -> int {   // modes 1, 2 have no such path: one instance
+            const auto kernel = pair_vel<decltype(M)::value, decltype(TOP)::value>;
+            if (hist_bytes > 48 * 1024)
+                HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
+            dim3 grid;
+            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+            ABACUS_LAUNCH("pair_vel", kernel, grid, dim3(PB), hist_bytes, a, wa, va, (int)ncell, fl.evaluated);
+            return 0;
+        });
+    });
+}
+
+// The periodic driver.  weighted: the entry takes weights and returns wsum (and rsum unless NULL), by pair_count_w - or, for a
+// call with velocities (c.vel), the five velocity sums beside wsum, by pair_vel
 int count_box(const PairCall &c, float boxsize, bool weighted) {
     ABACUS_TRY(check_box(c, boxsize, weighted));
     ABACUS_ENTER();
@@ -2487,9 +2697,12 @@ int count_box(const PairCall &c, float boxsize, bool weighted) {
     Columns cols[2];
     for (int k = 0; k < nsets; k++)
         ABACUS_TRY(stage_columns("pair_cast", c.set[k].x, c.set[k].w, c.where, ns[k], nullptr, W.cols[k], W.wts[k], cols[k]));
+    Columns vels[2];   // the velocities of a velocity call: staged like the positions (one rounding of float64 columns)
+    for (int k = 0; k < nsets && c.vel; k++)
+        ABACUS_TRY(stage_columns("pair_cast", c.set[k].v, nullptr, c.where, ns[k], nullptr, W.vcols[k], W.wts[k], vels[k]));
     const int gen = option("pairs_gen") ? option("pairs_gen") : 3;
     // the columns serve every run; a run sorts them into a grid of its own reach and counts
-    ABACUS_TRY(for_runs(b.nbins, nsub, jk ? JK_MAX_HIST : (weighted ? W_MAX_HIST : MAX_HIST), [&](int b0, int nb, size_t o) -> int {
+    ABACUS_TRY(for_runs(b.nbins, nsub, jk ? JK_MAX_HIST : (c.vel ? V_MAX_HIST : (weighted ? W_MAX_HIST : MAX_HIST)), [&](int b0, int nb, size_t o) -> int {
         const float *edges = b.bins + b0;
         const float reach_xy = edges[nb], reach_z = mode == 1 ? b.pimax : edges[nb];
         const size_t ntot = (size_t)nb * nsub;
@@ -2501,19 +2714,22 @@ int count_box(const PairCall &c, float boxsize, bool weighted) {
         else if (b0 > 0) ABACUS_TRY(W.flags(fl));
         for (int k = 0; k < nsets; k++) {
             if (jk) ABACUS_TRY(sort_into_cells_jk(cols[k], dl[k], ns[k], g, ncell, jk->nreg, k));
-            else ABACUS_TRY(sort_into_cells(cols[k], ns[k], FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[k], W.scratch));
+            else ABACUS_TRY(sort_into_cells(cols[k], ns[k], FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[k], W.scratch, c.vel ? vels[k].x : nullptr));
         }
         std::vector<float> e2;
         ABACUS_TRY(upload_edges(edges, nb, e2));
         Outputs dev = {};
-        if (!jk) ABACUS_TRY(device_outputs(ntot, weighted, dev));
+        if (!jk) ABACUS_TRY(device_outputs(ntot, weighted, c.vel, dev));
         PairArgs a;
         WeightArgs wa;
         fill_sets(a, wa, autocorr, nb, nsub, dev);
         fill_box_args(a, b, g);
         int R_used = 0, workgroups = 0;
         if (jk) ABACUS_TRY(launch_jk(a, wa, g_jk.sl[0], g_jk.sl[nsets - 1], jk_at(jdev, o), fl, ncell, workgroups));
-        else if (weighted) ABACUS_TRY(launch_weighted(a, wa, c.out.rsum != nullptr, fl, ncell));
+        else if (c.vel) {
+            const SortedSet &S1 = W.S[0], &T = W.S[nsets - 1];
+            ABACUS_TRY(launch_vel(a, wa, VelArgs{{S1.sv[0], S1.sv[1], S1.sv[2]}, {T.sv[0], T.sv[1], T.sv[2]}, dev.vsum}, fl, ncell));
+        } else if (weighted) ABACUS_TRY(launch_weighted(a, wa, c.out.rsum != nullptr, fl, ncell));
         else ABACUS_TRY(launch_unweighted(a, gen, R, e2, fl, ncell, R_used));
         if (!jk) ABACUS_TRY(fetch_outputs(c.out.at(o), dev, ntot));
         return record_run(fl, false, g.ncx, g.ncz, R_used, nullptr, workgroups);
@@ -2625,7 +2841,7 @@ int count_los(const PairCall &c, const double *origin) {
             else ABACUS_TRY(sort_into_cells(fr.cols[k], ns[k], og, ncell, W.S[k], W.scratch));
         }
         Outputs dev = {};
-        if (!jk) ABACUS_TRY(device_outputs(ntot, true, dev));
+        if (!jk) ABACUS_TRY(device_outputs(ntot, true, false, dev));
         HIP_TRY(hipMemsetAsync(fl.evaluated, 0, 8, stream()));
         LosArgs a;
         fill_sets(a, a, autocorr, nb, nsub, dev);
@@ -3195,6 +3411,27 @@ extern "C" int abacus_paircount_weighted_dev(int mode, const void *x1, const voi
     return count_box({"abacus_paircount_weighted_dev", SETS(w1, w2), where_of(pos_dtype), BINNING, {npairs, wsum, rsum}, nullptr}, boxsize,
                      true);
 }
+
+#define VSETS {{{x1, y1, z1}, w1, n1, {vx1, vy1, vz1}}, {{x2, y2, z2}, w2, n2, {vx2, vy2, vz2}}}
+extern "C" int abacus_pairvel(int mode, const float *x1, const float *y1, const float *z1, const float *vx1, const float *vy1,
+                              const float *vz1, const float *w1, int64_t n1, const float *x2, const float *y2, const float *z2,
+                              const float *vx2, const float *vy2, const float *vz2, const float *w2, int64_t n2, float boxsize,
+                              const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs,
+                              double *wsum, double *vsum) {
+    const size_t ntot = (size_t)std::max(nbins, 0) * (size_t)std::max(mode == 0 ? 1 : (mode == 1 ? npibins : nmubins), 0);
+    return count_box({"abacus_pairvel", VSETS, 0, BINNING, {npairs, wsum, nullptr, vsum, ntot}, nullptr, true}, boxsize, true);
+}
+
+extern "C" int abacus_pairvel_dev(int mode, const void *x1, const void *y1, const void *z1, const void *vx1, const void *vy1,
+                                  const void *vz1, const float *w1, int64_t n1, const void *x2, const void *y2, const void *z2,
+                                  const void *vx2, const void *vy2, const void *vz2, const float *w2, int64_t n2, int pos_dtype,
+                                  float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
+                                  uint64_t *npairs, double *wsum, double *vsum) {
+    const size_t ntot = (size_t)std::max(nbins, 0) * (size_t)std::max(mode == 0 ? 1 : (mode == 1 ? npibins : nmubins), 0);
+    return count_box({"abacus_pairvel_dev", VSETS, where_of(pos_dtype), BINNING, {npairs, wsum, nullptr, vsum, ntot}, nullptr, true},
+                     boxsize, true);
+}
+#undef VSETS
 
 extern "C" int abacus_paircount_los(int mode, const float *x1, const float *y1, const float *z1, const float *w1, int64_t n1,
                                     const float *x2, const float *y2, const float *z2, const float *w2, int64_t n2,

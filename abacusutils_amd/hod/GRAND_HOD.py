@@ -377,6 +377,30 @@ class MockDict(dict):
                 return None
         return [_lib.DeviceArray.view(cols[q], np.float64, (n,)) for q in range(3)]
 
+    def device_vel(self, tracer):
+        """`device_xyz` for the velocity columns vx, vy, vz (compute_pairwise_velocity): the same validity rules and the same
+        checksum test, on the host velocity columns"""
+        st = getattr(self, '_staged', lambda: None)()
+        if st is None or not st._h or st.generation != self._generation or tracer not in self:
+            return None
+        d = self[tracer]
+        lazy = isinstance(d, LazyTracer) and '_staged' in d.__dict__     # never copied to the host: nothing to compare
+        n = int(st.counts[TRACERS.index(tracer)] + st.counts[3 + TRACERS.index(tracer)])
+        if n == 0:
+            return None
+        cols = st.device_columns(tracer)
+        if not lazy:
+            try:
+                for q, c in enumerate(('vx', 'vy', 'vz')):
+                    a = d[c]
+                    if not isinstance(a, np.ndarray) or a.shape != (n,) or a.dtype != np.float64:
+                        return None
+                    if _lib.poshash_host(a) != _lib.poshash_device(cols[3 + q], n):
+                        return None
+            except (KeyError, TypeError):
+                return None
+        return [_lib.DeviceArray.view(cols[3 + q], np.float64, (n,)) for q in range(3)]
+
 
 def gen_gals(halos_array, subsample, tracers, params, Nthread, enable_ranks, rsd, verbose, nfw, NFW_draw=None,
              staged=None, lazy=False):

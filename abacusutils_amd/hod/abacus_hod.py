@@ -779,6 +779,37 @@ class AbacusHOD:
             out[tr] = delta_sigma(parts, x, y, rp_bins, weights=mock_dict[tr].get('w', None), particle_mass=particle_mass)
         return out
 
+    def compute_pairwise_velocity(self, mock_dict, rbins, mode='r', pimax=None, npibins=1, nmubins=1, weights=None):
+        """The pairwise velocity sums and moments of every tracer pair in the periodic box (no reference counterpart;
+        `analysis.pairwise_velocity`): {'{a}_{b}': the seven sums of `pairwise_velocity_sums` and the moments of `moments_from_sums`
+        (v12, sigma_r, sigma_t, vlos, sigma_los)}, the symmetric key filled like the pair counts'.  mode 'r': bins of r; 'rppi':
+        bins of rp and `npibins` bins of |pi| < pimax; 'smu': bins of s and `nmubins` bins of mu in [0, 1).  weights: see `_pairs`.
+        The six columns of a tracer are taken from HBM when `mock_dict` is the untouched result of the latest run_hod, else from
+        the host columns.  The line of sight is z, and with want_rsd the z column is the REDSHIFT-SPACE one: separations,
+        the radial direction and sign(dz) are then those of redshift space, while the velocities are the galaxies' own."""
+        from ..analysis.pairwise_velocity import moments_from_sums, pairwise_velocity_sums
+        if mode == 'rppi' and pimax is None:
+            raise ValueError("mode 'rppi' needs pimax")
+        kw = dict(pimax=0.0 if pimax is None else float(pimax), npibins=int(npibins), mu_max=1.0, nmubins=int(nmubins))
+
+        def six(tr, host=False):
+            xyz = None if host or not hasattr(mock_dict, 'device_vel') else mock_dict.device_xyz(tr)
+            vel = None if xyz is None else mock_dict.device_vel(tr)
+            if vel is not None:
+                return list(xyz) + list(vel)
+            return [mock_dict[tr][c] for c in ('x', 'y', 'z', 'vx', 'vy', 'vz')]
+        wcol = lambda tr: None if weights is None else mock_dict[tr].get(weights)   # noqa: E731
+        out = {}
+        tracers = list(mock_dict.keys())
+        for i1, tr1 in enumerate(tracers):
+            for tr2 in tracers[i1:]:
+                c1, c2 = six(tr1), (None,) * 6 if tr2 == tr1 else six(tr2)
+                if tr2 != tr1 and isinstance(c1[0], np.ndarray) != isinstance(c2[0], np.ndarray):   # one side only in HBM: both from the host
+                    c1, c2 = six(tr1, host=True), six(tr2, host=True)
+                sums = pairwise_velocity_sums(mode, *c1, self.lbox, rbins, *c2, W1=wcol(tr1), W2=None if tr2 == tr1 else wcol(tr2), **kw)
+                out[tr1 + '_' + tr2] = out[tr2 + '_' + tr1] = {**sums, **moments_from_sums(sums)}
+        return out
+
     def apply_zcv(self, mock_dict, config, load_presaved=False):
         """signature of hod/abacus_hod.py:1474; not built (needs ZeNBu and classy).  `abacusutils_amd.hod.zcv` produces the spectra that
         the reference's `tools_cv.run_zcv` combines"""

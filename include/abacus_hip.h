@@ -535,6 +535,47 @@ int abacus_paircount_weighted_dev(int mode, const void *x1, const void *y1, cons
                                   float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max,
                                   int nmubins, uint64_t *npairs, double *wsum, double *rsum);
 
+/*
+ * Pairwise velocity sums on the periodic box: what the mean pairwise infall v12(r), the radial and transverse pairwise
+ * dispersions and the line-of-sight pairwise mean and dispersion in (rp, pi) are moments of (halotools' mean_radial_velocity_vs_r,
+ * radial_pvd_vs_r, mean_los_velocity_vs_rp, los_pvd_vs_rp; no halotools run stands behind this - the contract below is pinned
+ * against the NumPy statement tests/pairvel_statement.py).
+ *   sets     float32 columns x, y, z, vx, vy, vz and optional float32 weights w (NULL: unit weights).  The _dev form takes the
+ *            six columns of a set in HBM, all of pos_dtype; ABACUS_F64 columns are rounded once to float32 on the device,
+ *            velocities like positions.  x2 == NULL: autocorrelation (w2 must be NULL, the velocities of set 2 are not read).
+ *   pairs    ordered; self pairs of an autocorrelation are excluded.  A pair is in a (bin, sub-bin) exactly when
+ *            abacus_paircount_weighted puts it there for the same mode, bins, pimax, npibins, mu_max, nmubins: float32
+ *            d = p_i - p_j with one minimum-image addition, float32 r2 against float32 squared edges, modes 0 (r), 1 (rp, pi),
+ *            2 (s, mu) with that entry's sub-bin rules.  npairs and wsum are that entry's.
+ *   a pair   u = v_i - v_j componentwise in float32; then in float64, left to right, no FMA:
+ *              s2 = dx dx + dy dy + dz dz          t = ux dx + uy dy + uz dz
+ *              vr = s2 > 0 ? t / sqrt(s2) : 0      (negative: the pair approaches)
+ *              uu = ux ux + uy uy + uz uz
+ *              vz = uz * sign(dz)                  (the sign of the minimum-image float32 dz, sign(0) = 0: the line of sight is z)
+ *   sums     per (bin, sub-bin), with ww = (double)w_i * (double)w_j, all float64:
+ *              npairs, wsum = sum ww, and in vsum - one block [5][nbins * nsub] -
+ *              vr1 = sum ww vr | vr2 = sum ww vr^2 | u2 = sum ww uu | vz1 = sum ww vz | vz2 = sum ww uz^2.
+ *            Accumulated by float64 atomics: |error| <= (n + 8) * 2^-52 * sum|term| of a cell with n pairs, the 8 for a
+ *            square root and a division that may each differ from the host's by an ulp.
+ * The moments: v12 = vr1 / wsum, sigma_r^2 = vr2 / wsum - v12^2, sigma_t^2 = (u2 - vr2) / (2 wsum) per transverse direction,
+ * vlos = vz1 / wsum, sigma_los^2 = vz2 / wsum - vlos^2.
+ * Validation as for every entry of this section (before the device is touched, the message starts with the entry's name),
+ * with the rules of the periodic entries and: no velocity column of set 1 NULL; in a cross count the velocities of set 2 given
+ * (all NULL: "velocities ... but not for set 2", some NULL: a null velocity column); wsum and vsum not NULL.  At most 1024
+ * sub-bins; binnings of more than 1024 entries are counted in runs of separation bins.  abacus_paircount_stats reports the
+ * candidate pairs of this call too (stencil_R = 0).  Periodic box only: no light cone, no jackknife regions.
+ */
+int abacus_pairvel(int mode, const float *x1, const float *y1, const float *z1, const float *vx1, const float *vy1,
+                   const float *vz1, const float *w1, int64_t n1, const float *x2, const float *y2, const float *z2,
+                   const float *vx2, const float *vy2, const float *vz2, const float *w2, int64_t n2, float boxsize,
+                   const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins, uint64_t *npairs,
+                   double *wsum, double *vsum);
+int abacus_pairvel_dev(int mode, const void *x1, const void *y1, const void *z1, const void *vx1, const void *vy1,
+                       const void *vz1, const float *w1, int64_t n1, const void *x2, const void *y2, const void *z2,
+                       const void *vx2, const void *vy2, const void *vz2, const float *w2, int64_t n2, int pos_dtype,
+                       float boxsize, const float *bins, int nbins, float pimax, int npibins, float mu_max, int nmubins,
+                       uint64_t *npairs, double *wsum, double *vsum);
+
 /* bookkeeping of the last pair-count call (bench.py's roofline): candidate pair separations the kernel evaluated (0 when an
  * older-generation kernel ran), cells per dimension in xy / z, stencil half-width in cells (1 or 2; 0: older kernel) */
 int abacus_paircount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z, int *stencil_R);
