@@ -1,4 +1,6 @@
 from .bispectrum import bispectrum_from_spectrum, calc_bispectrum, triangle_counts  # noqa: F401
 from .lensing import ProjectedParticles, delta_sigma, delta_sigma_box, delta_sigma_from_sums, projected_sums  # noqa: F401
+from .minkowski import (calc_minkowski, gaussian_prediction, mesh_moments, minkowski_counts, minkowski_from_counts,  # noqa: F401
+                        minkowski_functionals)
 from .spheres import count_in_spheres, knn_cdf, random_centres, vpf  # noqa: F401
 from .threepcf import calc_3pcf, triplet_multipoles, zeta_from_counts  # noqa: F401

@@ -605,6 +605,21 @@ int zcv_release_plans() {
     }
     return 0;
 }
+
+size_t zcv_padded_bytes(int n) { return padded_bytes(n); }
+
+// minkowski.hip: D, a padded spectrum normalised as get_field_fft normalises, times exp(-k^2 R^2 / 2) as the filter of gaussian_filter
+// forms it with kcut = 1 / R (R = 0: no filter), then the C2R in place: the padded real mesh
+int zcv_smooth_c2r_inplace(float *D, int n, double Lbox, double R) {
+    if (R > 0) {
+        const int pc = pitch_r(n) / 2;
+        MultArgs m = mult_args(n, Lbox, pc, pc, 1.0);
+        m.norm = (float)(2.0 / (R * R));
+        if (!(m.norm > 0)) return fail("abacus_mf_smooth_spectrum_dev: R = %g is too large for the float32 filter", R);
+        ABACUS_TRY(launch_mult(OP_FILTER, false, (const float2 *)D, (float2 *)D, m));
+    }
+    return inverse(D, n);
+}
 }  // namespace abacus
 
 extern "C" {

@@ -752,6 +752,21 @@ class AbacusHOD:
                                       compensated=compensated, interlaced=interlaced)
         return out
 
+    def compute_minkowski(self, mock_dict, thresholds, R, num_cells=256, paste='TSC', compensated=True, interlaced=True, sigma_units=True):
+        """The four Minkowski functionals V0 .. V3 of every tracer's density contrast in the periodic box, smoothed with a Gaussian of
+        radius `R` (no reference counterpart; `analysis.minkowski.calc_minkowski`): {tracer: its result dict}.  `thresholds`: at
+        most 64 increasing values, nu in units of sigma around the mean with `sigma_units`, else values of the smoothed contrast.  The
+        columns are taken from HBM when `mock_dict` is the untouched result of the latest run_hod; a 'w' column weights its tracer.
+        No cross-field morphology."""
+        from ..analysis.minkowski import calc_minkowski
+        out = {}
+        for tr in mock_dict.keys():
+            cols = self._xyz(mock_dict, tr)
+            pos = list(cols) if not isinstance(cols[0], np.ndarray) else np.stack([np.asarray(c) for c in cols], axis=1)
+            out[tr] = calc_minkowski(pos, self.lbox, thresholds, R, nmesh=num_cells, w=mock_dict[tr].get('w', None), paste=paste,
+                                     compensated=compensated, interlaced=interlaced, sigma_units=sigma_units)
+        return out
+
     def compute_3pcf(self, mock_dict, rbins, lmax, randoms=None, seed=42):
         """The three-point correlation function multipoles zeta_l(r1, r2) of every tracer in the periodic box (no reference
         counterpart; `analysis.threepcf.calc_3pcf`): {tracer: its result dict}.  `rbins`: the edges of at most 32 radial bins, the

@@ -1118,6 +1118,45 @@ int abacus_bk_shells_dev(const void *spec_padded, int n, double Lbox, const doub
  * images under a permutation of (i, j, l). */
 int abacus_bk_triple_dev(const float *const *meshes, int n, int nb, double *T_host, double *G_host);
 
+/* ---------------------------------------------------------------- Minkowski functionals ------------------- */
+/*
+ * Minkowski functionals of a periodic mesh on DEVICE pointers (csrc/minkowski.hip; Python: analysis/minkowski.py); every call enqueues
+ * on the library stream.  replaces: nothing in the reference, which has no morphological statistic.  Estimator: Crofton's formula on
+ * the cubic lattice (Schmalzing & Buchert 1997).  For a mesh of n^3 float32 cells with periodic indices and a threshold t:
+ *   the excursion set is the union of the closed voxels with value >= t, compared in float32 (a tie is inside);
+ *   an element of the lattice belongs to it iff the maximum of the voxels that touch it is >= t: 2 voxels for a face, 4 for an edge,
+ *   8 for a vertex; voxel (i, j, k) owns its cube, the faces towards +x, +y, +z, the three edges between those faces and the vertex
+ *   at (i + 1, j + 1, k + 1), all read from the block (i .. i + 1, j .. j + 1, k .. k + 1) modulo n: every element is counted once;
+ *   n0, n1, n2, n3 = the vertices, edges, faces and voxels inside, exact integers.
+ * The caller forms V0 = n3 / N, V1 = 2 (n2 - 3 n3) / (9 a N), V2 = 2 (n1 - 2 n2 + 3 n3) / (9 a^2 N), V3 = (n0 - n1 + n2 - n3) /
+ * (a^3 N) with N = n^3 and a = Lbox / n.  "mesh": n * n rows of `pitch` floats, aligned to 4 bytes; pitch == n is a dense mesh,
+ * pitch == abacus_slab_pitch(n) the real side of a padded spectrum; the floats of a row beyond its n cells are never read.  A mesh
+ * aligned to 16 bytes with a pitch that is a multiple of 4 is read with 16-byte loads.  The mesh must be finite; that is not checked
+ * on the device (a NaN lies below every threshold, +inf above every one).  Limits, checked on the host before anything is launched,
+ * every message starting with the entry's name: 2 <= n <= 32767 (even for the two entries that handle a spectrum), pitch >= n,
+ * 1 <= nthr <= 64, thresholds finite and strictly increasing as float32; no null argument.
+ */
+/* fails, naming the largest mesh that fits, when the spectrum + the work area of one deposit and transform (two padded meshes) + the
+ * copies and deposit lists of np particles do not fit the free device memory */
+int abacus_mf_check_memory(int n, int64_t np);
+/* counts_host[4][nthr] int64, rows n0, n1, n2, n3, for the nthr thresholds (HOST array) in ONE pass over the mesh (not modified).
+ * mf_count: b(v) = the number of thresholds <= v is monotonic, so every cell is located among the thresholds once (8 comparisons
+ * against every eighth threshold, 7 against one group of a table in LDS) and the maxima are taken of the bins; tiles of 16 x 64 cells marched along x with a one-cell halo; uint32 bins
+ * per workgroup in LDS (integer adds), flushed once per workgroup and added to 64-bit totals by a second kernel: no float atomics,
+ * nothing depends on the order of arrival.  The host takes the suffix sums over the bins and checks that every class adds up to its
+ * N, 3 N, 3 N, N elements.  Device memory: 1040 bytes per workgroup of 16 x 64 x 32 cells. */
+int abacus_mf_counts_dev(const float *mesh, int n, int pitch, const float *thresholds_host, int nthr, int64_t *counts_host);
+/* out2_host[0] = sum x, out2_host[1] = sum x^2 over the n^3 cells in float64 (every x and x * x is exact in float64): per-workgroup
+ * partial sums over a fixed deal of the rows to 2048 workgroups, then one workgroup per sum over the partials, both in a fixed order -
+ * the same bits on every run */
+int abacus_mf_moments_dev(const float *mesh, int n, int pitch, double *out2_host);
+/* spec_padded: a padded spectrum delta(k), normalised as get_field_fft normalises (abacus_zcv_spectrum_dev), n even, aligned to 16
+ * bytes.  In place: every mode times exp(-k^2 R^2 / 2) in float32 - the multiplier of abacus_zcv_filter_dev with kcut = 1 / R:
+ * dk = float32(2 pi / Lbox), index i -> i below n/2, i - n from n/2 on (x, y), 0 .. n/2 on z, expf(-(kx^2 + ky^2 + kz^2) /
+ * float32(2 / R^2)) - then the C2R in place (no normalisation): the padded real mesh delta_R(x) in the first n floats of every row.
+ * R >= 0 and finite; R = 0: no filter.  hipFFT may take a work area. */
+int abacus_mf_smooth_spectrum_dev(void *spec_padded, int n, double Lbox, double R);
+
 /* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
  * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
  * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
