@@ -80,6 +80,7 @@ def lib():
         L.abacus_get_stream.restype = C.c_void_p
         L.abacus_power_geometry_ms.restype = C.c_double
         L.abacus_pairvel.restype = L.abacus_pairvel_dev.restype = C.c_int    # analysis/pairwise_velocity.py
+        L.abacus_fof.restype = L.abacus_fof_dev.restype = L.abacus_fof_stats.restype = C.c_int     # analysis/groups.py
         _lib = L
     return _lib
 

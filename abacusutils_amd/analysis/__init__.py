@@ -1,4 +1,5 @@
 from .bispectrum import bispectrum_from_spectrum, calc_bispectrum, triangle_counts  # noqa: F401
+from .groups import fof_groups, group_properties, group_sizes, linking_lengths, multiplicity_function  # noqa: F401
 from .lensing import ProjectedParticles, delta_sigma, delta_sigma_box, delta_sigma_from_sums, projected_sums  # noqa: F401
 from .minkowski import (calc_minkowski, gaussian_prediction, mesh_moments, minkowski_counts, minkowski_from_counts,  # noqa: F401
                         minkowski_functionals)

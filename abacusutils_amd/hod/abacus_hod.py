@@ -644,6 +644,15 @@ class AbacusHOD:
         return {tr: vpf(rmax, nbins, nspheres, numpN, seed, *self._xyz(mock_dict, tr), periodic=True, boxsize=self.lbox)
                 for tr in mock_dict.keys()}
 
+    def compute_groups(self, mock_dict, b_perp, b_par=None, nmax=64, return_labels=False):
+        """{tracer: the friends-of-friends groups of the tracer} (analysis/groups.py: `fof_groups` - 'labels', 'ngroups', 'mult',
+        'n'); b_perp and b_par in box units (`groups.linking_lengths` turns fractions of the mean separation into them), b_par:
+        cylinders along z.  The galaxies stay in HBM when `mock_dict` is the untouched result of the latest run_hod; one
+        catalogue per call - no groups across tracers"""
+        from ..analysis.groups import fof_groups
+        return {tr: fof_groups(*self._xyz(mock_dict, tr), self.lbox, b_perp, b_par=b_par, nmax=nmax, return_labels=return_labels)
+                for tr in mock_dict.keys()}
+
     def compute_knn(self, mock_dict, radii, ks, nquery, seed=42, pimax=None, data_queries=False):
         """{tracer: the kNN-CDFs (len(ks), len(radii)) of `nquery` random centres} (analysis/spheres.py: `knn_cdf`); pimax: the
         (rp, pi) form.  data_queries: also '{a}_{b}' for every ORDERED tracer pair - the galaxies of a as queries around the

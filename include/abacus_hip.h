@@ -693,6 +693,38 @@ int abacus_spherecount_dev(const void *x, const void *y, const void *z, int64_t 
 int abacus_spherecount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z);
 
 /*
+ * Friends-of-friends groups of one catalogue on the periodic box: a group label per point and the multiplicity function n(N)
+ * (analysis/groups.py).  No reference code stands behind this: the conventions below are the contract, pinned against the NumPy
+ * statement tests/groups_statement.py, whose per-point degrees are the counts in spheres of the set around itself.
+ *   friends  two points i != j are friends under the float32 expressions of abacus_spherecount, bit for bit: d = p_i - p_j per
+ *            component, one -+boxsize when |d| > boxsize / 2;
+ *            spheres (b_par = 0): r2 = dx dx + dy dy + dz dz left to right, no FMA; friends iff r2 < b_perp * b_perp (a float32
+ *            product), strictly;
+ *            cylinders (b_par > 0, the line of sight along z): r2 = dx dx + dy dy; friends iff r2 < b_perp * b_perp and
+ *            |dz| < b_par, both strictly;
+ *            a coincident twin is a friend; a point is not its own friend - by identity, not by distance;
+ *   groups   the connected components of the friendship graph;
+ *   labels   NULL, or [n] uint32 in the CALLER's order: labels[i] = the smallest caller index among the members of i's group - a
+ *            pure function of the input, whatever order the unions ran in; with NULL nothing of size n is copied back;
+ *   ngroups  the number of i with labels[i] == i, i.e. the number of groups;
+ *   mult     [nmax + 1] uint64: mult[N] = groups with exactly N members for N < nmax, mult[0] = 0, mult[nmax] = those with nmax or
+ *            more; the entries sum to ngroups.
+ * Checked before the device is touched (every message starts with "abacus_fof: ", from both entries): x, y, z, mult, ngroups not
+ * NULL; pos_dtype ABACUS_F32 or ABACUS_F64; boxsize > 0; b_perp > 0; b_par >= 0; b_perp and b_par at most boxsize / 2 (the
+ * minimum image is not unique beyond); 0 <= n < 2^31; nmax >= 1 and nmax + 1 <= 8192 (the LDS histogram).
+ * Empty cases: n = 0 gives zeros in every output; n = 1 one group of one.
+ * _dev: the columns in HBM, of ONE dtype (pos_dtype; float64 is cast to float32 on the device); mult, labels and ngroups are host
+ * pointers in both forms.  Coordinates may lie in any interval, as for abacus_paircount_dev.
+ * abacus_fof_stats: of the last call, the candidate pairs evaluated, the unordered friend pairs found (exact: every pair is taken
+ * once) and the cells per dimension in xy / z.
+ */
+int abacus_fof(const float *x, const float *y, const float *z, int64_t n, float boxsize, float b_perp, float b_par, int nmax,
+               uint64_t *mult, uint32_t *labels, uint64_t *ngroups);
+int abacus_fof_dev(const void *x, const void *y, const void *z, int64_t n, int pos_dtype, float boxsize, float b_perp, float b_par,
+                   int nmax, uint64_t *mult, uint32_t *labels, uint64_t *ngroups);
+int abacus_fof_stats(uint64_t *candidates, uint64_t *links, int *ncell_xy, int *ncell_z);
+
+/*
  * Galaxy-galaxy lensing on the periodic box: the projected mass sums around galaxies, from which the excess surface density
  * Delta Sigma(R) follows (analysis/lensing.py).  The line of sight is a box axis and the projection runs along the whole box,
  * so both sets are pairs of TRANSVERSE columns.  The particles are sorted once into a 2-D periodic cell grid and stay in HBM
