@@ -1,5 +1,5 @@
 """Friends-of-friends galaxy groups on the MI355X: a group label per point and the group multiplicity function n(N) of one
-catalogue on the periodic box (csrc/pairs.hip: fof_link and the three kernels behind it, C ABI `abacus_fof[_dev]`), and what is
+catalogue on the periodic box (csrc/fof.hip: fof_link and the three kernels behind it, C ABI `abacus_fof[_dev]`), and what is
 built on the labels on the host - group sizes, richness-binned n(N) per volume, per-group centres and weight sums.
 
 The reference has no group finder: the conventions are those of include/abacus_hip.h, pinned against the NumPy statement

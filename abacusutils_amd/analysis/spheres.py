@@ -1,5 +1,5 @@
 """Counts in spheres on the MI355X: for every query point the number of data points inside each of a set of radii, on the
-periodic box (csrc/pairs.hip: sphere_count, C ABI `abacus_spherecount[_dev]`), and what is built from it - the void
+periodic box (csrc/spheres.hip: sphere_count, C ABI `abacus_spherecount[_dev]`), and what is built from it - the void
 probability function and the count probabilities P_N(r) (`vpf`, Corrfunc.theory.vpf's signature), the k-nearest-neighbour
 CDFs (`knn_cdf`: P(N(<r) >= k)) in 3-D and in the (rp, pi) form, and the per-centre counts a counts-in-cells or
 density-split analysis starts from (`count_in_spheres(..., return_counts=True)`).

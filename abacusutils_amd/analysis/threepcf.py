@@ -1,5 +1,5 @@
 """Three-point correlation function multipoles zeta_l(r1, r2) on the MI355X: the multipole algorithm of Slepian & Eisenstein
-(2015, MNRAS 454, 4142) on the periodic box (csrc/pairs.hip: threepcf_walk, C ABI `abacus_threepcf[_dev]`) - the
+(2015, MNRAS 454, 4142) on the periodic box (csrc/threepcf.hip: threepcf_walk, C ABI `abacus_threepcf[_dev]`) - the
 configuration-space partner of `analysis.bispectrum.calc_bispectrum`.
 
 The reference has none of this and Corrfunc has no 3PCF: the conventions are those of include/abacus_hip.h, pinned against the

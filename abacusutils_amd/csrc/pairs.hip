@@ -17,240 +17,22 @@
 // a missing weight array is unit weights; the weight is sorted into cells WITH its point (both sort paths); float64 atomics
 // make the sums reproducible to n 2^-52 sum|term| per bin, not bit for bit.
 //
-// What this file holds, in order:
-//   grids and the cell sort   CellGrid (periodic box), OpenGrid (bounding box of a light cone); cell_count<COUNT, W, Grid>,
-//                             cell_fill / cell_gather / cell_starts (counting sort below 200 000 points, radix sort above)
-//   unweighted, periodic      pair_count (first generation: the comparator of the tests), pair_count2, pair_count3 (default)
-//   weighted and light cone   one walk in two bodies: pair_count_w (periodic, float32), pair_count_los (open grid, float64)
-//   pairwise velocities       pair_vel: the walk of pair_count_w with the velocities of both sets, five float64 velocity sums per bin
-//   host helpers              one set of work buffers, stage_columns, sort_into_cells, launch helpers, the run loop
-//   jackknife                 pair_count_jk / pair_count_los_jk (the two walks with per-region histograms), the label-aware
-//                             sort, the per-region outputs
-//   counts in spheres         sphere_count: per query the data points inside each of nr radii (the walk of pair_count_w, a
-//                             wave-wide ballot per radius instead of a histogram atomic per pair), then a histogram over queries
-//   3PCF multipoles           threepcf_walk: per primary the spherical-harmonic sums of its neighbours per bin (the same walk, counted
-//                             pairs compacted into an LDS queue), then a Gram matrix per l; its driver count_threepcf stands with it
-//   the drivers               count_box (periodic) and count_los (open grid), each the plain and - with labels - the jackknife
-//                             counter, and count_spheres; validation, grids, kernel arguments and statistics in one place each;
-//                             the C ABI
-//   friends-of-friends        fof_link (the walk of sphere_count, a lock-free union per friend pair), fof_flatten, fof_reduce,
-//                             fof_emit, their driver find_groups and its C entries: at the file's end, behind every other kernel
+// The cell sort, the work buffers and the other families (jackknife, spheres, 3PCF, friends-of-friends): pairs_common.hpp lists
+// the files.  Here: the unweighted periodic kernels pair_count (first generation: the comparator of the tests), pair_count2,
+// pair_count3 (default); one walk in two bodies, pair_count_w (periodic, float32) and pair_count_los (open grid, float64);
+// pair_vel, the walk of pair_count_w with the velocities of both sets; each kernel's launch below it; the two drivers, each the
+// plain and - with labels - the jackknife counter (pairs_jk.hip), and the C ABI.
 #include <cmath>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 
-#include <hipcub/hipcub.hpp>
-
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "pairs_common.hpp"
 
 using namespace abacus;
-
-namespace abacus {
-int exclusive_scan_u32(unsigned int *counters, int64_t n, int64_t *out, DevBuf &scratch, int zero_counters);
-}
+using namespace abacus::pairs;
 
 namespace {
-
-constexpr int PB = 256;          // threads per workgroup
-constexpr int MAX_HIST = 8192;   // LDS histogram entries (bins * sub-bins)
-
-__device__ __forceinline__ int cell_coord(float v, int nc, float inv_box) {
-    // fractional position in the box, periodic: works for [0,L), [-L/2,L/2) or anything else
-    float f = v * inv_box;
-    f -= floorf(f);
-    int c = (int)(f * (float)nc);
-    return c >= nc ? nc - 1 : c;
-}
-
-struct CellGrid {
-    int ncx, ncy, ncz;
-    float box, inv_box;
-    __device__ __forceinline__ int cell(const float v[3]) const {
-        return (cell_coord(v[0], ncx, inv_box) * ncy + cell_coord(v[1], ncy, inv_box)) * ncz + cell_coord(v[2], ncz, inv_box);
-    }
-};
-
-// Open grid of a light cone: the bounding box of both sets, per-dimension cell counts 1 .. 128 with a cell side >= 1.0001
-// reach; cell = min(int((v - lo) inv_cell), nc - 1) in float32; neighbour cells outside the grid are skipped, nothing wraps.
-// The three float32 roundings of the cell index move a point by less than 3 2^-24 nc cells, so two points whose indices
-// differ by 2 or more are further apart than (1 - 5e-5) of a cell side > reach: the 27 cells suffice.
-struct OpenGrid {
-    int nc[3];
-    float lo[3], inv[3];
-    __device__ __forceinline__ int cell(const float v[3]) const {
-        int c[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            c[d] = (int)((v[d] - lo[d]) * inv[d]);
-            c[d] = c[d] >= nc[d] ? nc[d] - 1 : (c[d] < 0 ? 0 : c[d]);   // c < 0: only a NaN coordinate, kept inside the arrays
-        }
-        return (c[0] * nc[1] + c[1]) * nc[2] + c[2];
-    }
-};
-
-// Coordinate frame of a catalogue: the smallest and the largest coordinate per dimension as order-preserving integer keys
-// (so that atomicMin / atomicMax work on floats).  Corrfunc accepts any coordinate range; galaxies from the HOD live in
-// [-L/2, L/2).  When every coordinate of both sets lies in ONE interval [a, a + L) the periodic image of a pair of cells
-// is known per cell pair (pair_count3); `outside` only says that the frame is not [0, L).
-struct Frame {
-    unsigned int mn[3], mx[3];
-};
-__device__ __forceinline__ unsigned int fkey(float v) {
-    const unsigned int u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float funkey(unsigned int k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// A thread's smallest and largest keys per dimension into *frame: wave reduction, then ONE pair of global atomics per workgroup
-// and dimension (one per wave was 10^5 atomics on six addresses: 1 ms of cell_count's 1.1).  Every thread of the workgroup calls.
-struct MinMax {
-    unsigned int mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    __device__ __forceinline__ void take(const float v[3]) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const unsigned int k = fkey(v[d]);
-            mn[d] = min(mn[d], k), mx[d] = max(mx[d], k);
-        }
-    }
-};
-__device__ __forceinline__ void frame_reduce(const MinMax &m, Frame *__restrict__ frame) {
-    __shared__ unsigned int s_mn[3], s_mx[3];
-    if (threadIdx.x < 3) s_mn[threadIdx.x] = 0xffffffffu, s_mx[threadIdx.x] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        unsigned int a = m.mn[d], b = m.mx[d];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a = min(a, (unsigned int)__shfl_xor((int)a, off, 64)), b = max(b, (unsigned int)__shfl_xor((int)b, off, 64));
-        if ((threadIdx.x & 63) == 0 && a <= b) atomicMin(&s_mn[d], a), atomicMax(&s_mx[d], b);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && s_mn[threadIdx.x] <= s_mx[threadIdx.x])
-        atomicMin(&frame->mn[threadIdx.x], s_mn[threadIdx.x]), atomicMax(&frame->mx[threadIdx.x], s_mx[threadIdx.x]);
-}
-
-// The cell of every point on either grid.  COUNT: per-cell counters by global atomics (counting sort, small inputs); else the
-// cell ids become the keys of a radix sort and idx the values.  W (weighted counts): the point's weight rides in the free lane
-// of the packed record.  The periodic grid alone keeps the frame and `outside` (some coordinate is not in [0, L)): FramedGrid.
-struct FramedGrid : CellGrid {
-    int *outside;
-    Frame *frame;
-};
-template <bool COUNT, bool W, typename Grid>
-__global__ void cell_count(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                           const float *__restrict__ w, int64_t n, Grid g, unsigned int *__restrict__ counts, unsigned int *__restrict__ cellid,
-                           unsigned int *__restrict__ idx, float4 *__restrict__ packed) {
-    constexpr bool PERIODIC = std::is_same<Grid, FramedGrid>::value;
-    bool out = false;
-    MinMax m;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {x[i], y[i], z[i]};
-        const int c = g.cell(v);
-        cellid[i] = (unsigned int)c;
-        if (COUNT) atomicAdd(&counts[c], 1u);
-        else idx[i] = (unsigned int)i, packed[i] = make_float4(v[0], v[1], v[2], W ? w[i] : 0.f);   // one 16-B piece per point for the gather
-        if constexpr (PERIODIC) {
-            out = out || !(v[0] >= 0.f && v[0] < g.box && v[1] >= 0.f && v[1] < g.box && v[2] >= 0.f && v[2] < g.box);
-            m.take(v);
-        }
-    }
-    if constexpr (PERIODIC) {
-        if (out) *g.outside = 1;
-        frame_reduce(m, g.frame);
-    }
-}
-
-// bounding box of a set as order-preserving keys (fkey)
-__global__ void bbox_minmax(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, int64_t n,
-                            Frame *__restrict__ frame) {
-    MinMax m;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {x[i], y[i], z[i]};
-        m.take(v);
-    }
-    frame_reduce(m, frame);
-}
-
-// observer-centred float32 columns: the subtraction in the column's own dtype, then one rounding (dst may be src).  With
-// origin 0 this is the plain cast of float64 columns (the HOD catalogue), as the reference casts before it calls Corrfunc
-// (analysis/tpcf_corrfunc.py:134-139: `.astype(np.float32)`, round to nearest): x - 0.0 is x for every double.
-template <typename T>
-__global__ void los_centre(const T *src, T origin, float *dst, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)(src[i] - origin);
-}
-
-// W: the weight takes the slot its point drew (the order inside a cell differs from run to run, point and weight stay together)
-template <bool W>
-__global__ void cell_fill(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                          const float *__restrict__ w, int64_t n, const unsigned int *__restrict__ cellid,
-                          const int64_t *__restrict__ start, unsigned int *__restrict__ cursor, float *__restrict__ sx,
-                          float *__restrict__ sy, float *__restrict__ sz, float *__restrict__ sw) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned int c = cellid[i];
-        const int64_t s = start[c] + atomicAdd(&cursor[c], 1u);
-        sx[s] = x[i];
-        sy[s] = y[i];
-        sz[s] = z[i];
-        if (W) sw[s] = w[i];
-    }
-}
-
-// behind the radix sort of (cell id, point index): the points in cell order (ties in input order: the sort is stable, so
-// the sorted arrays do not depend on the run) ...
-template <bool W>
-__global__ void cell_gather(const float4 *__restrict__ packed, int64_t n, const unsigned int *__restrict__ idx,
-                            float *__restrict__ sx, float *__restrict__ sy, float *__restrict__ sz, float *__restrict__ sw) {
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        const float4 p = packed[idx[s]];   // one memory sector per point instead of three (x, y, z live in separate arrays)
-        sx[s] = p.x, sy[s] = p.y, sz[s] = p.z;
-        if (W) sw[s] = p.w;
-    }
-}
-// ... their velocities behind them, by the same sorted index (abacus_pairvel) ...
-__global__ void vel_gather(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz, int64_t n,
-                           const unsigned int *__restrict__ idx, float *__restrict__ svx, float *__restrict__ svy, float *__restrict__ svz) {
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned int i = idx[s];
-        svx[s] = vx[i], svy[s] = vy[i], svz[s] = vz[i];
-    }
-}
-// ... and the first point of every cell: start[c] = number of keys below c (c = 0 .. ncell)
-__global__ void cell_starts(const unsigned int *__restrict__ keys, int64_t n, int64_t ncell, int64_t *__restrict__ start) {
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= ncell; c += (int64_t)gridDim.x * blockDim.x) {
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)keys[mid] < c) lo = mid + 1;
-            else hi = mid;
-        }
-        start[c] = lo;
-    }
-}
-
-struct PairArgs {
-    int mode, autocorr, in_box;   // in_box: every coordinate of both sets lies in [0, L)
-    CellGrid g;
-    int nbins, nsub;
-    float half, pimax, dpi, mu_max, inv_dmu;
-    const float *edges2;   // (nbins+1) squared edges
-    // bin look-up of pair_count3: the float32 bit pattern of r^2, shifted by lut_sh, minus lut_off indexes lut_ncell cells, none
-    // of which holds more than one inner edge (0 cells: the kernel walks the edges instead)
-    int lut_sh, lut_off, lut_ncell;
-    int no_blocks;         // pair_count3: every cell a job of its own (comparator of the two-cell blocks)
-    const float *x1, *y1, *z1, *x2, *y2, *z2;
-    const int64_t *start1, *start2;
-    unsigned long long *npairs;
-};
-
-__device__ __forceinline__ float min_image(float d, float half, float box) {
-    if (d > half) return d - box;
-    if (d < -half) return d + box;
-    return d;
-}
 
 // One workgroup per (cell of set 1, slice of its points).
 __global__ __launch_bounds__(PB) void pair_count(PairArgs a, const int *__restrict__ work_cell,
@@ -880,6 +662,79 @@ __global__ __launch_bounds__(P3_WAVES * 64) void pair_count3(PairArgs a, const F
         if (hist[q]) atomicAdd(&a.npairs[q], mult * (unsigned long long)hist[q]);
 }
 
+// The unweighted periodic count of a run by the generation asked for (pairs_gen; 1, 2: the comparators of the tests); R_used:
+// the stencil of pair_count3, 0 when an older kernel ran
+int launch_unweighted(PairArgs &a, int gen, int R, const std::vector<float> &e2, const Flags &fl, int64_t ncell, int &R_used) {
+    Work &W = g_work;
+    const CellGrid &g = a.g;
+    const int nb = a.nbins;
+    const size_t ntot = (size_t)nb * a.nsub;
+    R_used = 0;
+    if (gen == 1) {   // first-generation kernel: host-built work list, one workgroup per 256 points of a non-empty cell
+        std::vector<int64_t> start1((size_t)ncell + 1);
+        HIP_TRY(hipMemcpyAsync(start1.data(), W.S[0].start.p, (size_t)(ncell + 1) * 8, hipMemcpyDeviceToHost, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        std::vector<int> wc, wo;
+        for (int64_t c = 0; c < ncell; c++)
+            for (int64_t off = 0; off < start1[c + 1] - start1[c]; off += PB) wc.push_back((int)c), wo.push_back((int)off);
+        const int nwork = (int)wc.size();
+        ABACUS_TRY(W.list.reserve((size_t)std::max(nwork, 1) * 8));
+        int *d_wc = W.list.as<int>(), *d_wo = d_wc + std::max(nwork, 1);
+        HIP_TRY(hipMemcpyAsync(d_wc, wc.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
+        HIP_TRY(hipMemcpyAsync(d_wo, wo.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
+        HIP_TRY(hipStreamSynchronize(stream()));
+        if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
+        return 0;
+    }
+    if (gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1) {
+        R_used = R;
+        // cells of the bin table: the coarsest 2^m per octave (m = 2 .. 8) that keep the inner edges apart, at most 8192 cells
+        a.no_blocks = option("pairs_noblocks");
+        if (!option("pairs_nolut") && e2[0] >= 0.f) {
+            auto fbits = [](float v) {
+                unsigned int u;
+                memcpy(&u, &v, 4);
+                return u;
+            };
+            for (int m = 2; m <= 8 && !a.lut_ncell; m++) {
+                const int sh = 23 - m;
+                const unsigned int c0 = fbits(e2[0]) >> sh, c1 = fbits(e2[nb]) >> sh;
+                if (c1 - c0 + 1 > 8192u) break;
+                bool ok = true;
+                for (int b = 1; b + 1 < nb && ok; b++) ok = (fbits(e2[b]) >> sh) != (fbits(e2[b + 1]) >> sh);
+                for (int b = 0; b < nb && ok; b++) ok = e2[b] < e2[b + 1];
+                if (ok) a.lut_sh = sh, a.lut_off = (int)c0, a.lut_ncell = (int)(c1 - c0 + 1);
+            }
+        }
+        const bool lut = a.lut_ncell > 0;
+        const size_t hist_bytes = ((ntot + 1) & ~(size_t)1) * sizeof(unsigned int) + (size_t)a.lut_ncell * sizeof(uint2);
+        return with_mode(a.mode, [&](auto M) {
+            return with_flag(lut, [&](auto LUT) -> int {
+                const auto kernel = pair_count3<decltype(M)::value, decltype(LUT)::value>;
+                if (hist_bytes > 48 * 1024)
+                    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
+                dim3 grid;   // persistent waves: as many workgroups as are resident at once
+                ABACUS_TRY(resident_grid(kernel, P3_WAVES * 64, hist_bytes, ceil_div(ncell, P3_WAVES), grid));
+                ABACUS_LAUNCH("pair_count", kernel, grid, dim3(P3_WAVES * 64), hist_bytes, a, fl.frame, (int)ncell, R, fl.evaluated);
+                return 0;
+            });
+        });
+    }
+    int ncu = 256;
+    ABACUS_TRY(cu_count(ncu));
+    const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * 8));
+    const size_t hist_bytes = ntot * sizeof(unsigned int);
+    // a few points per cell: stage all neighbour cells together (one round per slice instead of 27)
+    const bool agg = (double)W.S[a.autocorr ? 0 : 1].n / (double)ncell < 12.0;
+    return with_mode(a.mode, [&](auto M) {
+        return with_flag(agg, [&](auto AGG) -> int {
+            ABACUS_LAUNCH("pair_count", (pair_count2<decltype(M)::value, decltype(AGG)::value>), grid, dim3(PB), hist_bytes, a,
+                          (const int *)fl.outside, (int)ncell);
+            return 0;
+        });
+    });
+}
+
 // Weighted counter: per (bin, sub-bin) the integer count, sum of w_i w_j and sum of the pair separation (r | rp | s).
 // One kernel for every geometry: cells of the full reach (or one cell per dimension when fewer than 3 fit), a persistent
 // workgroup per cell of set 1, the 27 (or fewer) neighbour cells as ONE virtual list of which every thread fetches one point
@@ -892,13 +747,10 @@ __global__ __launch_bounds__(P3_WAVES * 64) void pair_count3(PairArgs a, const F
 //     them to the histogram once, at the end (64 lanes on one LDS address serialise; a ballot cannot carry a float64 sum).
 //   * An entry is 20 bytes: W_MAX_HIST entries per launch, more are counted in runs of separation bins (for_runs).
 //   * The autocorrelation walks the full stencil (ordered pairs, nothing is doubled).
-// pair_count_los below is this walk on the open grid: a fix to one belongs in both (profiles/pairs_shared_walk/README.md).
+// pair_count_los below is this walk on the open grid, pair_vel its copy with velocities; pair_count_jk and pair_count_los_jk
+// (pairs_jk.hip), sphere_count (spheres.hip), threepcf_walk (threepcf.hip) and fof_link (fof.hip) repeat it too: a fix to one
+// walk belongs in all of them (profiles/pairs_shared_walk/README.md).
 constexpr int W_MAX_HIST = 2048;
-
-struct WeightArgs {
-    const float *w1, *w2;   // weights in cell order; NULL: unit weights
-    double *wsum, *rsum;    // rsum is read only when RSUM
-};
 
 template <int MODE, bool RSUM>
 __global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, int ncell, unsigned long long *__restrict__ evaluated) {
@@ -1025,10 +877,23 @@ __global__ __launch_bounds__(PB) void pair_count_w(PairArgs a, WeightArgs wa, in
         }
 }
 
+int launch_weighted(const PairArgs &a, const WeightArgs &wa, bool rsum, const Flags &fl, int64_t ncell) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
+    return with_mode(a.mode, [&](auto M) {
+        return with_flag(rsum, [&](auto RS) -> int {
+            const auto kernel = pair_count_w<decltype(M)::value, decltype(RS)::value>;
+            dim3 grid;
+            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+            ABACUS_LAUNCH("pair_count_w", kernel, grid, dim3(PB), hist_bytes, a, wa, (int)ncell, fl.evaluated);
+            return 0;
+        });
+    });
+}
+
 // Pairwise velocity sums (abacus_pairvel; halotools' mean_radial_velocity_vs_r / radial_pvd_vs_r / mean_los_velocity_vs_rp /
 // los_pvd_vs_rp are moments of them).  The walk, the membership tests and the bin of pair_count_w, untouched - npairs and wsum are
 // that counter's - with the velocities of both sets riding along; a fix to one walk belongs in all of them
-// (profiles/pairs_shared_walk/README.md).  Per counted pair: u = v_i - v_j in float32, then float64, left to right, no FMA
+// (the other copies: pair_count_w's comment names their files; profiles/pairs_shared_walk/README.md).  Per counted pair: u = v_i - v_j in float32, then float64, left to right, no FMA
 // (this file is built with contraction off):
 //   s2 = dx dx + dy dy + dz dz, t = ux dx + uy dy + uz dz, vr = s2 > 0 ? t / sqrt(s2) : 0 (negative: approaching),
 //   uu = ux ux + uy uy + uz uz, vz = uz sign(dz) (the minimum-image float32 dz; sign(0) = 0)
@@ -1184,6 +1049,21 @@ __global__ __launch_bounds__(PB) void pair_vel(PairArgs a, WeightArgs wa, VelArg
         }
 }
 
+int launch_vel(const PairArgs &a, const WeightArgs &wa, const VelArgs &va, const Flags &fl, int64_t ncell) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 52;   // <= V_MAX_HIST * 52 = 52 KiB beside 7.6 KiB of static LDS
+    return with_mode(a.mode, [&](auto M) {
+        return with_flag(a.mode != 0 || !option("pairvel_lds_top"), [&](auto TOP) -> int {   // modes 1, 2 have no such path: one instance
+            const auto kernel = pair_vel<decltype(M)::value, decltype(TOP)::value>;
+            if (hist_bytes > 48 * 1024)
+                HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
+            dim3 grid;
+            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+            ABACUS_LAUNCH("pair_vel", kernel, grid, dim3(PB), hist_bytes, a, wa, va, (int)ncell, fl.evaluated);
+            return 0;
+        });
+    });
+}
+
 // Light cones: pair counts with a PAIRWISE line of sight on an OPEN grid (abacus_paircount_los, Corrfunc.mocks' DDrppi_mocks /
 // DDsmu_mocks on Cartesian columns).  No reference code and no Corrfunc run stands behind this; the conventions are restated
 // here and pinned against the NumPy statement tests/pairs_los_statement.py.
@@ -1209,18 +1089,6 @@ __global__ __launch_bounds__(PB) void pair_vel(PairArgs a, WeightArgs wa, VelArg
 //   float32(e2[0] (1 - 2^-20)) rounded DOWN, and 0 (test off) when that is below 1e-30: above it an underflowing product
 //   (< 1.2e-38 lost) moves s2f by less than 2^-22 relative too.  s2f < pre_lo implies s2 < e2[0] (1 - 2^-20) (1 + 2^-22) < e2[0].
 // NaN fails both comparisons and falls to the float64 path, which counts nothing for it.
-struct LosArgs {
-    int autocorr, nc[3], nbins, nsub;
-    // float32 pre-test: a candidate with s2f > pre_hi or s2f < pre_lo skips the float64 arithmetic (see above)
-    float pre_lo, pre_hi;
-    double pimax, dpi, mu_max, inv_dmu;
-    const double *edges2;   // (nbins + 1) squared edges
-    const float *x1, *y1, *z1, *w1, *x2, *y2, *z2, *w2;   // cell order; w NULL: unit weights
-    const int64_t *start1, *start2;
-    unsigned long long *npairs;
-    double *wsum, *rsum;
-};
-
 // The walk of pair_count_w on the open grid: a persistent workgroup per non-empty cell of set 1, the in-range neighbour cells
 // as ONE virtual list; LDS histogram ([WEIGHTED: sums of w w] [RSUM: sums of sqrt(q)] counts), flushed once per workgroup; full
 // stencil for the autocorrelation; MODE 0 keeps the last bin in registers.
@@ -1356,217 +1224,24 @@ __global__ __launch_bounds__(PB) void pair_count_los(LosArgs a, int ncell, unsig
         }
 }
 
-// ------------------------------------------------------------------------------------------------------------- host side ----
-struct SortedSet {
-    DevBuf sorted, counts, cellid, start, keys2, idx, idx2, tmp, packed, wsorted, vsorted;
-    float *sx, *sy, *sz, *sw;   // sw: the weights in cell order (weighted counts with weights for this set), else NULL
-    float *sv[3];               // the velocities in cell order (sort_into_cells with velocities), else stale
-    int64_t n;
-};
-
-// Empty frame, block of flags and counters in HBM: [0] outside, [16] Frame, [48] candidate pairs evaluated
-const Frame EMPTY_FRAME = {{0xffffffffu, 0xffffffffu, 0xffffffffu}, {0u, 0u, 0u}};
-struct Flags {
-    int *outside;
-    Frame *frame;
-    unsigned long long *evaluated;
-};
-
-// The work buffers of every counter of this file: the library serialises its entry points (ABACUS_ENTER), so the periodic and
-// the light-cone driver take turns on one set
-struct Work {
-    SortedSet S[2];
-    DevBuf cols[2], wts[2];   // staged float32 columns and weights of the two sets
-    DevBuf vcols[2];          // and their staged velocities (abacus_pairvel)
-    DevBuf scratch, edges, out, list, flag;
-    int flags(Flags &f) {
-        ABACUS_TRY(flag.reserve(64));
-        f.outside = flag.as<int>(), f.frame = reinterpret_cast<Frame *>(flag.as<char>() + 16);
-        f.evaluated = reinterpret_cast<unsigned long long *>(flag.as<char>() + 48);
-        HIP_TRY(hipMemsetAsync(flag.p, 0, 64, stream()));
-        HIP_TRY(hipMemcpyAsync(f.frame, &EMPTY_FRAME, sizeof EMPTY_FRAME, hipMemcpyHostToDevice, stream()));
+// weighted: with sums of w w; rs: and of the separation
+int launch_los(int mode, const LosArgs &a, bool weighted, bool rs, const Flags &fl, int64_t ncell) {
+    const size_t hist_bytes = (size_t)a.nbins * a.nsub * (4 + (weighted ? 8 : 0) + (rs ? 8 : 0));
+    auto launch = [&](auto M, auto WT, auto RS) -> int {
+        const auto kernel = pair_count_los<decltype(M)::value, decltype(WT)::value, decltype(RS)::value>;
+        dim3 grid;
+        ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
+        ABACUS_LAUNCH("pair_count_los", kernel, grid, dim3(PB), hist_bytes, a, (int)ncell, fl.evaluated);
         return 0;
-    }
-} g_work;
-
-struct Columns {   // float32 device columns of a set, with its weights (NULL: none)
-    const float *x[3], *w;
-};
-
-// Caller columns -> float32 device columns.  where = 0: host float32 arrays (and host weights); 1: device float32; 2: device
-// float64 (device weights).  origin (NULL: none) is subtracted in the column's own dtype before the one rounding; device float32
-// columns that need no shift are read in place.  n > 0.  `label` names the conversion kernel to the profiler.
-int stage_columns(const char *label, const void *const src[3], const float *w, int where, int64_t n, const double *origin,
-                  DevBuf &cols, DevBuf &wts, Columns &c) {
-    const bool shifted = origin && (origin[0] != 0.0 || origin[1] != 0.0 || origin[2] != 0.0);
-    const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 2048);
-    if (where == 1 && !shifted) {
-        for (int d = 0; d < 3; d++) c.x[d] = (const float *)src[d];
-    } else {
-        ABACUS_TRY(cols.reserve(3 * (size_t)n * 4));
-        for (int d = 0; d < 3; d++) {
-            float *dst = cols.as<float>() + (size_t)d * n;
-            const double o = origin ? origin[d] : 0.0;
-            c.x[d] = dst;
-            if (where == 2) {
-                ABACUS_LAUNCH(label, los_centre<double>, dim3(nblk), dim3(256), 0, (const double *)src[d], o, dst, n);
-                continue;
-            }
-            const float *from = (const float *)src[d];
-            if (where == 0) {
-                HIP_TRY(hipMemcpyAsync(dst, from, (size_t)n * 4, hipMemcpyHostToDevice, stream()));
-                from = dst;
-            }
-            if (shifted) ABACUS_LAUNCH(label, los_centre<float>, dim3(nblk), dim3(256), 0, from, (float)o, dst, n);
-        }
-    }
-    c.w = w;
-    if (w && where == 0) {
-        ABACUS_TRY(wts.reserve((size_t)n * 4));
-        HIP_TRY(hipMemcpyAsync(wts.p, w, (size_t)n * 4, hipMemcpyHostToDevice, stream()));
-        c.w = wts.as<float>();
-    }
-    return 0;
+    };
+    return with_mode(mode, [&](auto M) {
+        if (rs) return launch(M, std::true_type(), std::true_type());
+        if (weighted) return launch(M, std::true_type(), std::false_type());
+        return launch(M, std::false_type(), std::false_type());
+    });
 }
 
-template <bool COUNT, bool W, typename Grid>
-int count_cells(const Columns &c, int64_t n, const Grid &g, SortedSet &s, int nblk) {
-    ABACUS_LAUNCH("pair_cell_count", (cell_count<COUNT, W, Grid>), dim3(nblk), dim3(256), 0, c.x[0], c.x[1], c.x[2], COUNT ? nullptr : c.w, n, g,
-                  COUNT ? s.counts.as<unsigned int>() : nullptr, s.cellid.as<unsigned int>(), COUNT ? nullptr : s.idx.as<unsigned int>(),
-                  COUNT ? nullptr : s.packed.as<float4>());
-    return 0;
-}
-
-// The set in cell order on either grid (ncell cells): s.sx | sy | sz, s.start and - with weights - s.sw.  vel (NULL: none): three
-// float32 device columns that follow their points into s.sv; such a set takes the radix sort at every size, whose sorted index
-// says where a point went (the counting sort hands out slots by atomics and keeps no index).  n > 0 with vel.
-template <typename Grid>
-int sort_into_cells(const Columns &c, int64_t n, const Grid &g, int64_t ncell, SortedSet &s, DevBuf &scratch, const float *const *vel = nullptr) {
-    const size_t n1 = (size_t)std::max<int64_t>(n, 1);
-    s.n = n;
-    ABACUS_TRY(s.sorted.reserve(3 * n1 * 4));
-    ABACUS_TRY(s.counts.reserve((size_t)(ncell + 1) * 4));
-    ABACUS_TRY(s.cellid.reserve(n1 * 4));
-    ABACUS_TRY(s.start.reserve((size_t)(ncell + 1) * 8));
-    const float *rx = c.x[0], *ry = c.x[1], *rz = c.x[2], *rw = c.w;
-    s.sx = s.sorted.as<float>();
-    s.sy = s.sx + n1;
-    s.sz = s.sy + n1;
-    const int nblk = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), 2048);
-    s.sw = nullptr;
-    if (rw) {
-        ABACUS_TRY(s.wsorted.reserve(n1 * 4));
-        s.sw = s.wsorted.as<float>();
-    }
-    // large inputs: stable radix sort of (cell id, index) + gather + a search per cell (10^7 points: 0.6 ms against 2.2 ms of
-    // the counting sort below, whose two passes are a global atomic per point each)
-    if (vel || (n >= 200000 && n < ((int64_t)1 << 31) && !option("pairs_countsort"))) {
-        ABACUS_TRY(s.keys2.reserve(n1 * 4));
-        ABACUS_TRY(s.idx.reserve(n1 * 4));
-        ABACUS_TRY(s.idx2.reserve(n1 * 4));
-        ABACUS_TRY(s.packed.reserve(n1 * 16));
-        if (rw) ABACUS_TRY((count_cells<false, true>(c, n, g, s, nblk)));
-        else ABACUS_TRY((count_cells<false, false>(c, n, g, s, nblk)));
-        int end_bit = 1;
-        while (((int64_t)1 << end_bit) < ncell) end_bit++;
-        size_t tmp_bytes = 0;
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, s.cellid.as<unsigned int>(), s.keys2.as<unsigned int>(),
-                                                 s.idx.as<unsigned int>(), s.idx2.as<unsigned int>(), (int)n, 0, end_bit, stream());
-        ABACUS_TRY(s.tmp.reserve(tmp_bytes));
-        prof_begin("pair_cell_sort");         // library kernels (rocPRIM radix sort of the cell ids): listed with the hand-written ones
-        const hipError_t sorted = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tmp_bytes, s.cellid.as<unsigned int>(), s.keys2.as<unsigned int>(),
-                                                                     s.idx.as<unsigned int>(), s.idx2.as<unsigned int>(), (int)n, 0, end_bit, stream());
-        prof_end("pair_cell_sort");
-        if (sorted != hipSuccess) return fail("abacus_paircount: radix sort failed");
-        if (rw)
-            ABACUS_LAUNCH("pair_cell_fill", cell_gather<true>, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(),
-                          s.sx, s.sy, s.sz, s.sw);
-        else
-            ABACUS_LAUNCH("pair_cell_fill", cell_gather<false>, dim3(nblk), dim3(256), 0, s.packed.as<float4>(), n, s.idx2.as<unsigned int>(),
-                          s.sx, s.sy, s.sz, s.sw);
-        if (vel) {
-            ABACUS_TRY(s.vsorted.reserve(3 * n1 * 4));
-            for (int d = 0; d < 3; d++) s.sv[d] = s.vsorted.as<float>() + (size_t)d * n1;
-            ABACUS_LAUNCH("pair_vel_gather", vel_gather, dim3(nblk), dim3(256), 0, vel[0], vel[1], vel[2], n, s.idx2.as<unsigned int>(), s.sv[0],
-                          s.sv[1], s.sv[2]);
-        }
-        const int cblk = (int)std::min<int64_t>(ceil_div(ncell + 1, 256), 8192);
-        ABACUS_LAUNCH("pair_cell_starts", cell_starts, dim3(cblk), dim3(256), 0, s.keys2.as<unsigned int>(), n, ncell, s.start.as<int64_t>());
-        return 0;
-    }
-    HIP_TRY(hipMemsetAsync(s.counts.p, 0, (size_t)(ncell + 1) * 4, stream()));
-    if (n > 0) ABACUS_TRY((count_cells<true, false>(c, n, g, s, nblk)));
-    ABACUS_TRY(exclusive_scan_u32(s.counts.as<unsigned int>(), ncell, s.start.as<int64_t>(), scratch, 1));
-    if (n > 0 && rw)
-        ABACUS_LAUNCH("pair_cell_fill", cell_fill<true>, dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n,
-                      s.cellid.as<unsigned int>(), s.start.as<int64_t>(), s.counts.as<unsigned int>(), s.sx, s.sy, s.sz, s.sw);
-    else if (n > 0)
-        ABACUS_LAUNCH("pair_cell_fill", cell_fill<false>, dim3(nblk), dim3(256), 0, rx, ry, rz, rw, n,
-                      s.cellid.as<unsigned int>(), s.start.as<int64_t>(), s.counts.as<unsigned int>(), s.sx, s.sy, s.sz, s.sw);
-    return 0;
-}
-
-// f(std::integral_constant<int, mode>()): the mode as a template argument of what f launches
-template <typename F>
-int with_mode(int mode, F &&f) {
-    if (mode == 0) return f(std::integral_constant<int, 0>());
-    if (mode == 1) return f(std::integral_constant<int, 1>());
-    return f(std::integral_constant<int, 2>());
-}
-template <typename F>
-int with_flag(bool on, F &&f) { return on ? f(std::true_type()) : f(std::false_type()); }
-
-int cu_count(int &ncu) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    return 0;
-}
-
-// grid of persistent workgroups: min(jobs, CUs x resident workgroups of this kernel at this block size and dynamic LDS)
-template <typename K>
-int resident_grid(K kernel, int block, size_t lds, int64_t jobs, dim3 &grid) {
-    int ncu = 256, per_cu = 1;
-    ABACUS_TRY(cu_count(ncu));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, block, lds));
-    grid = dim3((unsigned int)std::min<int64_t>(jobs, (int64_t)ncu * std::max(per_cu, 1)));
-    return 0;
-}
-
-// One launch bins into at most 63 separation bins (the kernels' edge tables) and max_hist LDS histogram entries.  More bins -
-// Corrfunc takes any number - are counted in runs of consecutive separation bins, each on a grid of its own, smaller reach; a
-// pair ON an edge shared by two runs belongs to the upper bin in both ([lo, hi) bins).  f(first bin, bins, offset in the outputs)
-template <typename F>
-int for_runs(int nbins, int nsub, int max_hist, F &&f) {
-    const int run = std::min(63, max_hist / nsub);
-    for (int b0 = 0; b0 < nbins; b0 += run) ABACUS_TRY(f(b0, std::min(run, nbins - b0), (size_t)b0 * nsub));
-    return 0;
-}
-
-// the squared edges of a run in the kernel's edge type, on the host and in g_work.edges
-template <typename Q>
-int upload_edges(const float *edges, int nb, std::vector<Q> &e2) {
-    e2.resize(nb + 1);
-    for (int b = 0; b <= nb; b++) e2[b] = (Q)edges[b] * (Q)edges[b];
-    ABACUS_TRY(g_work.edges.reserve((size_t)(nb + 1) * sizeof(Q)));
-    HIP_TRY(hipMemcpyAsync(g_work.edges.p, e2.data(), (size_t)(nb + 1) * sizeof(Q), hipMemcpyHostToDevice, stream()));
-    return 0;
-}
-
-// outputs of a run: ntot counts [| ntot sums of w w | ntot sums of the separation] in g_work.out
-struct Outputs {
-    uint64_t *npairs;
-    double *wsum, *rsum;   // NULL: not asked for
-    double *vsum = nullptr;   // abacus_pairvel: five velocity sums, [5][vstride] with this block's entries at the front of each row
-    size_t vstride = 0;
-    Outputs at(size_t o) const { return Outputs{npairs + o, wsum ? wsum + o : nullptr, rsum ? rsum + o : nullptr, vsum ? vsum + o : nullptr, vstride}; }
-    void zero(size_t ntot) const {
-        memset(npairs, 0, ntot * sizeof(uint64_t));
-        if (wsum) memset(wsum, 0, ntot * sizeof(double));
-        if (rsum) memset(rsum, 0, ntot * sizeof(double));
-        if (vsum) memset(vsum, 0, 5 * vstride * sizeof(double));
-    }
-};
+// ---------------------------------------------------------------- host side: the outputs of a run (Outputs) in g_work.out ----
 int device_outputs(size_t ntot, bool sums, bool vel, Outputs &d) {
     const size_t bytes = ((sums ? 3 : 1) + (vel ? 5 : 0)) * ntot * 8;
     ABACUS_TRY(g_work.out.reserve(bytes));
@@ -1596,925 +1271,10 @@ void fill_sets(Args &a, Sums &s, int autocorr, int nbins, int nsub, const Output
     s.w1 = S1.sw, s.w2 = T.sw, s.wsum = d.wsum, s.rsum = d.rsum;
 }
 
-// The launches of a run, one function per walk; the two drivers (below the jackknife kernels) choose among them.  Each stands
-// behind the instantiation of its family's sort: the code object lists kernels in the order of their instantiation, and the
-// launches keep that order whichever driver calls them.
-template int sort_into_cells<FramedGrid>(const Columns &, int64_t, const FramedGrid &, int64_t, SortedSet &, DevBuf &, const float *const *);
-
-int launch_weighted(const PairArgs &a, const WeightArgs &wa, bool rsum, const Flags &fl, int64_t ncell) {
-    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 20;   // <= W_MAX_HIST * 20 = 40 KiB beside 5 KiB of static LDS
-    return with_mode(a.mode, [&](auto M) {
-        return with_flag(rsum, [&](auto RS) -> int {
-            const auto kernel = pair_count_w<decltype(M)::value, decltype(RS)::value>;
-            dim3 grid;
-            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-            ABACUS_LAUNCH("pair_count_w", kernel, grid, dim3(PB), hist_bytes, a, wa, (int)ncell, fl.evaluated);
-            return 0;
-        });
-    });
-}
-
-// The unweighted periodic count of a run by the generation asked for (pairs_gen; 1, 2: the comparators of the tests); R_used:
-// the stencil of pair_count3, 0 when an older kernel ran
-int launch_unweighted(PairArgs &a, int gen, int R, const std::vector<float> &e2, const Flags &fl, int64_t ncell, int &R_used) {
-    Work &W = g_work;
-    const CellGrid &g = a.g;
-    const int nb = a.nbins;
-    const size_t ntot = (size_t)nb * a.nsub;
-    R_used = 0;
-    if (gen == 1) {   // first-generation kernel: host-built work list, one workgroup per 256 points of a non-empty cell
-        std::vector<int64_t> start1((size_t)ncell + 1);
-        HIP_TRY(hipMemcpyAsync(start1.data(), W.S[0].start.p, (size_t)(ncell + 1) * 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        std::vector<int> wc, wo;
-        for (int64_t c = 0; c < ncell; c++)
-            for (int64_t off = 0; off < start1[c + 1] - start1[c]; off += PB) wc.push_back((int)c), wo.push_back((int)off);
-        const int nwork = (int)wc.size();
-        ABACUS_TRY(W.list.reserve((size_t)std::max(nwork, 1) * 8));
-        int *d_wc = W.list.as<int>(), *d_wo = d_wc + std::max(nwork, 1);
-        HIP_TRY(hipMemcpyAsync(d_wc, wc.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
-        HIP_TRY(hipMemcpyAsync(d_wo, wo.data(), (size_t)nwork * 4, hipMemcpyHostToDevice, stream()));
-        HIP_TRY(hipStreamSynchronize(stream()));
-        if (nwork > 0) ABACUS_LAUNCH("pair_count", pair_count, dim3(nwork), dim3(PB), 0, a, d_wc, d_wo);
-        return 0;
-    }
-    if (gen >= 3 && g.ncx >= 2 * R + 1 && g.ncy >= 2 * R + 1 && g.ncz >= 2 * R + 1) {
-        R_used = R;
-        // cells of the bin table: the coarsest 2^m per octave (m = 2 .. 8) that keep the inner edges apart, at most 8192 cells
-        a.no_blocks = option("pairs_noblocks");
-        if (!option("pairs_nolut") && e2[0] >= 0.f) {
-            auto fbits = [](float v) {
-                unsigned int u;
-                memcpy(&u, &v, 4);
-                return u;
-            };
-            for (int m = 2; m <= 8 && !a.lut_ncell; m++) {
-                const int sh = 23 - m;
-                const unsigned int c0 = fbits(e2[0]) >> sh, c1 = fbits(e2[nb]) >> sh;
-                if (c1 - c0 + 1 > 8192u) break;
-                bool ok = true;
-                for (int b = 1; b + 1 < nb && ok; b++) ok = (fbits(e2[b]) >> sh) != (fbits(e2[b + 1]) >> sh);
-                for (int b = 0; b < nb && ok; b++) ok = e2[b] < e2[b + 1];
-                if (ok) a.lut_sh = sh, a.lut_off = (int)c0, a.lut_ncell = (int)(c1 - c0 + 1);
-            }
-        }
-        const bool lut = a.lut_ncell > 0;
-        const size_t hist_bytes = ((ntot + 1) & ~(size_t)1) * sizeof(unsigned int) + (size_t)a.lut_ncell * sizeof(uint2);
-        return with_mode(a.mode, [&](auto M) {
-            return with_flag(lut, [&](auto LUT) -> int {
-                const auto kernel = pair_count3<decltype(M)::value, decltype(LUT)::value>;
-                if (hist_bytes > 48 * 1024)
-                    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-                dim3 grid;   // persistent waves: as many workgroups as are resident at once
-                ABACUS_TRY(resident_grid(kernel, P3_WAVES * 64, hist_bytes, ceil_div(ncell, P3_WAVES), grid));
-                ABACUS_LAUNCH("pair_count", kernel, grid, dim3(P3_WAVES * 64), hist_bytes, a, fl.frame, (int)ncell, R, fl.evaluated);
-                return 0;
-            });
-        });
-    }
-    int ncu = 256;
-    ABACUS_TRY(cu_count(ncu));
-    const dim3 grid((unsigned int)std::min<int64_t>(ncell, (int64_t)ncu * 8));
-    const size_t hist_bytes = ntot * sizeof(unsigned int);
-    // a few points per cell: stage all neighbour cells together (one round per slice instead of 27)
-    const bool agg = (double)W.S[a.autocorr ? 0 : 1].n / (double)ncell < 12.0;
-    return with_mode(a.mode, [&](auto M) {
-        return with_flag(agg, [&](auto AGG) -> int {
-            ABACUS_LAUNCH("pair_count", (pair_count2<decltype(M)::value, decltype(AGG)::value>), grid, dim3(PB), hist_bytes, a,
-                          (const int *)fl.outside, (int)ncell);
-            return 0;
-        });
-    });
-}
-
-template int sort_into_cells<OpenGrid>(const Columns &, int64_t, const OpenGrid &, int64_t, SortedSet &, DevBuf &, const float *const *);
-
-// weighted: with sums of w w; rs: and of the separation
-int launch_los(int mode, const LosArgs &a, bool weighted, bool rs, const Flags &fl, int64_t ncell) {
-    const size_t hist_bytes = (size_t)a.nbins * a.nsub * (4 + (weighted ? 8 : 0) + (rs ? 8 : 0));
-    auto launch = [&](auto M, auto WT, auto RS) -> int {
-        const auto kernel = pair_count_los<decltype(M)::value, decltype(WT)::value, decltype(RS)::value>;
-        dim3 grid;
-        ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-        ABACUS_LAUNCH("pair_count_los", kernel, grid, dim3(PB), hist_bytes, a, (int)ncell, fl.evaluated);
-        return 0;
-    };
-    return with_mode(mode, [&](auto M) {
-        if (rs) return launch(M, std::true_type(), std::true_type());
-        if (weighted) return launch(M, std::true_type(), std::false_type());
-        return launch(M, std::false_type(), std::false_type());
-    });
-}
-
-}  // namespace
-
-// a device column, observer-centred: dst = float32(src - origin), the subtraction in the column's dtype (the estimators of
-// analysis/tpcf_corrfunc.py centre a sample once and count it against several others)
-extern "C" int abacus_paircount_los_centre(const void *src, int pos_dtype, int64_t n, double origin, float *dst) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_paircount_los_centre: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    if (n < 0 || (n > 0 && (!src || !dst)) || !std::isfinite(origin)) return fail("abacus_paircount_los_centre: bad argument");
-    ABACUS_ENTER();
-    if (n == 0) return 0;
-    const dim3 grid((unsigned int)std::min<int64_t>(ceil_div(n, 256), 2048));
-    if (pos_dtype == ABACUS_F64) ABACUS_LAUNCH("pair_los_centre", los_centre<double>, grid, dim3(256), 0, (const double *)src, origin, dst, n);
-    else ABACUS_LAUNCH("pair_los_centre", los_centre<float>, grid, dim3(256), 0, (const float *)src, (float)origin, dst, n);
-    HIP_TRY(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------ jackknife pair counts ----
-// Per-region pair counts in ONE walk (abacus_paircount_jk, abacus_paircount_los_jk): every point carries an int32 label in
-// [0, nreg) and per (bin, sub-bin) q and region k
-//   first[k][q] = pairs of q whose point of set 1 has label k,     both[k][q] = those whose point of set 2 has label k too,
-// as integer counts and as sums of w_i w_j (float64 products and sums, like wsum above).  total[q] = sum_k first[k][q] is the
-// parent counter's result; there are no separation sums here.  second[k][q] (the point of set 2 has label k) is no output:
-// membership is symmetric under exchange of the two points in every mode of both families - d -> -d negates exactly (the
-// minimum image adds -+L to -+d), so r^2, |dz|, mu, and on the light cone l = p_i + p_j, |t| and pi^2 are bit-equal - hence
-// second of (1, 2) is first of (2, 1): the autocorrelation has second = first, a cross count calls again with the sets
-// exchanged.  The expressions that decide membership and bin are those of pair_count_w / pair_count_los, untouched.
-//   * The labels ride through the cell sort (one radix sort of the key cell << bits | label - the stable label pass in front
-//     of the cell pass, fused), so a cell's slice is a few runs of constant label; with sub-box regions normally one.
-//   * A primary slice ends with its label run: ni = min(PB, end of run - i0), found in the slice's labels in LDS.
-//   * Two LDS histograms of nh entries (first | both, each a float64 sum and a u32 count: 24 bytes per entry, JK_MAX_HIST
-//     entries per launch; the unweighted light-cone count drops the sums) accumulate ONE label.  They are flushed - non-zero
-//     entries, global atomics to out[label][q] - when the next run's label differs, across cells too, and at the end; a
-//     workgroup walks a CONTIGUOUS range of cells (an equal share of the points), so that consecutive cells of one sub-box
-//     flush once.
-//   * MODE 0 keeps the last bin of both histograms in registers, per run.
-// The candidate count is the parent's: splitting slices into runs leaves sum ni M unchanged.
-namespace {
-
-constexpr int JK_MAX_HIST = 2048;
-constexpr int JK_MAX_REG = 65535;
-constexpr int64_t JK_MAX_OUT = (int64_t)1 << 24;
-
-struct JkOut {   // four arrays [nreg][stride]; a run's kernel writes columns 0 .. nh of every row (the pointers are offset)
-    unsigned long long *nfirst, *nboth;
-    double *wfirst, *wboth;   // not read by an unweighted kernel
-    size_t stride;
-    unsigned long long *flushes;
-};
-
-template <bool WEIGHTED>
-struct JkHist {
-    double *wf, *wb;
-    unsigned int *cf, *cb;
-    int nh;
-    __device__ __forceinline__ JkHist(double *base, int n) : nh(n) {
-        wf = base, wb = base + (WEIGHTED ? n : 0);
-        cf = reinterpret_cast<unsigned int *>(wb + (WEIGHTED ? n : 0)), cb = cf + n;
-    }
-    __device__ __forceinline__ void clear() const {
-        for (int q = threadIdx.x; q < nh; q += PB) {
-            cf[q] = 0u, cb[q] = 0u;
-            if (WEIGHTED) wf[q] = 0.0, wb[q] = 0.0;
-        }
-    }
-    __device__ __forceinline__ void add(int q, bool same, double ww) const {
-        atomicAdd(&cf[q], 1u);
-        if (WEIGHTED) atomicAdd(&wf[q], ww);
-        if (same) {
-            atomicAdd(&cb[q], 1u);
-            if (WEIGHTED) atomicAdd(&wb[q], ww);
-        }
-    }
-    // every thread of the workgroup: the accumulated entries to region k's rows, and the histograms zero again
-    __device__ __forceinline__ void flush(const JkOut &o, int k) const {
-        __syncthreads();
-        const size_t row = (size_t)k * o.stride;
-        for (int q = threadIdx.x; q < nh; q += PB)
-            if (cf[q]) {
-                atomicAdd(&o.nfirst[row + q], (unsigned long long)cf[q]);
-                if (WEIGHTED) atomicAdd(&o.wfirst[row + q], wf[q]), wf[q] = 0.0;
-                cf[q] = 0u;
-                if (cb[q]) {
-                    atomicAdd(&o.nboth[row + q], (unsigned long long)cb[q]);
-                    if (WEIGHTED) atomicAdd(&o.wboth[row + q], wb[q]), wb[q] = 0.0;
-                    cb[q] = 0u;
-                }
-            }
-        __syncthreads();
-    }
-};
-
-// MODE 0: a lane's pairs of the last bin for the run's label (a lane's share stays far below 2^32 between two flushes)
-template <bool WEIGHTED>
-struct JkTop {
-    unsigned long long nf = 0, nb = 0;
-    double wf = 0.0, wb = 0.0;
-    __device__ __forceinline__ void add(bool same, double ww) {
-        nf++, wf += ww;
-        if (same) nb++, wb += ww;
-    }
-    __device__ __forceinline__ void fold(const JkHist<WEIGHTED> &h, int q) {
-        if (!nf) return;
-        atomicAdd(&h.cf[q], (unsigned int)nf);
-        if (WEIGHTED) atomicAdd(&h.wf[q], wf);
-        if (nb) {
-            atomicAdd(&h.cb[q], (unsigned int)nb);
-            if (WEIGHTED) atomicAdd(&h.wb[q], wb);
-        }
-        nf = nb = 0, wf = wb = 0.0;
-    }
-};
-
-// il[0 .. cap): the labels of the points a slice could take, ascending (the sort's order inside a cell): the length of the
-// run of il[0].  Every thread searches the same way (broadcast reads)
-__device__ __forceinline__ int jk_run_length(const int *il, int cap) {
-    const int L = il[0];
-    int lo = 1, hi = cap;   // the first index in [1, cap] whose label is not L
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (il[mid] != L) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// The cells of this workgroup: a CONTIGUOUS range holding its share of the points of set 1 - workgroup b takes the cells whose
-// first point lies in [n b / G, n (b + 1) / G) (an equal share of the cells leaves most workgroups of a light cone, whose
-// bounding box is mostly empty, without work).  Every thread searches the same way
-__device__ __forceinline__ void jk_cell_range(const int64_t *__restrict__ start, int ncell, int &c_lo, int &c_hi) {
-    const int64_t n = start[ncell];
-    auto first_cell_from = [&](int64_t target) {   // the first cell whose first point is not before `target`
-        int lo = 0, hi = ncell;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (start[mid] < target) lo = mid + 1;
-            else hi = mid;
-        }
-        return lo;
-    };
-    c_lo = first_cell_from(n * (int64_t)blockIdx.x / (int64_t)gridDim.x);
-    c_hi = blockIdx.x + 1 == gridDim.x ? ncell : first_cell_from(n * (int64_t)(blockIdx.x + 1) / (int64_t)gridDim.x);
-}
-
-// the walk of pair_count_w (no separation sums) with the two histograms of the current label
-template <int MODE>
-__global__ __launch_bounds__(PB) void pair_count_jk(PairArgs a, WeightArgs wa, const int *__restrict__ lab1, const int *__restrict__ lab2,
-                                                    JkOut out, int ncell, unsigned long long *__restrict__ evaluated) {
-    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
-    __shared__ int il[PB];
-    __shared__ float e2[64];
-    __shared__ int64_t nb_j0[27];
-    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
-    extern __shared__ __align__(8) double jk_lds[];   // nh sums first | nh sums both | nh counts first | nh counts both
-    const int tid = threadIdx.x;
-    const int nh = a.nbins * a.nsub;
-    const JkHist<true> h(jk_lds, nh);
-    h.clear();
-    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
-    __syncthreads();
-    const float lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
-    const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
-    const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
-    JkTop<true> top;
-    unsigned long long n_eval = 0;
-    unsigned int nflush = 0;
-    int cur = -1;                            // the label the histograms hold (none yet)
-    int c_lo, c_hi;
-    jk_cell_range(a.start1, ncell, c_lo, c_hi);
-    for (int c1 = c_lo; c1 < c_hi; c1++) {
-        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
-        if (cbeg == cend) continue;
-        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
-        if (tid < 64) {
-            int len = 0;
-            int64_t j0 = 0;
-            if (tid < nnb) {
-                const int cz = c1 % a.g.ncz, cy = (c1 / a.g.ncz) % a.g.ncy, cx = c1 / (a.g.ncz * a.g.ncy);
-                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
-                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
-                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
-                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
-                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
-                j0 = a.start2[c2];
-                len = (int)(a.start2[c2 + 1] - j0);
-            }
-            int incl = len;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const int v = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += v;
-            }
-            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
-            if (tid == nnb - 1) nb_pre[nnb] = incl;
-        }
-        __syncthreads();
-        const int M = nb_pre[nnb];
-        for (int64_t i0 = cbeg; i0 < cend;) {
-            const int cap = (int)min((int64_t)PB, cend - i0);
-            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
-            if (tid < cap) {                  // the points behind the run's end are loaded again by the next slice
-                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
-                iw[tid] = wa.w1 ? wa.w1[i0 + tid] : 1.0f;
-                il[tid] = lab1[i0 + tid];
-            }
-            __syncthreads();
-            const int L = il[0], ni = jk_run_length(il, cap);
-            if (L != cur) {                   // uniform: another region from here on
-                if (cur >= 0) {
-                    if (MODE == 0) top.fold(h, a.nbins - 1);
-                    h.flush(out, cur);
-                    nflush++;
-                }
-                cur = L;
-            }
-            for (int base = 0; base < M; base += PB) {
-                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
-                const int v = base + tid;
-                if (v >= M) continue;
-                int sg = 0;
-                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[nnb]: ends at a non-empty cell
-                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
-                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
-                const double wj = wa.w2 ? (double)wa.w2[jj] : 1.0;
-                const bool same = lab2[jj] == L;
-                for (int i = 0; i < ni; i++) {
-                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
-                    const float dx = min_image(ix[i] - xj, a.half, a.g.box);
-                    const float dy = min_image(iy[i] - yj, a.half, a.g.box);
-                    const float dz = min_image(iz[i] - zj, a.half, a.g.box);
-                    float r2;
-                    int sub = 0;
-                    if (MODE == 1) {
-                        const float adz = fabsf(dz);
-                        if (adz >= a.pimax) continue;
-                        r2 = dx * dx + dy * dy;
-                        if (r2 < lo2 || r2 >= hi2) continue;
-                        sub = (int)(adz / a.dpi);
-                        if (sub >= a.nsub) continue;
-                    } else {
-                        r2 = dx * dx + dy * dy + dz * dz;
-                        if (r2 < lo2 || r2 >= hi2) continue;
-                    }
-                    if (MODE == 2) {
-                        const float sep = sqrtf(r2);
-                        const float mu = sep > 0.f ? fabsf(dz) / sep : 0.f;
-                        if (mu >= a.mu_max) continue;
-                        sub = (int)(mu * a.inv_dmu);
-                        if (sub >= a.nsub) continue;
-                    }
-                    const double ww = (double)iw[i] * wj;
-                    if (MODE == 0 && r2 >= top2) {
-                        top.add(same, ww);
-                        continue;
-                    }
-                    int b = a.nbins - 1;
-                    while (r2 < e2[b]) b--;
-                    h.add(b * a.nsub + sub, same, ww);
-                }
-            }
-            i0 += ni;
-        }
-    }
-    if (cur >= 0) {
-        if (MODE == 0) top.fold(h, a.nbins - 1);
-        h.flush(out, cur);
-        nflush++;
-    }
-    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
-    if (tid == 0 && nflush) atomicAdd(out.flushes, (unsigned long long)nflush);
-}
-
-// the walk of pair_count_los (no separation sums) with the two histograms of the current label
-template <int MODE, bool WEIGHTED>
-__global__ __launch_bounds__(PB) void pair_count_los_jk(LosArgs a, const int *__restrict__ lab1, const int *__restrict__ lab2, JkOut out,
-                                                        int ncell, unsigned long long *__restrict__ evaluated) {
-    __shared__ float ix[PB], iy[PB], iz[PB], iw[PB];
-    __shared__ int il[PB];
-    __shared__ double e2[64];
-    __shared__ int64_t nb_j0[27];
-    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
-    extern __shared__ __align__(8) double jk_lds[];   // [nh sums first | nh sums both] nh counts first | nh counts both
-    const int tid = threadIdx.x;
-    const int nh = a.nbins * a.nsub;
-    const JkHist<WEIGHTED> h(jk_lds, nh);
-    h.clear();
-    if (tid <= a.nbins) e2[tid] = a.edges2[tid];
-    __syncthreads();
-    const double lo2 = e2[0], hi2 = e2[a.nbins], top2 = e2[a.nbins - 1];
-    const int ncx = a.nc[0], ncy = a.nc[1], ncz = a.nc[2];
-    JkTop<WEIGHTED> top;
-    unsigned long long n_eval = 0;
-    unsigned int nflush = 0;
-    int cur = -1;                            // the label the histograms hold (none yet)
-    int c_lo, c_hi;
-    jk_cell_range(a.start1, ncell, c_lo, c_hi);
-    for (int c1 = c_lo; c1 < c_hi; c1++) {
-        const int64_t cbeg = a.start1[c1], cend = a.start1[c1 + 1];
-        if (cbeg == cend) continue;
-        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
-        if (tid < 64) {
-            int len = 0;
-            int64_t j0 = 0;
-            if (tid < 27) {
-                const int cz = c1 % ncz, cy = (c1 / ncz) % ncy, cx = c1 / (ncz * ncy);
-                const int nx = cx + tid / 9 - 1, ny = cy + (tid / 3) % 3 - 1, nz = cz + tid % 3 - 1;
-                if (nx >= 0 && nx < ncx && ny >= 0 && ny < ncy && nz >= 0 && nz < ncz) {   // open grid: nothing wraps
-                    const int c2 = (nx * ncy + ny) * ncz + nz;
-                    j0 = a.start2[c2];
-                    len = (int)(a.start2[c2 + 1] - j0);
-                }
-            }
-            int incl = len;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const int v = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += v;
-            }
-            if (tid < 27) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
-            if (tid == 26) nb_pre[27] = incl;
-        }
-        __syncthreads();
-        const int M = nb_pre[27];
-        for (int64_t i0 = cbeg; i0 < cend;) {
-            const int cap = (int)min((int64_t)PB, cend - i0);
-            if (i0 > cbeg) __syncthreads();   // the previous slice's reads are done
-            if (tid < cap) {                  // the points behind the run's end are loaded again by the next slice
-                ix[tid] = a.x1[i0 + tid], iy[tid] = a.y1[i0 + tid], iz[tid] = a.z1[i0 + tid];
-                iw[tid] = WEIGHTED && a.w1 ? a.w1[i0 + tid] : 1.0f;
-                il[tid] = lab1[i0 + tid];
-            }
-            __syncthreads();
-            const int L = il[0], ni = jk_run_length(il, cap);
-            if (L != cur) {                   // uniform: another region from here on
-                if (cur >= 0) {
-                    if (MODE == 0) top.fold(h, a.nbins - 1);
-                    h.flush(out, cur);
-                    nflush++;
-                }
-                cur = L;
-            }
-            for (int base = 0; base < M; base += PB) {
-                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
-                const int v = base + tid;
-                if (v >= M) continue;
-                int sg = 0;
-                while (nb_pre[sg + 1] <= v) sg++;        // v < nb_pre[27]: ends at a non-empty cell
-                const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
-                const float xj = a.x2[jj], yj = a.y2[jj], zj = a.z2[jj];
-                const double wj = WEIGHTED && a.w2 ? (double)a.w2[jj] : 1.0;
-                const bool same = lab2[jj] == L;
-                for (int i = 0; i < ni; i++) {
-                    const float dxf = ix[i] - xj, dyf = iy[i] - yj, dzf = iz[i] - zj;
-                    const float s2f = dxf * dxf + dyf * dyf + dzf * dzf;
-                    if (s2f > a.pre_hi || s2f < a.pre_lo) continue;
-                    if (a.autocorr && jj == i0 + i) continue;   // the same point (the two sorted sets are one array)
-                    const double dx = (double)dxf, dy = (double)dyf, dz = (double)dzf;
-                    const double s2 = dx * dx + dy * dy + dz * dz;
-                    double q = s2, pi2 = 0.0;
-                    int sub = 0;
-                    if (MODE == 0) {
-                        if (!(q >= lo2 && q < hi2)) continue;
-                    } else {
-                        if (MODE == 2 && !(q >= lo2 && q < hi2)) continue;
-                        const double lx = (double)(ix[i] + xj), ly = (double)(iy[i] + yj), lz = (double)(iz[i] + zj);
-                        const double l2 = lx * lx + ly * ly + lz * lz;
-                        if (l2 == 0.0) continue;                // no line of sight
-                        const double t = dx * lx + dy * ly + dz * lz;
-                        pi2 = t * t / l2;
-                        if (MODE == 1) {
-                            const double pi = sqrt(pi2);
-                            if (!(pi < a.pimax)) continue;
-                            const double rp2 = s2 - pi2;
-                            q = rp2 > 0.0 ? rp2 : 0.0;
-                            if (!(q >= lo2 && q < hi2)) continue;
-                            sub = (int)(pi / a.dpi);
-                        } else {
-                            const double mu = s2 > 0.0 ? sqrt(pi2 / s2) : 0.0;
-                            if (!(mu < a.mu_max)) continue;
-                            sub = (int)(mu * a.inv_dmu);
-                        }
-                        if (sub >= a.nsub) continue;
-                    }
-                    const double ww = WEIGHTED ? (double)iw[i] * wj : 0.0;
-                    if (MODE == 0 && q >= top2) {
-                        top.add(same, ww);
-                        continue;
-                    }
-                    int b = a.nbins - 1;
-                    while (q < e2[b]) b--;
-                    h.add(b * a.nsub + sub, same, ww);
-                }
-            }
-            i0 += ni;
-        }
-    }
-    if (cur >= 0) {
-        if (MODE == 0) top.fold(h, a.nbins - 1);
-        h.flush(out, cur);
-        nflush++;
-    }
-    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
-    if (tid == 0 && nflush) atomicAdd(out.flushes, (unsigned long long)nflush);
-}
-
-// smallest and largest label of a set: range[0] = min, range[1] = max (the host refuses a call whose labels leave [0, nreg)
-// before anything is sorted or counted)
-__global__ void jk_label_range(const int *__restrict__ labels, int64_t n, int *__restrict__ range) {
-    int mn = 0x7fffffff, mx = (int)0x80000000;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int l = labels[i];
-        mn = min(mn, l), mx = max(mx, l);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off, 64)), mx = max(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0 && mn <= mx) atomicMin(&range[0], mn), atomicMax(&range[1], mx);
-}
-
-// the sort key of a point: its cell above its label (the label masked to its bits: it was range-checked before)
-template <typename K, typename Grid>
-__global__ void jk_cell_keys(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                             const int *__restrict__ labels, int64_t n, Grid g, int lab_bits, K *__restrict__ keys,
-                             unsigned int *__restrict__ idx) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {x[i], y[i], z[i]};
-        keys[i] = ((K)g.cell(v) << lab_bits) | (K)((unsigned int)labels[i] & ((1u << lab_bits) - 1u));
-        idx[i] = (unsigned int)i;
-    }
-}
-// behind the sort: points, weights and labels in (cell, label, input) order
-__global__ void jk_gather(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
-                          const float *__restrict__ w, const int *__restrict__ labels, int64_t n, const unsigned int *__restrict__ idx,
-                          float *__restrict__ sx, float *__restrict__ sy, float *__restrict__ sz, float *__restrict__ sw,
-                          int *__restrict__ sl) {
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned int i = idx[s];
-        sx[s] = x[i], sy[s] = y[i], sz[s] = z[i], sl[s] = labels[i];
-        if (w) sw[s] = w[i];
-    }
-}
-template <typename K>
-__global__ void jk_cell_starts(const K *__restrict__ keys, int64_t n, int64_t ncell, int lab_bits, int64_t *__restrict__ start) {
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= ncell; c += (int64_t)gridDim.x * blockDim.x) {
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)(keys[mid] >> lab_bits) < c) lo = mid + 1;
-            else hi = mid;
-        }
-        start[c] = lo;
-    }
-}
-
-// labels of an nx x ny x nz split of the periodic box, from the float32 coordinate the counter sees, wrapped like the cell grid
-template <typename T>
-__global__ void jk_box_labels(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z, int64_t n, float inv_box,
-                              int nx, int ny, int nz, int *__restrict__ labels) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int cx = max(cell_coord((float)x[i], nx, inv_box), 0), cy = max(cell_coord((float)y[i], ny, inv_box), 0),
-                  cz = max(cell_coord((float)z[i], nz, inv_box), 0);
-        labels[i] = (cx * ny + cy) * nz + cz;
-    }
-}
-
-struct JkWork {
-    DevBuf labs[2], keys[2], sorted_labels[2], range;
-    int *sl[2];
-} g_jk;
-
-int bits_for(int64_t n) {   // bits that hold 0 .. n - 1
-    int b = 1;
-    while (((int64_t)1 << b) < n) b++;
-    return b;
-}
-
-template <typename K, typename Grid>
-int jk_sort_keys(const Columns &c, const int *labels, int64_t n, const Grid &g, int64_t ncell, int lab_bits, int end_bit, SortedSet &s,
-                 DevBuf &keybuf, int nblk) {
-    ABACUS_TRY(keybuf.reserve(2 * (size_t)n * sizeof(K)));
-    K *keys = keybuf.as<K>(), *keys2 = keys + n;
-    ABACUS_LAUNCH("pair_jk_keys", (jk_cell_keys<K, Grid>), dim3(nblk), dim3(256), 0, c.x[0], c.x[1], c.x[2], labels, n, g, lab_bits, keys,
-                  s.idx.as<unsigned int>());
-    size_t tmp_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, s.idx.as<unsigned int>(), s.idx2.as<unsigned int>(), (int)n, 0,
-                                             end_bit, stream());
-    ABACUS_TRY(s.tmp.reserve(tmp_bytes));
-    prof_begin("pair_jk_sort");
-    const hipError_t sorted = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tmp_bytes, keys, keys2, s.idx.as<unsigned int>(),
-                                                                 s.idx2.as<unsigned int>(), (int)n, 0, end_bit, stream());
-    prof_end("pair_jk_sort");
-    if (sorted != hipSuccess) return fail("abacus_paircount_jk: radix sort failed");
-    const int cblk = (int)std::min<int64_t>(ceil_div(ncell + 1, 256), 8192);
-    ABACUS_LAUNCH("pair_jk_starts", jk_cell_starts<K>, dim3(cblk), dim3(256), 0, keys2, n, ncell, lab_bits, s.start.as<int64_t>());
-    return 0;
-}
-
-// The set in (cell, label) order on either grid: s.sx | sy | sz, s.start, s.sw with weights, and g_jk.sl[k].  One stable radix
-// sort for every size (the counting sort of sort_into_cells leaves the order inside a cell to the run); n > 0
-template <typename Grid>
-int sort_into_cells_jk(const Columns &c, const int *labels, int64_t n, const Grid &g, int64_t ncell, int nreg, int k) {
-    SortedSet &s = g_work.S[k];
-    const size_t n1 = (size_t)n;
-    s.n = n;
-    ABACUS_TRY(s.sorted.reserve(3 * n1 * 4));
-    ABACUS_TRY(s.start.reserve((size_t)(ncell + 1) * 8));
-    ABACUS_TRY(s.idx.reserve(n1 * 4));
-    ABACUS_TRY(s.idx2.reserve(n1 * 4));
-    ABACUS_TRY(g_jk.sorted_labels[k].reserve(n1 * 4));
-    s.sx = s.sorted.as<float>(), s.sy = s.sx + n1, s.sz = s.sy + n1, s.sw = nullptr;
-    if (c.w) {
-        ABACUS_TRY(s.wsorted.reserve(n1 * 4));
-        s.sw = s.wsorted.as<float>();
-    }
-    g_jk.sl[k] = g_jk.sorted_labels[k].as<int>();
-    const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 2048);
-    const int lab_bits = bits_for(nreg), end_bit = lab_bits + bits_for(ncell);
-    if (end_bit <= 32) ABACUS_TRY((jk_sort_keys<unsigned int, Grid>(c, labels, n, g, ncell, lab_bits, end_bit, s, g_jk.keys[k], nblk)));
-    else ABACUS_TRY((jk_sort_keys<unsigned long long, Grid>(c, labels, n, g, ncell, lab_bits, end_bit, s, g_jk.keys[k], nblk)));
-    ABACUS_LAUNCH("pair_jk_fill", jk_gather, dim3(nblk), dim3(256), 0, c.x[0], c.x[1], c.x[2], c.w, labels, n, s.idx2.as<unsigned int>(), s.sx,
-                  s.sy, s.sz, s.sw, g_jk.sl[k]);
-    return 0;
-}
-
-struct JkHostOut {
-    uint64_t *nfirst, *nboth;
-    double *wfirst, *wboth;
-};
-
-// what both drivers check before the device is touched
-int jk_check(const char *who, int nreg, int nbins, int nsub, int autocorr, const void *labels1, const void *labels2, int64_t n1, int64_t n2,
-             const JkHostOut &o, bool need_sums) {
-    if (nreg < 1 || nreg > JK_MAX_REG) return fail("%s: nreg = %d must lie in [1, %d]", who, nreg, JK_MAX_REG);
-    if (nsub > JK_MAX_HIST) return fail("%s: %d pi / mu bins exceed the LDS histogram", who, nsub);
-    if ((int64_t)nreg * nbins * nsub > JK_MAX_OUT) return fail("%s: nreg * nbins * sub-bins = %lld exceeds 2^24 output entries", who, (long long)nreg * nbins * nsub);
-    if (!o.nfirst || !o.nboth) return fail("%s: npairs_first / npairs_both is NULL", who);
-    if ((o.wfirst == nullptr) != (o.wboth == nullptr)) return fail("%s: wsum_first and wsum_both go together", who);
-    if (need_sums && !o.wfirst) return fail("%s: wsum_first / wsum_both is NULL", who);
-    if (autocorr && labels2) return fail("%s: labels2 given for an autocorrelation (x2 is NULL)", who);
-    if (n1 > 0 && !labels1) return fail("%s: labels1 is NULL", who);
-    if (!autocorr && n2 > 0 && !labels2) return fail("%s: labels2 is NULL", who);
-    return 0;
-}
-
-// labels in HBM (host labels are uploaded) and range-checked by a device reduction: nothing is sorted or counted with a label
-// outside [0, nreg)
-int jk_stage_labels(const char *who, const int32_t *const src[2], const int64_t ns[2], int nsets, int where, int nreg, const int *dl[2]) {
-    ABACUS_TRY(g_jk.range.reserve(8));
-    const int init[2] = {0x7fffffff, (int)0x80000000};
-    HIP_TRY(hipMemcpyAsync(g_jk.range.p, init, 8, hipMemcpyHostToDevice, stream()));
-    for (int k = 0; k < nsets; k++) {
-        dl[k] = src[k];
-        if (where == 0) {
-            ABACUS_TRY(g_jk.labs[k].reserve((size_t)ns[k] * 4));
-            HIP_TRY(hipMemcpyAsync(g_jk.labs[k].p, src[k], (size_t)ns[k] * 4, hipMemcpyHostToDevice, stream()));
-            dl[k] = g_jk.labs[k].as<int>();
-        }
-        ABACUS_LAUNCH("pair_jk_label_range", jk_label_range, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 1024)), dim3(256), 0,
-                      dl[k], ns[k], g_jk.range.as<int>());
-    }
-    int range[2];
-    HIP_TRY(hipMemcpyAsync(range, g_jk.range.p, 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
-    if (range[0] < 0 || range[1] >= nreg) return fail("%s: labels span [%d, %d], outside [0, %d)", who, range[0], range[1], nreg);
-    return 0;
-}
-
-// the four output arrays in g_work.out, zeroed: [nreg][ntot] each
-int jk_device_outputs(int nreg, size_t ntot, bool sums, JkOut &d, unsigned long long *flushes) {
-    const size_t cnt = (size_t)nreg * ntot, bytes = (sums ? 4 : 2) * cnt * 8;
-    ABACUS_TRY(g_work.out.reserve(bytes));
-    HIP_TRY(hipMemsetAsync(g_work.out.p, 0, bytes, stream()));
-    d.nfirst = g_work.out.as<unsigned long long>(), d.nboth = d.nfirst + cnt;
-    d.wfirst = sums ? reinterpret_cast<double *>(d.nboth + cnt) : nullptr, d.wboth = sums ? d.wfirst + cnt : nullptr;
-    d.stride = ntot, d.flushes = flushes;
-    return 0;
-}
-JkOut jk_at(const JkOut &d, size_t o) {
-    JkOut r = d;
-    r.nfirst += o, r.nboth += o;
-    if (r.wfirst) r.wfirst += o, r.wboth += o;
-    return r;
-}
-int jk_fetch(const JkHostOut &h, const JkOut &d, size_t cnt) {
-    HIP_TRY(hipMemcpyAsync(h.nfirst, d.nfirst, cnt * 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipMemcpyAsync(h.nboth, d.nboth, cnt * 8, hipMemcpyDeviceToHost, stream()));
-    if (h.wfirst) {
-        HIP_TRY(hipMemcpyAsync(h.wfirst, d.wfirst, cnt * 8, hipMemcpyDeviceToHost, stream()));
-        HIP_TRY(hipMemcpyAsync(h.wboth, d.wboth, cnt * 8, hipMemcpyDeviceToHost, stream()));
-    }
-    return 0;
-}
-void jk_zero(const JkHostOut &h, size_t cnt) {
-    memset(h.nfirst, 0, cnt * 8), memset(h.nboth, 0, cnt * 8);
-    if (h.wfirst) memset(h.wfirst, 0, cnt * 8), memset(h.wboth, 0, cnt * 8);
-}
-
-// The jackknife launches of a run, like those of the plain walks above; out: the run's columns of the [nreg][ntot] block.
-// They take fewer workgroups on request (pairs_jk_grid, tests: many cells per workgroup) and report how many they took.
-void cap_jk_grid(dim3 &grid) {
-    if (option("pairs_jk_grid") > 0) grid.x = std::min<unsigned int>(grid.x, (unsigned int)option("pairs_jk_grid"));
-}
-
-template int sort_into_cells_jk<CellGrid>(const Columns &, const int *, int64_t, const CellGrid &, int64_t, int, int);
-
-int launch_jk(const PairArgs &a, const WeightArgs &wa, const int *lab1, const int *lab2, const JkOut &out, const Flags &fl, int64_t ncell,
-              int &workgroups) {
-    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 24;   // <= JK_MAX_HIST * 24 = 48 KiB beside 6 KiB of static LDS
-    return with_mode(a.mode, [&](auto M) -> int {
-        const auto kernel = pair_count_jk<decltype(M)::value>;
-        dim3 grid;
-        ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-        cap_jk_grid(grid);
-        ABACUS_LAUNCH("pair_count_jk", kernel, grid, dim3(PB), hist_bytes, a, wa, lab1, lab2, out, (int)ncell, fl.evaluated);
-        workgroups = (int)grid.x;
-        return 0;
-    });
-}
-
-template int sort_into_cells_jk<OpenGrid>(const Columns &, const int *, int64_t, const OpenGrid &, int64_t, int, int);
-
-int launch_los_jk(int mode, const LosArgs &a, bool weighted, const int *lab1, const int *lab2, const JkOut &out, const Flags &fl,
-                  int64_t ncell, int &workgroups) {
-    const size_t hist_bytes = (size_t)a.nbins * a.nsub * (weighted ? 24 : 8);
-    return with_mode(mode, [&](auto M) {
-        return with_flag(weighted, [&](auto WT) -> int {
-            const auto kernel = pair_count_los_jk<decltype(M)::value, decltype(WT)::value>;
-            dim3 grid;
-            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-            cap_jk_grid(grid);
-            ABACUS_LAUNCH("pair_count_los_jk", kernel, grid, dim3(PB), hist_bytes, a, lab1, lab2, out, (int)ncell, fl.evaluated);
-            workgroups = (int)grid.x;
-            return 0;
-        });
-    });
-}
-
-// ------------------------------------------------------------------------------------------------ counts in spheres ----
-// Neighbour counts around query points (abacus_spherecount[_dev]): for every query the number of data points inside each of nr
-// radii - the primitive under the void probability function, the kNN-CDFs and counts-in-cells.  No reference code and no
-// Corrfunc run stands behind it; the NumPy statement tests/spheres_statement.py is the judge, and its column sums are the
-// cumulative counts of the pair counter.
-//   per (query, data) pair, float32, the expressions of pair_count_w: d = q - p per component through min_image, r2 = dx dx +
-//   dy dy + dz dz left to right (cylinders: r2 = dx dx + dy dy, and the pair needs |dz| < pimax); the point is inside radius j
-//   iff r2 < e2[j], e2[j] = r_j r_j as a float32 product - strict, so N(<r_j) is the cumulative sum of the [lo, hi) bins over
-//   (0, r_1 .. r_nr).  Queries that ARE the data (qx == NULL) do not count themselves, by identity: a coincident twin counts.
-//   out: hist[j][k] = queries with exactly k points inside r_j (k < kmax), hist[j][kmax] = those with kmax or more; and, when
-//   asked for, counts[query][j] in the caller's query order.
-// Mapping: the walk of pair_count_w with another reduction.  A persistent workgroup takes a query cell; the 27 (or fewer)
-// neighbour cells are ONE virtual list of which every lane holds one data point in registers; the queries of the cell are an
-// LDS slice read by broadcast (one 16-byte read: x, y, z and the caller's index).  Membership is reduced over the WAVE, not per
-// pair: the ballot of r2 < e2[j] is the wave's contribution to N(<r_j), already cumulative, so the radii are walked from the
-// largest down and the walk ends at the first empty ballot (logarithmic radii: the sphere's volume halves per step, a round of
-// 64 candidates is empty after some five).  Lane j keeps the population count of radius j, and lanes 0 .. nr - 1
-// add the round's row to cnt[query][0 .. nr) in LDS with one conflict-free instruction.  No atomics per pair, and a workgroup is
-// busy when a cell holds a handful of queries and hundreds of candidates - 10^6 random centres in 10^7 galaxies, the usual
-// regime.  (The transposed mapping - a lane per query, data tiles broadcast from LDS, private counters - needs no ballots and
-// wins when the queries are as dense as the data; it is not built: with a few queries per cell it leaves most lanes idle.)
-// After the walk of a slice hist[j][min(cnt, kmax)] is bumped in an LDS histogram (flushed once per workgroup, 64-bit global
-// atomics) and the row goes to counts[caller's index].  That index rides through both sort paths in the weight lane of the
-// existing sort kernels, as the bit pattern of a float32 that only moves touch.
-struct SphereArgs {
-    CellGrid g;
-    int nr, kmax, autocorr;
-    float half, pimax;
-    const float *e2;               // nr squared radii
-    const float *qx, *qy, *qz;     // the queries in cell order ...
-    const unsigned int *qid;       // ... and their indices in the caller's order (NULL: counts not asked for)
-    const float *px, *py, *pz;     // the data in cell order (the queries' arrays when the queries are the data)
-    const int64_t *qstart, *pstart;
-    unsigned long long *hist;      // [nr][kmax + 1]
-    unsigned int *counts;          // [nq][nr], or NULL
-    unsigned int nq;               // rows of counts
-};
-
-// (a template, like sphere_count: the code object lists such kernels where they are first asked for - behind the kernels that were
-// here before, which come out of the compiler as they did; only the two jk_box_labels kernels of the file's last entry follow,
-// with their local labels renumbered: profiles/spheres/README.md)
-template <typename T>
-__global__ void sphere_iota(T *__restrict__ idx, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) idx[i] = (T)i;
-}
-
-template <bool CYL>
-__global__ __launch_bounds__(PB) void sphere_count(SphereArgs a, int ncell, unsigned long long *__restrict__ evaluated) {
-    __shared__ float4 qp[PB];                // the slice: x, y, z, the caller's index as a bit pattern
-    __shared__ int64_t nb_j0[27];
-    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations
-    extern __shared__ unsigned int sph_lds[];   // nr (kmax + 1) histogram entries | PB rows of nr counts
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int nr = a.nr, kw = a.kmax + 1, nh = nr * kw;
-    unsigned int *hist = sph_lds, *cnt = sph_lds + nh;
-    for (int q = tid; q < nh + PB * nr; q += PB) sph_lds[q] = 0u;
-    const float e2l = lane < nr ? a.e2[lane] : 0.f;   // lane j holds e2[j]: read back as a scalar (v_readlane), no memory in the loop
-    const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
-    const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
-    unsigned long long n_eval = 0;
-    for (int c1 = blockIdx.x; c1 < ncell; c1 += gridDim.x) {
-        const int64_t cbeg = a.qstart[c1], cend = a.qstart[c1 + 1];
-        if (cbeg == cend) continue;
-        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done, its count rows are zero again
-        if (tid < 64) {
-            int len = 0;
-            int64_t j0 = 0;
-            if (tid < nnb) {
-                const int cz = c1 % a.g.ncz, cy = (c1 / a.g.ncz) % a.g.ncy, cx = c1 / (a.g.ncz * a.g.ncy);
-                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
-                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
-                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
-                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
-                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
-                j0 = a.pstart[c2];
-                len = (int)(a.pstart[c2 + 1] - j0);
-            }
-            int incl = len;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const int v = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += v;
-            }
-            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
-            if (tid == nnb - 1) nb_pre[nnb] = incl;
-        }
-        __syncthreads();
-        const int M = nb_pre[nnb];
-        for (int64_t i0 = cbeg; i0 < cend; i0 += PB) {
-            const int ni = (int)min((int64_t)PB, cend - i0);
-            if (i0 > cbeg) __syncthreads();   // the previous slice's rows are read and zero again
-            if (tid < ni) qp[tid] = make_float4(a.qx[i0 + tid], a.qy[i0 + tid], a.qz[i0 + tid], a.qid ? __uint_as_float(a.qid[i0 + tid]) : 0.f);
-            __syncthreads();
-            for (int base = 0; base < M; base += PB) {
-                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
-                if (base + (tid & ~63) >= M) continue;   // per wave: no candidate left for it in this round
-                // every lane of the wave stays in the loop below (the ballots are over the whole wave); one without a point never matches
-                const int v = base + tid;
-                const bool have = v < M;
-                float xj = 0.f, yj = 0.f, zj = 0.f;
-                int self = -1;                           // the slice index of this very point (the two sorted sets are one array)
-                if (have) {
-                    int sg = 0;
-                    while (nb_pre[sg + 1] <= v) sg++;    // v < nb_pre[nnb]: ends at a non-empty cell
-                    const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
-                    xj = a.px[jj], yj = a.py[jj], zj = a.pz[jj];
-                    if (a.autocorr && jj >= i0 && jj < i0 + ni) self = (int)(jj - i0);
-                }
-                for (int i = 0; i < ni; i++) {
-                    const float4 q = qp[i];
-                    // min_image, branch-free: its single addition of -+L, or of 0 (which leaves d, and -0 as +0: the same square)
-                    float dx = q.x - xj, dy = q.y - yj, dz = q.z - zj;
-                    dx += dx > a.half ? -a.g.box : (dx < -a.half ? a.g.box : 0.f);
-                    dy += dy > a.half ? -a.g.box : (dy < -a.half ? a.g.box : 0.f);
-                    dz += dz > a.half ? -a.g.box : (dz < -a.half ? a.g.box : 0.f);
-                    bool in = have && i != self;
-                    float r2;
-                    if (CYL) {
-                        r2 = dx * dx + dy * dy;
-                        in = in && fabsf(dz) < a.pimax;
-                    } else {
-                        r2 = dx * dx + dy * dy + dz * dz;
-                    }
-                    if (!in) r2 = __builtin_huge_valf();    // below no radius
-                    int mine = 0;                        // lane j: the wave's points inside radius j of query i
-                    for (int j = nr - 1; j >= 0; j--) {
-                        const float ej = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2l), j));
-                        const unsigned long long m = __builtin_amdgcn_ballot_w64(r2 < ej);
-                        if (!m) break;                   // none inside r_j: none inside a smaller radius
-                        mine = lane == j ? __popcll(m) : mine;
-                    }
-                    if (mine) atomicAdd(&cnt[i * nr + lane], (unsigned int)mine);
-                }
-            }
-            __syncthreads();
-            // the slice's rows: into the histogram, to the caller's row, and zero again
-            for (int p = tid; p < ni * nr; p += PB) {
-                const int i = p / nr, j = p - i * nr;
-                const unsigned int c = cnt[p];
-                cnt[p] = 0u;
-                atomicAdd(&hist[j * kw + (int)min(c, (unsigned int)a.kmax)], 1u);
-                const unsigned int row = __float_as_uint(qp[i].w);
-                if (a.counts && row < a.nq) a.counts[(size_t)row * nr + j] = c;   // (row < nq always: the guard keeps a store inside the array whatever a sort did)
-            }
-        }
-    }
-    if (tid == 0 && n_eval) atomicAdd(evaluated, n_eval);
-    __syncthreads();
-    for (int q = tid; q < nh; q += PB)
-        if (hist[q]) atomicAdd(&a.hist[q], (unsigned long long)hist[q]);
-}
-
-int launch_spheres(const SphereArgs &a, bool cyl, const Flags &fl, int64_t ncell) {
-    const size_t lds = ((size_t)a.nr * (a.kmax + 1) + (size_t)PB * a.nr) * sizeof(unsigned int);   // <= 32 + 32 KiB beside 4.4 KiB static
-    return with_flag(cyl, [&](auto CYL) -> int {
-        const auto kernel = sphere_count<decltype(CYL)::value>;
-        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        dim3 grid;
-        ABACUS_TRY(resident_grid(kernel, PB, lds, ncell, grid));
-        ABACUS_LAUNCH("sphere_count", kernel, grid, dim3(PB), lds, a, (int)ncell, fl.evaluated);
-        return 0;
-    });
-}
-
 // ------------------------------------------------------------------------------------------------ the drivers ----
 // A call as an entry point hands it on.  count_box (periodic) and count_los (open grid) serve the twelve entries; with a
 // JkSpec they are the jackknife counters, without one the plain ones.  Inside a run they part only for the sort (labels ride
 // along or not), the launch, and the device outputs (a block per run, or one [nreg][ntot] block of which a run takes columns).
-struct PointSet {
-    const void *x[3];
-    const float *w;   // NULL: unit weights
-    int64_t n;
-    const void *v[3];   // velocity columns of a velocity call (PairCall::vel), in the dtype of x
-};
 struct Binning {
     int mode;
     const float *bins;
@@ -2541,7 +1301,6 @@ struct PairCall {
     int autocorr() const { return set[1].x[0] == nullptr; }
     bool empty() const { return set[0].n == 0 || (!autocorr() && set[1].n == 0); }
 };
-int where_of(int pos_dtype) { return pos_dtype == ABACUS_F32 ? 1 : (pos_dtype == ABACUS_F64 ? 2 : -1); }
 
 // Validation, before the device is touched.  check_box and check_los hold the rules of their family; both start with
 // check_sets_and_bins and end the output rules with check_outputs.
@@ -2597,30 +1356,6 @@ int check_los(const PairCall &c, const double *origin) {
     return 0;
 }
 
-// Bookkeeping of the last call (abacus_paircount_stats, abacus_paircount_los_grid, abacus_paircount_jk_stats): zero when a call
-// starts, so what an empty or a refused-on-the-device call leaves is zero in all of them
-struct Stats {
-    unsigned long long evaluated = 0, flushes = 0;   // candidate pairs (not of the first two generations); jackknife flushes
-    int cells[3] = {0, 0, 0};                        // cells in xy, in z, stencil half-width R (0: not pair_count3)
-    int los_cells[3] = {0, 0, 0};
-    int workgroups = 0;
-} g_stats;
-
-// A run's candidate count and, behind it in the block of flags, the flush count of the jackknife kernels (over the call so
-// far; 0 from any other kernel) come to the host with the run's synchronise; `sum`: the candidates add up over the runs (light
-// cone), else the last run's stand.  workgroups: of a jackknife launch
-int record_run(const Flags &fl, bool sum, int ncxy, int ncz, int R, const int *los_nc, int workgroups) {
-    unsigned long long ctr[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(ctr, fl.evaluated, 16, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipStreamSynchronize(stream()));
-    g_stats.evaluated = (sum ? g_stats.evaluated : 0) + ctr[0];
-    g_stats.flushes = ctr[1];
-    g_stats.cells[0] = ncxy, g_stats.cells[1] = ncz, g_stats.cells[2] = R;
-    for (int d = 0; d < 3 && los_nc; d++) g_stats.los_cells[d] = los_nc[d];
-    g_stats.workgroups = workgroups;
-    return 0;
-}
-
 // What the periodic kernels read beside the sets; the bin table and the job blocks are pair_count3's and stay off here
 void fill_box_args(PairArgs &a, const Binning &b, const CellGrid &g) {
     a.mode = b.mode;
@@ -2634,44 +1369,6 @@ void fill_box_args(PairArgs &a, const Binning &b, const CellGrid &g) {
     a.edges2 = g_work.edges.as<float>();
     a.lut_sh = a.lut_off = a.lut_ncell = 0;
     a.no_blocks = 0;
-}
-
-// The periodic grid of a run and its stencil half-width R.  Jackknife and weighted counts walk the 27 cells of the full reach.
-// The unweighted kernels take cells of size >= reach / R: R = 2 (125-cell stencil of cells an eighth the volume: 1.7x fewer
-// candidate pairs) when the catalogue is dense enough to keep a wave busy with a small cell, else R = 1
-int periodic_grid(float boxsize, float reach_xy, float reach_z, bool full_reach, int gen, double nmax, CellGrid &g) {
-    auto ncells = [&](float reach, int R, int cap) {
-        int nc = (int)floorf(boxsize / reach * (float)R * 0.9999f);   // cell size strictly >= reach / R
-        nc = std::min(nc, cap);
-        return nc < 3 ? 1 : nc;
-    };
-    int R = 1;
-    if (!full_reach && gen >= 3) {
-        const double per_cell = nmax * ((double)reach_xy / boxsize) * ((double)reach_xy / boxsize) * ((double)reach_z / boxsize);
-        if (per_cell > 12.0 && ncells(reach_xy, 2, 192) >= 5 && ncells(reach_z, 2, 192) >= 5) R = 2;
-    }
-    g.box = boxsize;
-    g.inv_box = 1.0f / boxsize;
-    g.ncx = g.ncy = ncells(reach_xy, R, R == 2 ? 192 : 128);
-    g.ncz = ncells(reach_z, R, R == 2 ? 192 : 128);
-    // the cap may leave cells larger than reach / R: still correct (a cell >= reach / R is all the stencil needs)
-    return R;
-}
-
-// pair_vel stands behind every instantiation above, so the kernels before it keep their order in the code object
-int launch_vel(const PairArgs &a, const WeightArgs &wa, const VelArgs &va, const Flags &fl, int64_t ncell) {
-    const size_t hist_bytes = (size_t)a.nbins * a.nsub * 52;   // <= V_MAX_HIST * 52 = 52 KiB beside 7.6 KiB of static LDS
-    return with_mode(a.mode, [&](auto M) {
-        return with_flag(a.mode != 0 || !option("pairvel_lds_top"), [&](auto TOP) -> int {   // modes 1, 2 have no such path: one instance
-            const auto kernel = pair_vel<decltype(M)::value, decltype(TOP)::value>;
-            if (hist_bytes > 48 * 1024)
-                HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-            dim3 grid;
-            ABACUS_TRY(resident_grid(kernel, PB, hist_bytes, ncell, grid));
-            ABACUS_LAUNCH("pair_vel", kernel, grid, dim3(PB), hist_bytes, a, wa, va, (int)ncell, fl.evaluated);
-            return 0;
-        });
-    });
 }
 
 // The periodic driver.  weighted: the entry takes weights and returns wsum (and rsum unless NULL), by pair_count_w - or, for a
@@ -2761,8 +1458,7 @@ int los_frame(const PairCall &c, bool weighted, const double *origin, const Flag
     for (int k = 0; k < (c.autocorr() ? 1 : 2); k++) {
         const PointSet &s = c.set[k];
         ABACUS_TRY(stage_columns("pair_los_centre", s.x, weighted ? s.w : nullptr, c.where, s.n, origin, W.cols[k], W.wts[k], f.cols[k]));
-        ABACUS_LAUNCH("pair_los_bbox", bbox_minmax, dim3((unsigned int)std::min<int64_t>(ceil_div(s.n, 256), 1024)), dim3(256), 0,
-                      f.cols[k].x[0], f.cols[k].x[1], f.cols[k].x[2], s.n, fl.frame);
+        ABACUS_TRY(bounding_box(f.cols[k], s.n, fl.frame));
     }
     Frame fr;
     HIP_TRY(hipMemcpyAsync(&fr, fl.frame, sizeof fr, hipMemcpyDeviceToHost, stream()));
@@ -2858,523 +1554,6 @@ int count_los(const PairCall &c, const double *origin) {
         ABACUS_TRY(jk_fetch(jk->out, jdev, (size_t)jk->nreg * ntot_all));
         HIP_TRY(hipStreamSynchronize(stream()));
     }
-    return 0;
-}
-
-// The sphere driver (abacus_spherecount[_dev]).  Set 0 of the work buffers holds the queries - the data themselves when
-// q[0] == NULL - and set 1 the data, both in one periodic grid of the full reach.
-constexpr int SPH_MAX_RADII = 32;
-struct SphereCall {
-    const char *who;
-    const void *p[3];    // the data
-    int64_t n;
-    const void *q[3];    // the queries; q[0] == NULL: the data are the queries (a point does not count itself)
-    int64_t nq;
-    int where;           // as PairCall::where
-    float boxsize;
-    const float *radii;
-    int nr;
-    float pimax;         // 0: spheres; > 0: cylinders along z, |dz| < pimax
-    int kmax;
-    uint64_t *hist;      // [nr][kmax + 1]
-    uint32_t *counts;    // [nq][nr] in the caller's order, or NULL
-    bool self() const { return q[0] == nullptr; }
-};
-struct SphereWork {
-    DevBuf counts;
-} g_sph;
-
-int check_spheres(const SphereCall &c) {
-    const char *who = c.who;
-    if (c.where < 0) return fail("%s: pos_dtype must be ABACUS_F32 or ABACUS_F64", who);
-    if (!c.p[0] || !c.p[1] || !c.p[2] || !c.radii || !c.hist) return fail("%s: null argument", who);
-    if (!c.self() && (!c.q[1] || !c.q[2])) return fail("%s: null argument (qy / qz)", who);
-    if (c.nr < 1 || c.nr > SPH_MAX_RADII) return fail("%s: nr = %d must lie in [1, %d]", who, c.nr, SPH_MAX_RADII);
-    if (c.kmax < 1) return fail("%s: kmax must be at least 1", who);
-    const long long nh = (long long)c.nr * ((long long)c.kmax + 1);
-    if (nh > MAX_HIST) return fail("%s: nr * (kmax + 1) = %lld exceeds the LDS histogram of %d entries", who, nh, MAX_HIST);
-    if (!(c.boxsize > 0)) return fail("%s: boxsize must be positive", who);
-    if (!(c.radii[0] > 0.f)) return fail("%s: radii must be positive", who);
-    for (int j = 1; j < c.nr; j++)
-        if (!(c.radii[j] > c.radii[j - 1])) return fail("%s: radii must increase", who);
-    if (!(c.pimax >= 0.f)) return fail("%s: pimax must be positive (0: spheres)", who);
-    if (c.radii[c.nr - 1] > 0.5f * c.boxsize || c.pimax > 0.5f * c.boxsize)
-        return fail("%s: the largest radius or pimax exceeds half the box (minimum image not unique)", who);
-    if (c.n < 0 || c.n >= ((int64_t)1 << 31) || (!c.self() && (c.nq < 0 || c.nq >= ((int64_t)1 << 31))))
-        return fail("%s: point counts must lie in [0, 2^31)", who);
-    return 0;
-}
-
-int count_spheres(const SphereCall &c) {
-    ABACUS_TRY(check_spheres(c));
-    ABACUS_ENTER();
-    const int self = c.self() ? 1 : 0, nsets = self ? 1 : 2, nr = c.nr, kw = c.kmax + 1;
-    const int64_t nq = self ? c.n : c.nq;
-    const size_t nh = (size_t)nr * kw;
-    memset(c.hist, 0, nh * sizeof(uint64_t));
-    if (c.counts) memset(c.counts, 0, (size_t)nq * nr * sizeof(uint32_t));
-    g_stats = Stats{};
-    if (nq == 0) return 0;
-    if (c.n == 0) {   // nothing to count: every query has no neighbour
-        for (int j = 0; j < nr; j++) c.hist[(size_t)j * kw] = (uint64_t)nq;
-        return 0;
-    }
-    Work &W = g_work;
-    const bool cyl = c.pimax > 0.f;
-    const int64_t ns[2] = {nq, c.n};
-    Flags fl;
-    ABACUS_TRY(W.flags(fl));
-    Columns cols[2];
-    ABACUS_TRY(stage_columns("pair_cast", self ? c.p : c.q, nullptr, c.where, ns[0], nullptr, W.cols[0], W.wts[0], cols[0]));
-    if (!self) ABACUS_TRY(stage_columns("pair_cast", c.p, nullptr, c.where, ns[1], nullptr, W.cols[1], W.wts[1], cols[1]));
-    if (c.counts) {   // the caller's index of a query: the "weight" of set 0, a bit pattern the sort only moves
-        ABACUS_TRY(W.wts[0].reserve((size_t)nq * 4));
-        ABACUS_LAUNCH("sphere_iota", sphere_iota<unsigned int>, dim3((unsigned int)std::min<int64_t>(ceil_div(nq, 256), 2048)), dim3(256), 0,
-                      W.wts[0].as<unsigned int>(), nq);
-        cols[0].w = W.wts[0].as<float>();
-    }
-    const float reach = c.radii[nr - 1];
-    CellGrid g;
-    periodic_grid(c.boxsize, reach, cyl ? c.pimax : reach, true, 3, (double)std::max(ns[0], ns[1]), g);
-    const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-    for (int k = 0; k < nsets; k++) ABACUS_TRY(sort_into_cells(cols[k], ns[k], FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[k], W.scratch));
-    std::vector<float> e2;
-    ABACUS_TRY(upload_edges(c.radii, nr - 1, e2));   // nr squared radii, float32 products
-    ABACUS_TRY(W.out.reserve(nh * 8));
-    HIP_TRY(hipMemsetAsync(W.out.p, 0, nh * 8, stream()));
-    if (c.counts) ABACUS_TRY(g_sph.counts.reserve((size_t)nq * nr * 4));   // every row is written: each query belongs to one slice
-    const SortedSet &Q = W.S[0], &P = W.S[self ? 0 : 1];
-    SphereArgs a;
-    a.g = g, a.nr = nr, a.kmax = c.kmax, a.autocorr = self;
-    a.half = g.box * 0.5f, a.pimax = c.pimax;
-    a.e2 = W.edges.as<float>();
-    a.qx = Q.sx, a.qy = Q.sy, a.qz = Q.sz, a.qid = c.counts ? reinterpret_cast<const unsigned int *>(Q.sw) : nullptr;
-    a.px = P.sx, a.py = P.sy, a.pz = P.sz;
-    a.qstart = Q.start.as<int64_t>(), a.pstart = P.start.as<int64_t>();
-    a.hist = W.out.as<unsigned long long>();
-    a.counts = c.counts ? g_sph.counts.as<unsigned int>() : nullptr;
-    a.nq = (unsigned int)nq;
-    ABACUS_TRY(launch_spheres(a, cyl, fl, ncell));
-    HIP_TRY(hipMemcpyAsync(c.hist, W.out.p, nh * 8, hipMemcpyDeviceToHost, stream()));
-    if (c.counts) HIP_TRY(hipMemcpyAsync(c.counts, g_sph.counts.p, (size_t)nq * nr * 4, hipMemcpyDeviceToHost, stream()));
-    return record_run(fl, false, g.ncx, g.ncz, 0, nullptr, 0);
-}
-
-// ------------------------------------------------------------------------------- three-point function multipoles ----
-// zeta_l(r1, r2) of one catalogue on the periodic box by the multipole algorithm of Slepian & Eisenstein (2015)
-// (abacus_threepcf[_dev]): per primary i the real spherical-harmonic sums a[bin][component] = sum_j w_j y_c(u_ij) over its
-// neighbours, then the Gram matrix per l, which by the addition theorem is sum_{j,k} w_j w_k P_l(u_ij . u_ik); the j = k term
-// (P_l(1) = 1: sum_j w_j^2) leaves the diagonal.  O(N k) instead of the O(N k^2) triplet count.  No reference code stands behind
-// it; the NumPy statement tests/threepcf_statement.py is the judge (its `harmonic` form restates the components below).
-//   pairs: the float32 expressions, the bins and the grid of pair_count_w mode 0 - npairs is bit-equal to that counter's.
-//   components: (cm, sm) = w_j (Re, Im) (ux + i uy)^m and R_l^m(uz) by R_m^m = D_m, R_l^m = A_lm uz R_{l-1}^m - B_lm R_{l-2}^m
-//   (the host's table `coef`: D | A | B); component l^2 is R_l^0 cm, l^2 + 2m - 1 and l^2 + 2m are R_l^m cm and R_l^m sm.
-// Mapping: the walk of sphere_count - a persistent workgroup per primary cell, the neighbour cells as one virtual list, a lane
-// per candidate - but ONE primary at a time, shared by the workgroup: its table a[nbins][ncomp] (15.5 KiB at 32 bins and
-// lmax = 10) lives once in LDS.  Only ~15 % of the candidates of a 27-cell walk are counted, so a counted pair is not expanded
-// where it is found: its direction, weight and bin go into an LDS queue (a ballot per wave, one LDS atomic on the fill count by
-// its leader), and whenever the queue holds a workgroup's worth - and after the primary's last round - a pass takes 256 entries:
-// a counting sort by bin in place (which also yields the pass's npairs), then an entry per lane: the recurrence in registers
-// (two values per m, the loop bounds are uniform), and every component summed per bin inside each row of 16 lanes by four DPP
-// steps before the first lane of a bin in its row adds it to the table - an LDS float atomic that at most four lanes of a wave
-// share.  (Measured, 10^6 points, 10 bins, lmax 10: an LDS atomic per pair and component - 64 lanes on ten addresses - 228 ms;
-// a whole-wave sum per bin of the wave 214 ms; the row-wise segmented sum 53 ms: profiles/threepcf/README.md.)  The order of the
-// float32 atomics, and with it the last bits of zeta and wself, depends on the run.
-// Gram step, once per primary with a counted pair: lane t owns the triples (l, b1 <= b2) t, t + PB, ...; the 2l + 1 products in
-// float64 (exact products of float32), times w_i, into the lane's own float64 accumulators in LDS, which stay there across the
-// primaries of all the workgroup's cells and leave once, by float64 global atomics.
-struct TpcfArgs {
-    CellGrid g;
-    int nbins, lmax, npair, ntrip;   // npair = nbins (nbins + 1) / 2, ntrip = (lmax + 1) npair
-    const float *e2;                 // nbins + 1 squared edges
-    const float *coef;               // D[lmax + 1] | A[(lmax + 1)^2] | B[(lmax + 1)^2], A and B indexed l (lmax + 1) + m
-    const float *x, *w;              // the catalogue in cell order: x | y | z, each `stride` floats apart; w NULL: unit weights
-    int stride;
-    const int64_t *start;
-    double *out;                     // zeta [lmax + 1][npair] (the upper triangle, b1 <= b2, row by row) | wself [nbins] | npairs [nbins] |
-                                     // candidate pairs evaluated [1] (the last two uint64)
-};
-
-constexpr int TPCF_QCAP = 2 * PB;    // a round adds at most PB entries to fewer than PB left over
-
-// lane i's copy of lane i + D's value inside its row of 16 lanes (DPP row_shl); `edge` where the row ends before that
-template <int D>
-__device__ __forceinline__ int tpcf_row_next(int v, int edge) {
-    return __builtin_amdgcn_update_dpp(edge, v, 0x100 + D, 0xF, 0xF, false);
-}
-template <int D>
-__device__ __forceinline__ float tpcf_row_next(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + D, 0xF, 0xF, true));
-}
-
-// a value for every element of a column (the weights of a set without weights beside one with)
-template <typename T>
-__global__ void threepcf_fill(T *__restrict__ dst, T v, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = v;
-}
-
-template <bool WEIGHTED>
-__global__ __launch_bounds__(PB) void threepcf_walk(TpcfArgs a, int ncell) {
-    __shared__ float4 qd[TPCF_QCAP];         // the queue: direction and w_j ...
-    __shared__ int qb[TPCF_QCAP];            // ... and bin
-    __shared__ int qn;                       // entries in the queue
-    __shared__ int ncand;                    // candidates of the cell: the neighbour cells' populations together
-    __shared__ int bcnt[32];                 // a pass: its entries per bin (zero between passes)
-    __shared__ float e2[33];
-    __shared__ int64_t nb_j0[27];
-    __shared__ int nb_pre[28];
-    extern __shared__ __align__(8) double tp_lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int nb = a.nbins, L1 = a.lmax + 1, nc = L1 * L1, ncoef = L1 + 2 * nc;
-    // dynamic LDS: acc[ntrip] | wacc[nb] | hc[nb] (64-bit) | tab[nb][nc] | s2[nb] | coef[ncoef] (32-bit) | pr[npair] (16-bit)
-    double *acc = tp_lds, *wacc = acc + a.ntrip;
-    unsigned long long *hc = reinterpret_cast<unsigned long long *>(wacc + nb);
-    float *tab = reinterpret_cast<float *>(hc + nb), *s2 = tab + nb * nc, *coef = s2 + nb;
-    unsigned short *pr = reinterpret_cast<unsigned short *>(coef + ncoef);
-    for (int q = tid; q < a.ntrip; q += PB) acc[q] = 0.0;
-    for (int q = tid; q < nb; q += PB) wacc[q] = 0.0, hc[q] = 0ull;
-    for (int q = tid; q < nb * nc + nb; q += PB) tab[q] = 0.f;   // the table and s2
-    for (int q = tid; q < ncoef; q += PB) coef[q] = a.coef[q];
-    for (int q = tid; q < a.npair; q += PB) {   // the q-th pair b1 <= b2, row by row
-        int b1 = 0, left = q;
-        while (left >= nb - b1) left -= nb - b1, b1++;
-        pr[q] = (unsigned short)(b1 | ((b1 + left) << 8));
-    }
-    if (tid <= nb) e2[tid] = a.e2[tid];
-    if (tid == 0) qn = 0;
-    if (tid < 32) bcnt[tid] = 0;
-    __syncthreads();
-    const float *cD = coef, *cA = coef + L1, *cB = cA + nc;
-    const float lo2 = e2[0], hi2 = e2[nb], half = a.g.box * 0.5f;
-    unsigned long long n_eval = 0;
-
-    // The first `cnt` entries of the queue, in bin order, one per lane: their components into the table.  The entries of a bin are
-    // consecutive lanes, so a component is summed per bin inside every row of 16 lanes by a segmented suffix sum - four DPP steps
-    // on the vector units, lane i taking lane i + d's partial sum where that lane holds the same bin - and the first lane of a
-    // bin in its row adds the sum to the table: at most four lanes of a wave meet on one address, whatever the bins' populations.
-    auto expand = [&](int cnt) {
-        if ((tid & ~63) >= cnt) return;                  // per wave: no entry for it
-        const bool live = tid < cnt;
-        const float4 u = live ? qd[tid] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const int b = live ? qb[tid] : -1;               // (lanes without an entry: a bin of their own, sums of zeros, never added)
-        // 1 where lane i + d holds the same bin, else 0: factors in vector registers (as lane masks they would cost eight scalars)
-        const float t1 = tpcf_row_next<1>(b, -2) == b ? 1.f : 0.f, t2 = tpcf_row_next<2>(b, -2) == b ? 1.f : 0.f,
-                    t4 = tpcf_row_next<4>(b, -2) == b ? 1.f : 0.f, t8 = tpcf_row_next<8>(b, -2) == b ? 1.f : 0.f;
-        const bool head = live && __builtin_amdgcn_update_dpp(-2, b, 0x111, 0xF, 0xF, false) != b;   // row_shr:1: the lane before
-        float *row = tab + (live ? b : 0) * nc;
-        auto add = [&](float *dst, float v) {
-            // (every lane runs the DPP move, then takes the value or not: inside the conditional only the taking lanes would be
-            // active, and a DPP read of an inactive lane returns nothing)
-            const float n1 = tpcf_row_next<1>(v);
-            v += t1 * n1;
-            const float n2 = tpcf_row_next<2>(v);
-            v += t2 * n2;
-            const float n4 = tpcf_row_next<4>(v);
-            v += t4 * n4;
-            const float n8 = tpcf_row_next<8>(v);
-            v += t8 * n8;
-            if (head) atomicAdd(dst, v);
-        };
-        add(&s2[live ? b : 0], u.w * u.w);
-        float cm = u.w, sm = 0.f;
-        for (int m = 0; m < L1; m++) {
-            if (m) {
-                const float c = cm * u.x - sm * u.y;
-                sm = sm * u.x + cm * u.y;
-                cm = c;
-            }
-            float p2 = 0.f, p1 = 0.f;
-            for (int l = m; l < L1; l++) {
-                const float r = l == m ? cD[m] : cA[l * L1 + m] * u.z * p1 - cB[l * L1 + m] * p2;
-                p2 = p1, p1 = r;
-                if (m == 0) {
-                    add(row + l * l, r * cm);
-                } else {
-                    add(row + l * l + 2 * m - 1, r * cm);
-                    add(row + l * l + 2 * m, r * sm);
-                }
-            }
-        }
-    };
-    // A pass over the first cnt <= PB entries: a counting sort by bin in place (an entry waits in its lane's registers), the
-    // pass's pairs per bin into npairs on the way, then the expansion.  Every lane of the workgroup calls.
-    auto pass = [&](int cnt) {
-        const bool live = tid < cnt;
-        float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-        int b = 0, pos = 0;
-        if (live) u = qd[tid], b = qb[tid], pos = atomicAdd(&bcnt[b], 1);
-        __syncthreads();
-        if (live)
-            for (int k = 0; k < b; k++) pos += bcnt[k];
-        if (tid < nb) hc[tid] += (unsigned long long)bcnt[tid];
-        __syncthreads();
-        if (live) qd[pos] = u, qb[pos] = b;
-        if (tid < nb) bcnt[tid] = 0;
-        __syncthreads();
-        expand(cnt);
-    };
-
-    for (int c1 = blockIdx.x; c1 < ncell; c1 += gridDim.x) {
-        const int64_t cbeg = a.start[c1], cend = a.start[c1 + 1];
-        if (cbeg == cend) continue;
-        __syncthreads();   // the previous cell's reads of the neighbour table are done
-        if (tid < 64) {
-            const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
-            const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
-            int len = 0;
-            int64_t j0 = 0;
-            if (tid < nnb) {
-                // (divisions by a vector-register copy of the grid that the compiler cannot see through: as scalars their
-                // reciprocals would be formed once and held in six scalar registers across the whole kernel)
-                int gz = a.g.ncz, gy = a.g.ncy;
-                asm volatile("" : "+v"(gz), "+v"(gy));
-                const int cz = c1 % gz, cy = (c1 / gz) % gy, cx = c1 / (gz * gy);
-                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
-                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
-                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
-                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
-                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
-                j0 = a.start[c2];
-                len = (int)(a.start[c2 + 1] - j0);
-            }
-            int incl = len;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const int v = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += v;
-            }
-            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
-            if (tid == nnb - 1) nb_pre[nnb] = incl, ncand = incl;
-        }
-        __syncthreads();
-        const int M = ncand;
-        for (int64_t i = cbeg; i < cend; i++) {
-            // (the queue is empty, the table and s2 are zero, and a barrier stands behind all of that)
-            const float xi = a.x[i], yi = a.x[i + a.stride], zi = a.x[i + 2 * (int64_t)a.stride];
-            bool any = false;                            // the primary has a counted pair with a direction (uniform)
-            for (int base = 0; base < M; base += PB) {
-                n_eval += (unsigned long long)min(PB, M - base);
-                const int v = base + tid;
-                float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-                int eb = -1;                               // the bin of a counted pair with a direction
-                if (v < M) {
-                    int sg = 0;
-                    while (nb_pre[sg + 1] <= v) sg++;    // v < nb_pre[nnb]: ends at a non-empty cell
-                    const int64_t jj = nb_j0[sg] + (v - nb_pre[sg]);
-                    if (jj != i) {                        // not the primary itself, by identity
-                        const float dx = min_image(xi - a.x[jj], half, a.g.box);
-                        const float dy = min_image(yi - a.x[jj + a.stride], half, a.g.box);
-                        const float dz = min_image(zi - a.x[jj + 2 * (int64_t)a.stride], half, a.g.box);
-                        const float r2 = dx * dx + dy * dy + dz * dz;
-                        if (!(r2 < lo2 || r2 >= hi2)) {
-                            int b = nb - 1;
-                            while (r2 < e2[b]) b--;
-                            if (r2 > 0.f) {
-                                const float r = sqrtf(r2);
-                                e = make_float4(dx / r, dy / r, dz / r, WEIGHTED ? a.w[jj] : 1.f), eb = b;
-                            } else {
-                                atomicAdd(&hc[b], 1ull);  // a coincident twin (or a NaN): a pair of its bin without a direction
-                            }
-                        }
-                    }
-                }
-                // into the queue: one atomic per wave (the ballot's leader), the lanes take consecutive slots behind it
-                {
-                    const unsigned long long mask = __builtin_amdgcn_ballot_w64(eb >= 0);
-                    if (mask) {
-                        const int leader = __ffsll((long long)mask) - 1;
-                        int slot = 0;
-                        if (lane == leader) slot = atomicAdd(&qn, __popcll(mask));
-                        slot = __builtin_amdgcn_readlane(slot, leader) + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
-                        if (eb >= 0) qd[slot] = e, qb[slot] = eb;   // slot < TPCF_QCAP: fewer than PB were left, a round adds at most PB
-                    }
-                }
-                __syncthreads();
-                const int n = qn;
-                __syncthreads();                           // every lane has read the count before the next round adds to it
-                const bool last = base + PB >= M;
-                if (n >= PB || (last && n > 0)) {
-                    any = true;
-                    pass(min(n, PB));
-                    __syncthreads();                       // the first PB entries are read: the rest moves to the front
-                    float4 td = make_float4(0.f, 0.f, 0.f, 0.f);
-                    int tb = 0;
-                    const int rest = n > PB ? n - PB : 0;
-                    if (tid < rest) td = qd[PB + tid], tb = qb[PB + tid];
-                    if (tid < rest) qd[tid] = td, qb[tid] = tb;   // PB + tid and tid: different entries, no lane reads what another writes
-                    if (tid == 0) qn = rest;
-                    __syncthreads();
-                    if (last && rest > 0) {                // (n < 2 PB: one more pass empties the queue)
-                        pass(rest);
-                        __syncthreads();
-                        if (tid == 0) qn = 0;
-                    }
-                }
-            }
-            if (!any) continue;
-            __syncthreads();   // every component of this primary is in the table, and the queue is empty again
-            const double wi = WEIGHTED ? (double)a.w[i] : 1.0;
-            for (int t = tid; t < a.ntrip; t += PB) {
-                const int l = t / a.npair, p = t - l * a.npair;
-                const int b1 = pr[p] & 0xff, b2 = pr[p] >> 8;
-                const float *r1 = tab + b1 * nc, *r2 = tab + b2 * nc;
-                double g = 0.0;
-                for (int c = l * l; c < (l + 1) * (l + 1); c++) g += (double)r1[c] * (double)r2[c];
-                if (b1 == b2) g -= (double)s2[b1];
-                acc[t] += wi * g;
-            }
-            if (tid < nb) wacc[tid] += wi * (double)s2[tid];
-            __syncthreads();
-            for (int q = tid; q < nb * nc + nb; q += PB) tab[q] = 0.f;
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    if (tid == 0 && n_eval) atomicAdd(reinterpret_cast<unsigned long long *>(a.out + a.ntrip + 2 * nb), n_eval);
-    for (int t = tid; t < a.ntrip; t += PB)
-        if (acc[t] != 0.0) atomicAdd(&a.out[t], acc[t]);
-    if (tid < nb) {
-        if (wacc[tid] != 0.0) atomicAdd(&a.out[a.ntrip + tid], wacc[tid]);
-        if (hc[tid]) atomicAdd(reinterpret_cast<unsigned long long *>(a.out + a.ntrip + nb) + tid, hc[tid]);
-    }
-}
-
-// The 3PCF driver (abacus_threepcf[_dev]): set 2, when given, is appended to set 1 in HBM and the catalogue sorted into set 0 of
-// the work buffers, its weight in the weight lane.
-constexpr int TPCF_MAX_BINS = 32, TPCF_MAX_L = 10;
-struct TpcfCall {
-    const char *who;
-    PointSet set[2];     // set[1].x[0] == NULL: no second set
-    int where;           // as PairCall::where
-    float boxsize;
-    const float *bins;
-    int nbins, lmax;
-    double *zeta;        // [lmax + 1][nbins][nbins]
-    double *wself;       // [nbins]
-    uint64_t *npairs;    // [nbins]
-};
-struct TpcfWork {
-    DevBuf cat, coef;    // the appended catalogue x | y | z | w; the recurrence's coefficients
-    unsigned long long candidates = 0, counted = 0;
-    int cells = 0;
-} g_tpcf;
-
-int check_threepcf(const TpcfCall &c) {
-    const char *who = c.who;
-    const PointSet &s1 = c.set[0], &s2 = c.set[1];
-    if (c.where < 0) return fail("%s: pos_dtype must be ABACUS_F32 or ABACUS_F64", who);
-    if (!s1.x[0] || !s1.x[1] || !s1.x[2] || !c.bins || !c.zeta || !c.wself || !c.npairs) return fail("%s: null argument", who);
-    if (s2.x[0] && (!s2.x[1] || !s2.x[2])) return fail("%s: null argument (y2 / z2)", who);
-    if (!s2.x[0] && (s2.x[1] || s2.x[2])) return fail("%s: y2 / z2 given without x2", who);
-    if (!s2.x[0] && s2.w) return fail("%s: w2 given without a second set (x2 is NULL)", who);
-    if (c.nbins < 1 || c.nbins > TPCF_MAX_BINS) return fail("%s: nbins = %d must lie in [1, %d]", who, c.nbins, TPCF_MAX_BINS);
-    if (c.lmax < 0 || c.lmax > TPCF_MAX_L) return fail("%s: lmax = %d must lie in [0, %d]", who, c.lmax, TPCF_MAX_L);
-    if (!(c.boxsize > 0)) return fail("%s: boxsize must be positive", who);
-    if (!(c.bins[0] >= 0.f)) return fail("%s: bin edges must not be negative", who);
-    for (int k = 0; k < c.nbins; k++)
-        if (!(c.bins[k + 1] > c.bins[k])) return fail("%s: bin edges must increase", who);
-    if (c.bins[c.nbins] > 0.5f * c.boxsize) return fail("%s: maximum separation exceeds half the box (minimum image not unique)", who);
-    const int64_t n2 = s2.x[0] ? s2.n : 0;
-    if (s1.n < 0 || n2 < 0 || s1.n >= ((int64_t)1 << 31) || n2 >= ((int64_t)1 << 31) || s1.n + n2 >= ((int64_t)1 << 31))
-        return fail("%s: point counts must not be negative, with n + n2 < 2^31", who);
-    return 0;
-}
-
-int count_threepcf(const TpcfCall &c) {
-    ABACUS_TRY(check_threepcf(c));
-    ABACUS_ENTER();
-    const int nb = c.nbins, L1 = c.lmax + 1, nc = L1 * L1, npair = nb * (nb + 1) / 2, ntrip = L1 * npair;
-    memset(c.zeta, 0, (size_t)L1 * nb * nb * sizeof(double));
-    memset(c.wself, 0, (size_t)nb * sizeof(double));
-    memset(c.npairs, 0, (size_t)nb * sizeof(uint64_t));
-    g_stats = Stats{};
-    g_tpcf.candidates = g_tpcf.counted = 0, g_tpcf.cells = 0;
-    const int64_t n1 = c.set[0].n, n2 = c.set[1].x[0] ? c.set[1].n : 0, n = n1 + n2;
-    if (n == 0) return 0;
-    Work &W = g_work;
-    Flags fl;
-    ABACUS_TRY(W.flags(fl));
-    Columns cols[2] = {}, cat;
-    if (n1 > 0) ABACUS_TRY(stage_columns("pair_cast", c.set[0].x, c.set[0].w, c.where, n1, nullptr, W.cols[0], W.wts[0], cols[0]));
-    if (n2 > 0) ABACUS_TRY(stage_columns("pair_cast", c.set[1].x, c.set[1].w, c.where, n2, nullptr, W.cols[1], W.wts[1], cols[1]));
-    if (n2 == 0) {
-        cat = cols[0];
-    } else {   // set 2 behind set 1, column by column; a set without weights beside one with them counts with 1
-        const bool weighted = (n1 > 0 && cols[0].w) || cols[1].w;
-        ABACUS_TRY(g_tpcf.cat.reserve((size_t)n * 16));
-        float *dst = g_tpcf.cat.as<float>();
-        const int64_t ns[2] = {n1, n2}, at[2] = {0, n1};
-        for (int k = 0; k < 2; k++) {
-            if (ns[k] == 0) continue;
-            for (int d = 0; d < 3; d++)
-                HIP_TRY(hipMemcpyAsync(dst + (size_t)d * n + at[k], cols[k].x[d], (size_t)ns[k] * 4, hipMemcpyDeviceToDevice, stream()));
-            if (weighted && cols[k].w)
-                HIP_TRY(hipMemcpyAsync(dst + (size_t)3 * n + at[k], cols[k].w, (size_t)ns[k] * 4, hipMemcpyDeviceToDevice, stream()));
-            else if (weighted)
-                ABACUS_LAUNCH("threepcf_fill", threepcf_fill<float>, dim3((unsigned int)std::min<int64_t>(ceil_div(ns[k], 256), 2048)), dim3(256), 0,
-                              dst + (size_t)3 * n + at[k], 1.0f, ns[k]);
-        }
-        for (int d = 0; d < 3; d++) cat.x[d] = dst + (size_t)d * n;
-        cat.w = weighted ? dst + (size_t)3 * n : nullptr;
-    }
-    const float reach = c.bins[nb];
-    CellGrid g;
-    periodic_grid(c.boxsize, reach, reach, true, 3, (double)n, g);
-    const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-    ABACUS_TRY(sort_into_cells(cat, n, FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[0], W.scratch));
-    std::vector<float> e2;
-    ABACUS_TRY(upload_edges(c.bins, nb, e2));
-    // D | A | B of the recurrence, formed in float64 and rounded once
-    std::vector<float> coef((size_t)L1 + 2 * nc, 0.f);
-    double D = 1.0;
-    for (int m = 0; m < L1; m++) {
-        if (m) D *= std::sqrt((2.0 * m - 1.0) / (2.0 * m));
-        coef[m] = (float)(m ? std::sqrt(2.0) * D : 1.0);
-        for (int l = m + 1; l < L1; l++) {
-            const double den = (double)l * l - (double)m * m;
-            coef[L1 + l * L1 + m] = (float)((2.0 * l - 1.0) / std::sqrt(den));
-            coef[L1 + nc + l * L1 + m] = (float)std::sqrt(((l - 1.0) * (l - 1.0) - (double)m * m) / den);
-        }
-    }
-    ABACUS_TRY(g_tpcf.coef.reserve(coef.size() * 4));
-    HIP_TRY(hipMemcpyAsync(g_tpcf.coef.p, coef.data(), coef.size() * 4, hipMemcpyHostToDevice, stream()));
-    const size_t nout = (size_t)ntrip + 2 * nb + 1;   // zeta's upper triangles | wself | npairs | candidates
-    ABACUS_TRY(W.out.reserve(nout * 8));
-    HIP_TRY(hipMemsetAsync(W.out.p, 0, nout * 8, stream()));
-    const SortedSet &S = W.S[0];
-    TpcfArgs a;
-    a.g = g, a.nbins = nb, a.lmax = c.lmax, a.npair = npair, a.ntrip = ntrip;
-    a.e2 = W.edges.as<float>(), a.coef = g_tpcf.coef.as<float>();
-    a.x = S.sx, a.w = S.sw, a.stride = (int)(S.sy - S.sx);   // sort_into_cells: y and z stand behind x, max(n, 1) floats apart
-    a.start = S.start.as<int64_t>();
-    a.out = W.out.as<double>();
-    // acc | wacc | hc (8 B) | table | s2 | coef (4 B) | pairs (2 B): at most 46.4 + 0.5 + 15.5 + 0.1 + 1 + 1 KiB beside 11 KiB static
-    const size_t lds = ((size_t)ntrip + 2 * nb) * 8 + ((size_t)nb * nc + nb + coef.size()) * 4 + (((size_t)npair + 3) & ~(size_t)3) * 2;
-    ABACUS_TRY(with_flag(S.sw != nullptr, [&](auto WT) -> int {
-        const auto kernel = threepcf_walk<decltype(WT)::value>;
-        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        dim3 grid;
-        ABACUS_TRY(resident_grid(kernel, PB, lds, ncell, grid));
-        ABACUS_LAUNCH("threepcf_walk", kernel, grid, dim3(PB), lds, a, (int)ncell);
-        return 0;
-    }));
-    std::vector<double> up((size_t)ntrip);
-    HIP_TRY(hipMemcpyAsync(up.data(), a.out, (size_t)ntrip * 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipMemcpyAsync(c.wself, a.out + ntrip, (size_t)nb * 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipMemcpyAsync(c.npairs, a.out + ntrip + nb, (size_t)nb * 8, hipMemcpyDeviceToHost, stream()));
-    unsigned long long candidates = 0;
-    HIP_TRY(hipMemcpyAsync(&candidates, a.out + ntrip + 2 * nb, 8, hipMemcpyDeviceToHost, stream()));
-    ABACUS_TRY(record_run(fl, false, g.ncx, g.ncz, 0, nullptr, 0));   // synchronises
-    g_stats.evaluated = candidates;
-    // one triangle was computed: the other is its mirror, bit for bit
-    for (int l = 0; l < L1; l++) {
-        const double *src = up.data() + (size_t)l * npair;
-        double *z = c.zeta + (size_t)l * nb * nb;
-        for (int b1 = 0, p = 0; b1 < nb; b1++)
-            for (int b2 = b1; b2 < nb; b2++, p++) z[b1 * nb + b2] = z[b2 * nb + b1] = src[p];
-    }
-    g_tpcf.candidates = g_stats.evaluated, g_tpcf.cells = g.ncx;
-    for (int b = 0; b < nb; b++) g_tpcf.counted += c.npairs[b];
     return 0;
 }
 
@@ -3509,397 +1688,4 @@ extern "C" int abacus_paircount_jk_stats(uint64_t *flushes, int *workgroups) {
     if (flushes) *flushes = g_stats.flushes;
     if (workgroups) *workgroups = g_stats.workgroups;
     return 0;
-}
-
-extern "C" int abacus_spherecount(const float *x, const float *y, const float *z, int64_t n, const float *qx, const float *qy,
-                                  const float *qz, int64_t nq, float boxsize, const float *radii, int nr, float pimax, int kmax,
-                                  uint64_t *hist, uint32_t *counts) {
-    return count_spheres({"abacus_spherecount", {x, y, z}, n, {qx, qy, qz}, nq, 0, boxsize, radii, nr, pimax, kmax, hist, counts});
-}
-
-extern "C" int abacus_spherecount_dev(const void *x, const void *y, const void *z, int64_t n, const void *qx, const void *qy,
-                                      const void *qz, int64_t nq, int pos_dtype, float boxsize, const float *radii, int nr, float pimax,
-                                      int kmax, uint64_t *hist, uint32_t *counts) {
-    return count_spheres({"abacus_spherecount_dev", {x, y, z}, n, {qx, qy, qz}, nq, where_of(pos_dtype), boxsize, radii, nr, pimax, kmax,
-                          hist, counts});
-}
-
-extern "C" int abacus_spherecount_stats(uint64_t *candidates, int *ncell_xy, int *ncell_z) {
-    return abacus_paircount_stats(candidates, ncell_xy, ncell_z, nullptr);
-}
-
-extern "C" int abacus_threepcf(const float *x, const float *y, const float *z, const float *w, int64_t n, const float *x2,
-                               const float *y2, const float *z2, const float *w2, int64_t n2, float boxsize, const float *bins, int nbins,
-                               int lmax, double *zeta, double *wself, uint64_t *npairs) {
-    return count_threepcf({"abacus_threepcf", {{{x, y, z}, w, n}, {{x2, y2, z2}, w2, n2}}, 0, boxsize, bins, nbins, lmax, zeta, wself, npairs});
-}
-
-extern "C" int abacus_threepcf_dev(const void *x, const void *y, const void *z, const float *w, int64_t n, const void *x2, const void *y2,
-                                   const void *z2, const float *w2, int64_t n2, int pos_dtype, float boxsize, const float *bins, int nbins,
-                                   int lmax, double *zeta, double *wself, uint64_t *npairs) {
-    return count_threepcf({"abacus_threepcf_dev", {{{x, y, z}, w, n}, {{x2, y2, z2}, w2, n2}}, where_of(pos_dtype), boxsize, bins, nbins, lmax,
-                           zeta, wself, npairs});
-}
-
-extern "C" int abacus_threepcf_stats(uint64_t *candidates, uint64_t *counted, int *ncell) {
-    ABACUS_ENTER();
-    if (candidates) *candidates = g_tpcf.candidates;
-    if (counted) *counted = g_tpcf.counted;
-    if (ncell) *ncell = g_tpcf.cells;
-    return 0;
-}
-
-extern "C" int abacus_jk_box_labels_dev(const void *x, const void *y, const void *z, int pos_dtype, int64_t n, float boxsize, int nx, int ny,
-                                        int nz, int32_t *labels) {
-    if (pos_dtype != ABACUS_F32 && pos_dtype != ABACUS_F64) return fail("abacus_jk_box_labels_dev: pos_dtype must be ABACUS_F32 or ABACUS_F64");
-    if (n < 0 || (n > 0 && (!x || !y || !z || !labels))) return fail("abacus_jk_box_labels_dev: bad argument");
-    if (!(boxsize > 0)) return fail("abacus_jk_box_labels_dev: boxsize must be positive");
-    if (nx < 1 || ny < 1 || nz < 1 || (int64_t)nx * ny * nz > JK_MAX_REG)
-        return fail("abacus_jk_box_labels_dev: the split %d x %d x %d must have 1 .. %d regions", nx, ny, nz, JK_MAX_REG);
-    ABACUS_ENTER();
-    if (n == 0) return 0;
-    const dim3 grid((unsigned int)std::min<int64_t>(ceil_div(n, 256), 2048));
-    const float inv_box = 1.0f / boxsize;
-    if (pos_dtype == ABACUS_F64)
-        ABACUS_LAUNCH("pair_jk_box_labels", jk_box_labels<double>, grid, dim3(256), 0, (const double *)x, (const double *)y, (const double *)z, n,
-                      inv_box, nx, ny, nz, labels);
-    else
-        ABACUS_LAUNCH("pair_jk_box_labels", jk_box_labels<float>, grid, dim3(256), 0, (const float *)x, (const float *)y, (const float *)z, n,
-                      inv_box, nx, ny, nz, labels);
-    HIP_TRY(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------- friends-of-friends groups ----
-// Groups of one catalogue on the periodic box (abacus_fof[_dev]): the connected components of the friendship graph, as a label
-// per point and the multiplicity function.  No reference code stands behind it; the NumPy statement tests/groups_statement.py
-// is the judge, and its edge set is that of the counts in spheres with the single radius b_perp.
-//   friends: i != j (by identity: a coincident twin is a friend) under the float32 expressions of sphere_count, bit for bit: d
-//   = p_i - p_j per component through min_image, r2 = dx dx + dy dy + dz dz left to right and r2 < b b (b b a float32 product),
-//   strictly; cylinders (b_par > 0, the line of sight along z): r2 = dx dx + dy dy, r2 < b_perp b_perp and |dz| < b_par.
-//   out: labels[i] = the smallest caller's index among the members of i's group - a pure function of the input, whatever order
-//   the unions ran in and whichever sort path put the points into cells; mult[N] = groups of exactly N members (N < nmax),
-//   mult[nmax] = those of nmax or more; ngroups = sum of mult.
-// This section stands at the file's end - behind the last entry point - so that its kernels are listed behind every kernel that
-// was in the code object before, and those come out of the compiler as they did (the comment above sphere_iota).
-//
-// All union-find state lives in SORTED-index space: parent[s], uint32, s at first.  Four launches:
-//   fof_link     the walk of sphere_count with the set as its own queries: a persistent workgroup per cell, the neighbour cells as
-//                one virtual list, a lane per candidate, the cell's points an LDS slice read by broadcast.  A pair is taken only
-//                when jj < ii in sorted index - cells are contiguous and ascending, so the cells behind the primary leave the
-//                list and every unordered pair is taken once over the whole grid, on the one-cell-per-dimension grids too.  It
-//                is counted by ballot and population count (a scalar add per wave) and united: find both roots, hook the larger
-//                root under the smaller by atomicCAS that expects the larger to be a root still; a failed CAS returns what the
-//                root was hooked under meanwhile, and the unite carries on from there.
-//   fof_flatten  a launch later, so that every hook is visible: root[s] by a find with plain loads.
-//   fof_reduce   per point atomicMin(minid[root], caller's index) and size[root] += 1, runs of equal roots combined inside the
-//                wave first (a segmented scan: cell order makes such runs the rule, and a percolating group would otherwise put
-//                every point's atomic on one word).
-//   fof_emit     labels[caller's index] = minid[root]; every root bumps mult[min(size, nmax)] in an LDS histogram, flushed once
-//                per workgroup by 64-bit atomics.
-// Why fof_link cannot hang, and why stale reads are harmless:
-//   * every write to parent[] in fof_link is an atomic whose new value is SMALLER than the old one: a hook is atomicCAS(parent[hi],
-//     hi, lo) with lo < hi, on a root (path compression, if it ever returns, must be atomicMin for the same reason).  So
-//     parent[s] <= s always, and no cycle forms;
-//   * every find strictly descends (and returns at any value that would not: fof_find), every retry of a hook carries on from
-//     indices strictly below the one whose CAS failed;
-//   * no thread waits for another's progress: no locks, no flags, no spinning;
-//   * a plain load of parent[] may return an old value from this CU's L1 or another XCD's L2.  An old value names a point that was
-//     an ancestor and is one for ever after (trees only grow at their roots): it costs an extra step or a failed CAS, never a
-//     wrong or a lost union - a union is made by a CAS that succeeded on a true root, or was found made already by values that were
-//     true once;
-//   * the final labels are exact because of the kernel boundary before fof_flatten, not because of fences in fof_link (it has none).
-// Bound: n < 2^31 points; nmax + 1 <= MAX_HIST entries of LDS histogram; 16 bytes of union-find state per point beside the sort's.
-namespace {
-
-struct FofArgs {
-    CellGrid g;
-    float half, b2, bpar;          // box / 2; b_perp b_perp (a float32 product); b_par (cylinders)
-    const float *px, *py, *pz;     // the catalogue in cell order
-    const int64_t *start;
-    unsigned int *parent;          // [n]
-};
-
-// the root above s as this thread sees it.  p < s at every step: a value that does not descend ends the walk, so the loop is bounded
-// by s whatever the memory holds
-__device__ __forceinline__ unsigned int fof_find(const unsigned int *parent, unsigned int s) {
-    for (;;) {
-        const unsigned int p = parent[s];
-        if (p >= s) return s;
-        s = p;
-    }
-}
-
-// (no path compression here: an atomicMin(parent[s], root) on both points after their union was measured and made fof_link 0.5 to
-// 9 % slower on every workload of profiles/groups/README.md - the trees stay shallow without it, fof_flatten takes 0.02 ms at 10^7)
-__device__ __forceinline__ void fof_unite(unsigned int *parent, unsigned int a, unsigned int b) {
-    a = fof_find(parent, a), b = fof_find(parent, b);
-    while (a != b) {   // roots found equal by plain loads: united already, nothing to do
-        const unsigned int hi = max(a, b), lo = min(a, b);
-        const unsigned int old = atomicCAS(&parent[hi], hi, lo);
-        if (old >= hi) return;       // == hi: hooked (> hi cannot be)
-        a = fof_find(parent, old);   // hi was hooked under old < hi meanwhile: both indices are below hi now
-        b = lo;
-    }
-}
-
-template <bool CYL>
-__global__ __launch_bounds__(PB) void fof_link(FofArgs a, int ncell, unsigned long long *__restrict__ ctr) {
-    __shared__ float4 qp[PB];                // the slice: x, y, z
-    __shared__ int64_t nb_j0[27];
-    __shared__ int nb_pre[28];               // exclusive prefix of the neighbour cells' populations in front of the primary cell's end
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int rx = a.g.ncx >= 3 ? 1 : 0, ry = a.g.ncy >= 3 ? 1 : 0, rz = a.g.ncz >= 3 ? 1 : 0;
-    const int wy = 2 * ry + 1, wz = 2 * rz + 1, nnb = (2 * rx + 1) * wy * wz;
-    unsigned long long n_eval = 0, n_link = 0;   // n_link: per wave
-    for (int c1 = blockIdx.x; c1 < ncell; c1 += gridDim.x) {
-        const int64_t cbeg = a.start[c1], cend = a.start[c1 + 1];
-        if (cbeg == cend) continue;
-        __syncthreads();   // the previous cell's reads of the neighbour table and of the slice are done
-        if (tid < 64) {
-            int len = 0;
-            int64_t j0 = 0;
-            if (tid < nnb) {
-                const int cz = c1 % a.g.ncz, cy = (c1 / a.g.ncz) % a.g.ncy, cx = c1 / (a.g.ncz * a.g.ncy);
-                int nx = cx + tid / (wy * wz) - rx, ny = cy + (tid / wz) % wy - ry, nz = cz + tid % wz - rz;
-                nx = nx < 0 ? nx + a.g.ncx : (nx >= a.g.ncx ? nx - a.g.ncx : nx);
-                ny = ny < 0 ? ny + a.g.ncy : (ny >= a.g.ncy ? ny - a.g.ncy : ny);
-                nz = nz < 0 ? nz + a.g.ncz : (nz >= a.g.ncz ? nz - a.g.ncz : nz);
-                const int c2 = (nx * a.g.ncy + ny) * a.g.ncz + nz;
-                j0 = a.start[c2];
-                // only jj < ii is taken: a cell behind the primary holds no such point, the primary itself all of them
-                len = (int)max(min(a.start[c2 + 1], cend) - j0, (int64_t)0);
-            }
-            int incl = len;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const int v = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += v;
-            }
-            if (tid < nnb) nb_j0[tid] = j0, nb_pre[tid] = incl - len;
-            if (tid == nnb - 1) nb_pre[nnb] = incl;
-        }
-        __syncthreads();
-        const int M = nb_pre[nnb];
-        for (int64_t i0 = cbeg; i0 < cend; i0 += PB) {
-            const int ni = (int)min((int64_t)PB, cend - i0);
-            if (i0 > cbeg) __syncthreads();   // the previous slice is read
-            if (tid < ni) qp[tid] = make_float4(a.px[i0 + tid], a.py[i0 + tid], a.pz[i0 + tid], 0.f);
-            __syncthreads();
-            for (int base = 0; base < M; base += PB) {
-                n_eval += (unsigned long long)ni * (unsigned long long)min(PB, M - base);
-                if (base + (tid & ~63) >= M) continue;   // per wave: no candidate left for it in this round
-                // every lane of the wave stays in the loop below (the ballots are over the whole wave); one without a point never matches
-                const int v = base + tid;
-                const bool have = v < M;
-                float xj = 0.f, yj = 0.f, zj = 0.f;
-                int64_t jj = cend;                       // behind every ii
-                if (have) {
-                    int sg = 0;
-                    while (nb_pre[sg + 1] <= v) sg++;    // v < nb_pre[nnb]: ends at a non-empty cell
-                    jj = nb_j0[sg] + (v - nb_pre[sg]);
-                    xj = a.px[jj], yj = a.py[jj], zj = a.pz[jj];
-                }
-                for (int i = 0; i < ni; i++) {
-                    const float4 q = qp[i];
-                    // min_image, branch-free: its single addition of -+L, or of 0 (which leaves d, and -0 as +0: the same square)
-                    float dx = q.x - xj, dy = q.y - yj, dz = q.z - zj;
-                    dx += dx > a.half ? -a.g.box : (dx < -a.half ? a.g.box : 0.f);
-                    dy += dy > a.half ? -a.g.box : (dy < -a.half ? a.g.box : 0.f);
-                    dz += dz > a.half ? -a.g.box : (dz < -a.half ? a.g.box : 0.f);
-                    bool fr = jj < i0 + i;               // once per unordered pair, and never the point itself
-                    float r2;
-                    if (CYL) {
-                        r2 = dx * dx + dy * dy;
-                        fr = fr && fabsf(dz) < a.bpar;
-                    } else {
-                        r2 = dx * dx + dy * dy + dz * dz;
-                    }
-                    fr = fr && r2 < a.b2;
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(fr);
-                    if (!m) continue;
-                    n_link += (unsigned long long)__popcll(m);
-                    if (fr) fof_unite(a.parent, (unsigned int)(i0 + i), (unsigned int)jj);
-                }
-            }
-        }
-    }
-    if (tid == 0 && n_eval) atomicAdd(&ctr[0], n_eval);
-    if (lane == 0 && n_link) atomicAdd(&ctr[1], n_link);
-}
-
-template <typename T>
-__global__ void fof_flatten(const T *__restrict__ parent, T *__restrict__ root, int64_t n) {
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) root[s] = fof_find(parent, (T)s);
-}
-
-// LABELS: the smallest caller's index per root is wanted (id: the caller's index of sorted point s); sizes always.  A block takes
-// whole waves' worth of consecutive points: every lane of a wave runs every round (the shuffles are over the whole wave)
-template <bool LABELS>
-__global__ __launch_bounds__(PB) void fof_reduce(const unsigned int *__restrict__ root, const unsigned int *__restrict__ id, int64_t n,
-                                                 unsigned int *__restrict__ minid, unsigned int *__restrict__ size) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t s0 = (int64_t)blockIdx.x * PB; s0 < n; s0 += (int64_t)gridDim.x * PB) {
-        const int64_t s = s0 + threadIdx.x;
-        const bool have = s < n;
-        const unsigned int r = have ? root[s] : 0xffffffffu;
-        unsigned int mn = LABELS && have ? id[s] : 0xffffffffu;
-        const unsigned int before = __shfl_up(r, 1, 64);
-        const unsigned long long heads = __builtin_amdgcn_ballot_w64(lane == 0 || before != r);
-        const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-        const int first = 63 - __clzll((long long)(heads & upto));   // the head of this lane's run (bit 0 is set: lane 0 is a head)
-        if (LABELS) {
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned int o = __shfl_up(mn, d, 64);
-                if (lane - d >= first) mn = min(mn, o);
-            }
-        }
-        const bool last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
-        if (have && last) {   // the run's last lane holds its minimum and knows its length
-            if (LABELS) atomicMin(&minid[r], mn);
-            atomicAdd(&size[r], (unsigned int)(lane - first + 1));
-        }
-    }
-}
-
-template <bool LABELS>
-__global__ __launch_bounds__(PB) void fof_emit(const unsigned int *__restrict__ root, const unsigned int *__restrict__ id, int64_t n,
-                                               const unsigned int *__restrict__ minid, const unsigned int *__restrict__ size, int nmax,
-                                               unsigned int *__restrict__ labels, unsigned long long *__restrict__ mult) {
-    extern __shared__ unsigned int fof_hist[];   // nmax + 1 entries
-    for (int q = threadIdx.x; q <= nmax; q += PB) fof_hist[q] = 0u;
-    __syncthreads();
-    for (int64_t s = (int64_t)blockIdx.x * PB + threadIdx.x; s < n; s += (int64_t)gridDim.x * PB) {
-        const unsigned int r = root[s];
-        if (LABELS) {
-            const unsigned int row = id[s];
-            if ((int64_t)row < n) labels[row] = minid[r];   // (row < n always: the guard keeps a store inside the array whatever a sort did)
-        }
-        if ((int64_t)r == s) atomicAdd(&fof_hist[min(size[s], (unsigned int)nmax)], 1u);
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q <= nmax; q += PB)
-        if (fof_hist[q]) atomicAdd(&mult[q], (unsigned long long)fof_hist[q]);
-}
-
-struct FofCall {
-    const char *who;
-    const void *p[3];
-    int64_t n;
-    int where;           // as PairCall::where
-    float boxsize, b_perp, b_par;   // b_par 0: spheres; > 0: cylinders along z
-    int nmax;
-    uint64_t *mult;      // [nmax + 1]
-    uint32_t *labels;    // [n] in the caller's order, or NULL
-    uint64_t *ngroups;
-};
-struct FofWork {
-    DevBuf parent, root, minid, size;
-    unsigned long long links = 0;
-} g_fof;
-
-int check_fof(const FofCall &c) {
-    const char *who = c.who;
-    if (c.where < 0) return fail("%s: pos_dtype must be ABACUS_F32 or ABACUS_F64", who);
-    if (!c.p[0] || !c.p[1] || !c.p[2] || !c.mult || !c.ngroups) return fail("%s: null argument", who);
-    if (!(c.boxsize > 0)) return fail("%s: boxsize must be positive", who);
-    if (!(c.b_perp > 0.f)) return fail("%s: b_perp must be positive", who);
-    if (!(c.b_par >= 0.f)) return fail("%s: b_par must not be negative (0: spheres)", who);
-    if (c.b_perp > 0.5f * c.boxsize || c.b_par > 0.5f * c.boxsize)
-        return fail("%s: b_perp or b_par exceeds half the box (minimum image not unique)", who);
-    if (c.n < 0 || c.n >= ((int64_t)1 << 31)) return fail("%s: the point count must lie in [0, 2^31)", who);
-    if (c.nmax < 1) return fail("%s: nmax must be at least 1", who);
-    if ((long long)c.nmax + 1 > MAX_HIST) return fail("%s: nmax + 1 = %lld exceeds the LDS histogram of %d entries", who, (long long)c.nmax + 1, MAX_HIST);
-    return 0;
-}
-
-int find_groups(const FofCall &c) {
-    ABACUS_TRY(check_fof(c));
-    ABACUS_ENTER();
-    const int64_t n = c.n;
-    const size_t nh = (size_t)c.nmax + 1;
-    memset(c.mult, 0, nh * sizeof(uint64_t));
-    if (c.labels) memset(c.labels, 0, (size_t)n * sizeof(uint32_t));
-    *c.ngroups = 0;
-    g_stats = Stats{};
-    g_fof.links = 0;
-    if (n == 0) return 0;
-    Work &W = g_work;
-    const bool cyl = c.b_par > 0.f, want = c.labels != nullptr;
-    Flags fl;
-    ABACUS_TRY(W.flags(fl));
-    Columns cols;
-    ABACUS_TRY(stage_columns("pair_cast", c.p, nullptr, c.where, n, nullptr, W.cols[0], W.wts[0], cols));
-    const dim3 pts((unsigned int)std::min<int64_t>(ceil_div(n, 256), 2048));
-    if (want) {   // the caller's index of a point: the "weight" of the set, a bit pattern the sort only moves
-        ABACUS_TRY(W.wts[0].reserve((size_t)n * 4));
-        ABACUS_LAUNCH("sphere_iota", sphere_iota<unsigned int>, pts, dim3(256), 0, W.wts[0].as<unsigned int>(), n);
-        cols.w = W.wts[0].as<float>();
-    }
-    CellGrid g;
-    periodic_grid(c.boxsize, c.b_perp, cyl ? c.b_par : c.b_perp, true, 3, (double)n, g);
-    const int64_t ncell = (int64_t)g.ncx * g.ncy * g.ncz;
-    ABACUS_TRY(sort_into_cells(cols, n, FramedGrid{g, fl.outside, fl.frame}, ncell, W.S[0], W.scratch));
-    const SortedSet &S = W.S[0];
-    ABACUS_TRY(g_fof.parent.reserve((size_t)n * 4));
-    ABACUS_TRY(g_fof.root.reserve((size_t)n * 4));
-    ABACUS_TRY(g_fof.size.reserve((size_t)n * 4));
-    if (want) ABACUS_TRY(g_fof.minid.reserve((size_t)n * 4));
-    ABACUS_TRY(W.out.reserve((nh + 2) * 8));   // mult | candidates, links
-    HIP_TRY(hipMemsetAsync(W.out.p, 0, (nh + 2) * 8, stream()));
-    HIP_TRY(hipMemsetAsync(g_fof.size.p, 0, (size_t)n * 4, stream()));
-    if (want) HIP_TRY(hipMemsetAsync(g_fof.minid.p, 0xff, (size_t)n * 4, stream()));
-    unsigned int *parent = g_fof.parent.as<unsigned int>(), *root = g_fof.root.as<unsigned int>();
-    unsigned int *labels = parent;   // parent[] is read for the last time by fof_flatten
-    unsigned long long *mult = W.out.as<unsigned long long>(), *ctr = mult + nh;
-    ABACUS_LAUNCH("sphere_iota", sphere_iota<unsigned int>, pts, dim3(256), 0, parent, n);
-    FofArgs a;
-    a.g = g, a.half = g.box * 0.5f, a.b2 = c.b_perp * c.b_perp, a.bpar = c.b_par;
-    a.px = S.sx, a.py = S.sy, a.pz = S.sz;
-    a.start = S.start.as<int64_t>();
-    a.parent = parent;
-    ABACUS_TRY(with_flag(cyl, [&](auto CYL) -> int {
-        const auto kernel = fof_link<decltype(CYL)::value>;
-        dim3 grid;
-        ABACUS_TRY(resident_grid(kernel, PB, 0, ncell, grid));
-        ABACUS_LAUNCH("fof_link", kernel, grid, dim3(PB), 0, a, (int)ncell, ctr);
-        return 0;
-    }));
-    ABACUS_LAUNCH("fof_flatten", fof_flatten<unsigned int>, pts, dim3(256), 0, parent, root, n);
-    const unsigned int *id = reinterpret_cast<const unsigned int *>(S.sw);
-    ABACUS_TRY(with_flag(want, [&](auto LB) -> int {
-        constexpr bool L = decltype(LB)::value;
-        ABACUS_LAUNCH("fof_reduce", fof_reduce<L>, pts, dim3(PB), 0, root, id, n, g_fof.minid.as<unsigned int>(), g_fof.size.as<unsigned int>());
-        ABACUS_LAUNCH("fof_emit", fof_emit<L>, pts, dim3(PB), nh * sizeof(unsigned int), root, id, n, g_fof.minid.as<unsigned int>(),
-                      g_fof.size.as<unsigned int>(), c.nmax, labels, mult);
-        return 0;
-    }));
-    unsigned long long seen[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(c.mult, mult, nh * 8, hipMemcpyDeviceToHost, stream()));
-    HIP_TRY(hipMemcpyAsync(seen, ctr, 16, hipMemcpyDeviceToHost, stream()));
-    if (want) HIP_TRY(hipMemcpyAsync(c.labels, labels, (size_t)n * 4, hipMemcpyDeviceToHost, stream()));
-    ABACUS_TRY(record_run(fl, false, g.ncx, g.ncz, 0, nullptr, 0));   // synchronises
-    g_stats.evaluated = seen[0];
-    g_fof.links = seen[1];
-    for (size_t q = 0; q < nh; q++) *c.ngroups += c.mult[q];
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int abacus_fof(const float *x, const float *y, const float *z, int64_t n, float boxsize, float b_perp, float b_par, int nmax,
-                          uint64_t *mult, uint32_t *labels, uint64_t *ngroups) {
-    return find_groups({"abacus_fof", {x, y, z}, n, 0, boxsize, b_perp, b_par, nmax, mult, labels, ngroups});
-}
-
-extern "C" int abacus_fof_dev(const void *x, const void *y, const void *z, int64_t n, int pos_dtype, float boxsize, float b_perp,
-                              float b_par, int nmax, uint64_t *mult, uint32_t *labels, uint64_t *ngroups) {
-    return find_groups({"abacus_fof", {x, y, z}, n, where_of(pos_dtype), boxsize, b_perp, b_par, nmax, mult, labels, ngroups});
-}
-
-extern "C" int abacus_fof_stats(uint64_t *candidates, uint64_t *links, int *ncell_xy, int *ncell_z) {
-    ABACUS_ENTER();
-    if (links) *links = g_fof.links;
-    return abacus_paircount_stats(candidates, ncell_xy, ncell_z, nullptr);
 }

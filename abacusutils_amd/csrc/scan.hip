@@ -1,5 +1,5 @@
 // Exclusive prefix sum of 32-bit counters into 64-bit offsets, used for tile lists (tsc.hip) and cell lists
-// (pairs.hip).  Three small launches (block sums, scan of block sums, local scan + offset); the counters are
+// (cellsort.hip).  Three small launches (block sums, scan of block sums, local scan + offset); the counters are
 // optionally reset to zero for a following fill pass.  n up to 2^31.
 #include "common.hpp"
 

@@ -1,4 +1,4 @@
-"""A chunked NumPy statement of the friends-of-friends groups (include/abacus_hip.h, abacus_fof): the judge of csrc/pairs.hip's
+"""A chunked NumPy statement of the friends-of-friends groups (include/abacus_hip.h, abacus_fof): the judge of csrc/fof.hip's
 fof_link / fof_flatten / fof_reduce / fof_emit (helper of tests/test_groups_*.py, not a test module).
 
 Friendship per pair i != j, in float32 like tests/spheres_statement.py: d = p_i - p_j per component, minimum image by ONE

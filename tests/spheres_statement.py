@@ -1,5 +1,5 @@
 """A chunked NumPy statement of the counts in spheres (include/abacus_hip.h, abacus_spherecount): the judge of
-csrc/pairs.hip's sphere_count (helper of tests/test_spheres_*.py, not a test module).
+csrc/spheres.hip's sphere_count (helper of tests/test_spheres_*.py, not a test module).
 
 Per (query, data) pair, in float32 like tests/pairs_statement.py and the oracle's pair loop: d = q - p per component,
 minimum image by ONE addition of -+L when |d| > L/2, r2 = dx dx + dy dy + dz dz left to right (cylinders: r2 = dx dx + dy dy

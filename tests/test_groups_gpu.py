@@ -1,4 +1,4 @@
-"""Friends-of-friends groups on the device (csrc/pairs.hip: fof_link, fof_flatten, fof_reduce, fof_emit; C ABI
+"""Friends-of-friends groups on the device (csrc/fof.hip: fof_link, fof_flatten, fof_reduce, fof_emit; C ABI
 abacus_fof[_dev]; analysis/groups.py) against the NumPy statement tests/groups_statement.py.  Needs an MI355X: run with
 `-m gpu`.  Every comparison is between integers and exact: labels, ngroups, mult, and the links of abacus_fof_stats."""
 import functools

@@ -1,4 +1,4 @@
-"""Jackknife pair counts (csrc/pairs.hip: pair_count_jk, pair_count_los_jk; C ABI abacus_paircount_jk[_dev],
+"""Jackknife pair counts (csrc/pairs_jk.hip: pair_count_jk, pair_count_los_jk; C ABI abacus_paircount_jk[_dev],
 abacus_paircount_los_jk[_dev], abacus_jk_box_labels_dev) against tests/pairs_jk_statement.py, and the estimators of
 abacusutils_amd/analysis/jackknife.py on top.  Needs an MI355X: run with `-m gpu`.
 

@@ -1,4 +1,4 @@
-"""Counts in spheres on the device (csrc/pairs.hip: sphere_count, C ABI abacus_spherecount[_dev]; analysis/spheres.py)
+"""Counts in spheres on the device (csrc/spheres.hip: sphere_count, C ABI abacus_spherecount[_dev]; analysis/spheres.py)
 against the NumPy statement tests/spheres_statement.py.  Needs an MI355X: run with `-m gpu`.  Every comparison is between
 integers and exact."""
 import functools

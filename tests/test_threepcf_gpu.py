@@ -1,4 +1,4 @@
-"""The 3PCF multipoles on the device (csrc/pairs.hip: threepcf_walk, C ABI abacus_threepcf[_dev]; analysis/threepcf.py) against
+"""The 3PCF multipoles on the device (csrc/threepcf.hip: threepcf_walk, C ABI abacus_threepcf[_dev]; analysis/threepcf.py) against
 the NumPy statement tests/threepcf_statement.py.  Needs an MI355X: run with `-m gpu`.
 
 The bound is the project's rule (test_bispectrum_gpu.py::_check): per l, max|got - want| / max|want_l| <= 4 e_ref, where want is

@@ -1,5 +1,5 @@
 """NumPy statements of the three-point correlation function multipoles (include/abacus_hip.h, abacus_threepcf): the judge of
-csrc/pairs.hip's threepcf_walk.  Two forms:
+csrc/threepcf.hip's threepcf_walk.  Two forms:
 
   brute      per primary the k x k matrix of cosines between its neighbours, Legendre polynomials by recurrence on that matrix, the
              diagonal (j = k) zeroed: O(N k^2), float64, and independent of the algorithm;
