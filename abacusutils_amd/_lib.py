@@ -81,6 +81,15 @@ def lib():
         L.abacus_power_geometry_ms.restype = C.c_double
         L.abacus_pairvel.restype = L.abacus_pairvel_dev.restype = C.c_int    # analysis/pairwise_velocity.py
         L.abacus_fof.restype = L.abacus_fof_dev.restype = L.abacus_fof_stats.restype = C.c_int     # analysis/groups.py
+        for name in ('tophat_dev', 'create', 'level_dev', 'count', 'fetch', 'free', 'check_memory'):                # analysis/voids.py
+            getattr(L, 'abacus_void_' + name).restype = C.c_int
+        L.abacus_void_tophat_dev.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p]
+        L.abacus_void_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.abacus_void_level_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 3
+        L.abacus_void_count.argtypes = [C.c_void_p, C.c_void_p]
+        L.abacus_void_fetch.argtypes = [C.c_void_p] * 4
+        L.abacus_void_free.argtypes = [C.c_void_p]
+        L.abacus_void_check_memory.argtypes = [C.c_int, C.c_int64]
         _lib = L
     return _lib
 

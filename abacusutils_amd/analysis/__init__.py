@@ -5,3 +5,4 @@ from .minkowski import (calc_minkowski, gaussian_prediction, mesh_moments, minko
                         minkowski_functionals)
 from .spheres import count_in_spheres, knn_cdf, random_centres, vpf  # noqa: F401
 from .threepcf import calc_3pcf, triplet_multipoles, zeta_from_counts  # noqa: F401
+from .voids import find_voids, find_voids_mesh, tophat_smooth, void_galaxy_xi, void_size_function  # noqa: F401

@@ -776,6 +776,22 @@ class AbacusHOD:
                                      compensated=compensated, interlaced=interlaced, sigma_units=sigma_units)
         return out
 
+    def compute_voids(self, mock_dict, radii, threshold=-0.7, num_cells=256, paste='TSC', compensated=True, interlaced=True,
+                      return_fields=False):
+        """The spherical voids of every tracer's density contrast in the periodic box (no reference counterpart;
+        `analysis.voids.find_voids`): {tracer: its result dict}.  `radii`: at most 32 strictly decreasing radii, the largest at most
+        Lbox / 4; a cell is a candidate of a radius where the contrast smoothed with that top hat is below `threshold`.  The columns
+        are taken from HBM when `mock_dict` is the untouched result of the latest run_hod; a 'w' column weights its tracer.  No
+        voids across tracers."""
+        from ..analysis.voids import find_voids
+        out = {}
+        for tr in mock_dict.keys():
+            cols = self._xyz(mock_dict, tr)
+            pos = list(cols) if not isinstance(cols[0], np.ndarray) else np.stack([np.asarray(c) for c in cols], axis=1)
+            out[tr] = find_voids(pos, self.lbox, radii, threshold=threshold, nmesh=num_cells, w=mock_dict[tr].get('w', None), paste=paste,
+                                 compensated=compensated, interlaced=interlaced, return_fields=return_fields)
+        return out
+
     def compute_3pcf(self, mock_dict, rbins, lmax, randoms=None, seed=42):
         """The three-point correlation function multipoles zeta_l(r1, r2) of every tracer in the periodic box (no reference
         counterpart; `analysis.threepcf.calc_3pcf`): {tracer: its result dict}.  `rbins`: the edges of at most 32 radial bins, the

@@ -1189,6 +1189,57 @@ int abacus_mf_moments_dev(const float *mesh, int n, int pitch, double *out2_host
  * R >= 0 and finite; R = 0: no filter.  hipFFT may take a work area. */
 int abacus_mf_smooth_spectrum_dev(void *spec_padded, int n, double Lbox, double R);
 
+/* ---------------------------------------------------------------- Spherical voids -------------------------- */
+/*
+ * Spherical voids of a periodic mesh on DEVICE pointers (csrc/voids.hip; Python: analysis/voids.py); every call enqueues on the
+ * library stream.  replaces: nothing in the reference, which has no void finder.  Algorithm: the mesh-based spherical void finder of
+ * Banerjee & Dalal 2016, stated so that its decisions are integers (tests/voids_statement.py is the NumPy statement).  A box of side
+ * L, a mesh of n^3 cells of side a = L / n, cell i centred at i a; m <= 32 radii R_0 > R_1 > .. > 0 with 2 R_0 <= L / 2 ("levels").
+ *   Field of level i: delta(k) as abacus_zcv_spectrum_dev leaves it, every mode times float32(W(x)), W(x) = 3 (sin x - x cos x) / x^3
+ *   evaluated in float64 (1 - x^2/10 + x^4/280 below x = 0.1, W(0) = 1), x = |k| R_i, |k| = (2 pi / L) sqrt(i^2 + j^2 + l^2) of the
+ *   integer mode numbers (index i -> i below n/2, i - n from n/2 on (x, y), 0 .. n/2 on z; the Nyquist planes keep the multiplier of
+ *   their |k|), then the C2R without normalisation.
+ *   Candidates of level i: the cells with value < threshold, compared in float32 (never a NaN; -inf is one).  Key: (value, flat index
+ *   (x n + y) n + z), ordered by value first; -0.0 and +0.0 are one value.
+ *   Overlap: two voids of levels i and j overlap iff d2 < D[i][j], d2 = dx^2 + dy^2 + dz^2 of the minimum-image integer differences of
+ *   their centre cells, D[i][j] = ceil((R_i / a + R_j / a)^2) an int64 table computed once by the caller in float64.  d2 = D[i][j],
+ *   touching spheres, is no overlap.
+ *   Selection: levels in increasing order; within a level the candidates in ascending key order; a candidate becomes a void of its
+ *   level iff it overlaps no void accepted so far.  The device reaches the same set in rounds: (1) the candidates that overlap a void
+ *   of an earlier level die; (2) every live candidate whose key is below that of every live candidate it overlaps is accepted; (3) the
+ *   live candidates that overlap a newly accepted one die; (2) and (3) repeat while one is live.  A round is two kernels (void_accept,
+ *   void_settle); the kernel boundary is the only synchronisation - no thread waits for another, no cooperative launch.  Every round
+ *   accepts at least the smallest live key, so the rounds of a level are at most its candidates; beyond that the call fails.
+ * "Padded meshes" as in the recon section: n * n rows of abacus_slab_pitch(n) floats, abacus_zcv_spectrum_bytes(n) bytes, aligned to
+ * 16 bytes.  Limits, checked before the device is touched, every message starting with the entry's name: n even, 4 .. 1024 (a cell
+ * is kept as three 10-bit coordinates); pitch >= n; 1 .. 32 levels, taken in increasing order and each at most once; D symmetric,
+ * positive and at most (n / 2)^2; the threshold finite; no null argument; a freed handle is refused, not followed.
+ */
+typedef struct abacus_void abacus_void;
+/* fails, naming the largest mesh that fits, when the spectrum, the smoothed mesh, the work area of one deposit and transform, the
+ * copies and deposit lists of np particles and the selection's worst case (every cell a candidate: 30 bytes per cell) do not fit */
+int abacus_void_check_memory(int n, int64_t np);
+/* spec_padded (not modified) -> out_padded: void_wtable fills float32(W) for s = i^2 + j^2 + l^2 = 0 .. 3 (n/2)^2 in float64 (no
+ * float32 sin / cos anywhere), void_tophat multiplies every mode by its entry (16 bytes per mode; the floats of a row beyond its
+ * n/2 + 1 modes are not written), then the C2R in place in out_padded: the field of a level in the first n floats of every row.
+ * R >= 0 and finite; the two meshes must differ.  hipFFT may take a work area. */
+int abacus_void_tophat_dev(const void *spec_padded, int n, double Lbox, double R, void *out_padded);
+/* a finder for a mesh of n^3 cells and nlevels levels; d2min_host: the table D[nlevels][nlevels] (HOST).  Touches no device memory. */
+int abacus_void_create(int n, int nlevels, const int64_t *d2min_host, abacus_void **handle);
+/* one level on the mesh (n * n rows of `pitch` floats, aligned to 4 bytes, not modified; the floats of a row beyond its n cells are
+ * never read): its candidates binned by integer bricks of at least sqrt(D[level][level]) cells (two passes over the mesh around a
+ * prefix scan), the voids of the earlier levels in a brick grid of their own, then the rounds.  *ncand, *nvoid, *rounds (HOST): the
+ * candidates, the voids accepted and the rounds of this level; no candidate (or none that survives the earlier levels): 0 voids,
+ * 0 rounds.  The live count is read back after every round; the accepted keys are sorted on the host and kept in the handle. */
+int abacus_void_level_dev(abacus_void *handle, const float *mesh, int pitch, int level, float threshold, int64_t *ncand, int64_t *nvoid,
+                          int64_t *rounds);
+/* the number of voids accepted so far, then their cells[nvoid][3] (x, y, z), levels[nvoid] and deltas[nvoid] (the centre value as
+ * keyed: -0.0 comes back as +0.0) into HOST arrays, in level order and within a level in ascending key order */
+int abacus_void_count(abacus_void *handle, int64_t *nvoid);
+int abacus_void_fetch(abacus_void *handle, int32_t *cells, int32_t *levels, float *deltas);
+/* releases the handle and its device buffers (NULL: nothing to do); a freed handle is refused */
+int abacus_void_free(abacus_void *handle);
+
 /* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
  * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
  * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
