@@ -620,6 +620,9 @@ int zcv_smooth_c2r_inplace(float *D, int n, double Lbox, double R) {
     }
     return inverse(D, n);
 }
+
+// wst.hip: the R2C in place of a padded real mesh (no normalisation), by the transform `forward` picks for the size
+int zcv_r2c_inplace(float *D, int n) { return forward(D, n); }
 }  // namespace abacus
 
 extern "C" {

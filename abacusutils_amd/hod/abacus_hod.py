@@ -776,6 +776,21 @@ class AbacusHOD:
                                      compensated=compensated, interlaced=interlaced, sigma_units=sigma_units)
         return out
 
+    def compute_wst(self, mock_dict, J=4, L=4, q=(0.8,), num_cells=256, sigma0=0.8, paste='TSC', compensated=True, interlaced=True,
+                    contrast=False, second_order=True):
+        """The solid-harmonic wavelet scattering coefficients S0, S1, S2 of every tracer's density field in the periodic box (no
+        reference counterpart; `analysis.wst.calc_wst`): {tracer: its result dict}.  `J` scales sigma0 2^j cells, angular orders
+        0 .. `L` <= 4, at most 8 exponents `q`.  The columns are taken from HBM when `mock_dict` is the untouched result of the latest
+        run_hod; a 'w' column weights its tracer.  No cross-tracer coefficients."""
+        from ..analysis.wst import calc_wst
+        out = {}
+        for tr in mock_dict.keys():
+            cols = self._xyz(mock_dict, tr)
+            pos = list(cols) if not isinstance(cols[0], np.ndarray) else np.stack([np.asarray(c) for c in cols], axis=1)
+            out[tr] = calc_wst(pos, self.lbox, J=J, L=L, q=q, sigma0=sigma0, nmesh=num_cells, w=mock_dict[tr].get('w', None), paste=paste,
+                               compensated=compensated, interlaced=interlaced, contrast=contrast, second_order=second_order)
+        return out
+
     def compute_voids(self, mock_dict, radii, threshold=-0.7, num_cells=256, paste='TSC', compensated=True, interlaced=True,
                       return_fields=False):
         """The spherical voids of every tracer's density contrast in the periodic box (no reference counterpart;

@@ -1240,6 +1240,59 @@ int abacus_void_fetch(abacus_void *handle, int32_t *cells, int32_t *levels, floa
 /* releases the handle and its device buffers (NULL: nothing to do); a freed handle is refused */
 int abacus_void_free(abacus_void *handle);
 
+/* ---------------------------------------------------------------- Wavelet scattering transform ------------- */
+/*
+ * Solid-harmonic wavelet scattering coefficients S0, S1, S2 of a periodic mesh on DEVICE pointers (csrc/wst.hip; Python:
+ * analysis/wst.py); every call enqueues on the library stream.  replaces: nothing in the reference, which has no such statistic.
+ * Estimator: Eickenberg et al. (2018) as used by Valogiannis & Dvorkin (2022); tests/wst_statement.py is the NumPy statement.
+ * A mesh of n^3 float32 cells, n even, N = n^3.
+ *   Field: rho^(k), a padded half spectrum in the delta(k) / N convention of abacus_zcv_spectrum_dev; the driver sets the mode k = 0
+ *   to 1 (rho = 1 + delta) or to 0 (the contrast).
+ *   Mode numbers: index i -> i below n/2, i - n from n/2 on (x, y), 0 .. n/2 on z.
+ *   Scales: sigma_j = sigma0 2^j cells, j = 0 .. J - 1.  Profile: g(kappa) = (sigma kappa)^l exp(-sigma^2 kappa^2 / 2), kappa =
+ *   (2 pi / n) sqrt(i^2 + j^2 + l^2), evaluated in float64 per value of the integer i^2 + j^2 + l^2 and rounded once to float32.
+ *   Harmonics: S_lm(k^), m = 1 .. 2 l + 1, the real harmonics scaled so that sum_m S_lm(a) S_lm(b) = P_l(a . b): polynomials of the
+ *   unit vector formed in float32 from the mode numbers (l = 0, 2, 4 as in the light-cone section; l = 1: z, x, y; l = 3:
+ *   z (5 z^2 - 3) / 2, sqrt(6)/4 {x, y} (5 z^2 - 1), sqrt(15)/2 z (x^2 - y^2), sqrt(15) x y z, sqrt(10)/4 x (x^2 - 3 y^2),
+ *   sqrt(10)/4 y (3 x^2 - y^2)).
+ *   Multiplier of a mode: g S_lm for even l, i g S_lm for odd l ((re, im) -> (-im, re)); for l > 0 exactly 0 at k = 0 and on every
+ *   mode with a mode number n/2 in any axis (the stored mode stands for +-n/2, S_lm differs on the two: only with the zeros is the
+ *   product Hermitian and the C2R defined).
+ *   First order: U1[j, l](x) = sqrt(sum_m (C2R[multiplier_{j, l, m} rho^](x))^2); l = 0: |C2R[..]|.
+ *   Second order, the same l and j1 < j2 only: U^ = R2C(U1[j1, l]) / N, U2[j1, j2, l] = the same expression on U^ at scale j2.
+ *   Coefficients, for Q exponents q: S0[q] = <|rho|^q>, S1[j, l, q] = <U1^q>, S2[j1, j2, l, q] = <U2^q>, means over the N cells of
+ *   pow((double)u, q) of the float32 cell, summed in float64 in two stages of a fixed order: the same bits on every run.
+ * Passes and their traffic per cell of the mesh: wst_mult 8 B (8 B read + 8 B written per mode, half as many modes as cells);
+ * wst_accum 8 B for the first m (4 read, 4 written), 12 B after it; wst_scale 8 B; wst_moments 4 B; between them the C2R (one per
+ * (j, l, m)) and the R2C (one per (j1, l)) in place.  "Padded meshes" as in the recon section: n * n rows of abacus_slab_pitch(n)
+ * floats, abacus_zcv_spectrum_bytes(n) bytes, aligned to 16 bytes; the floats of a row beyond its n cells (n/2 + 1 modes) are
+ * never read as data.  Limits, checked on the host before anything is launched, every message starting with the entry's name:
+ * n even, 4 .. 32766 (abacus_wst_moments_dev: 2 .. 32767, any parity, pitch >= n); 1 <= J <= 8; 0 <= L, ell <= 4; 1 <= nq <= 8 and
+ * 0 < q <= 8; sigma > 0 and finite; no null argument; the three meshes of abacus_wst_modulus_dev must not overlap.
+ */
+/* fails, naming the largest mesh that fits, when the four padded meshes of the chain (the spectrum, the work mesh, u2 / U, the
+ * spectrum of U), the profile table and the copies and deposit lists of np particles do not fit the free device memory */
+int abacus_wst_check_memory(int n, int64_t np);
+/* U[sigma, ell] of spec_padded (any padded spectrum in the 1 / N convention; not modified) into the first n floats of every row of
+ * out_padded, through work_padded (overwritten): wst_table, then for every m wst_mult, the C2R in place in work_padded and
+ * wst_accum.  sigma_cells in cells.  hipFFT may take a work area. */
+int abacus_wst_modulus_dev(const void *spec_padded, int n, double sigma_cells, int ell, void *work_padded, void *out_padded);
+/* the forward step of the second order: the R2C in place of a padded real mesh, every stored mode times float32(1 / N) (wst_scale) */
+int abacus_wst_spectrum_dev(void *mesh_padded, int n);
+/* sums_host[nq] (HOST, float64) = sum over the n^3 cells of pow((double)|x|, q_host[k]); mesh: n * n rows of `pitch` floats, aligned
+ * to 4 bytes, not modified (16-byte loads when aligned to 16 bytes with a pitch that is a multiple of 4).  Per-workgroup partial sums
+ * over a fixed deal of the rows to at most 2048 workgroups per exponent, then one workgroup per exponent over the partials: no float
+ * atomics, and the sum of an exponent does not depend on the others asked for.  q = 1, 2 and 0.5 are taken as |x|, x x (exact in
+ * float64) and the correctly rounded sqrt, which is what pow returns up to its own error (16 ulp) */
+int abacus_wst_moments_dev(const float *mesh, int n, int pitch, const double *q_host, int nq, double *sums_host);
+/* the whole (J, L, Q) loop on a resident spectrum.  spec_padded: its mode k = 0 is overwritten (1, or 0 with `contrast`), the rest
+ * is kept.  HOST arrays out, float64, the means: S0_host[nq], S1_host[J][L + 1][nq], S2_host[J][J][L + 1][nq] with NaN where
+ * j2 <= j1 (all NaN, or S2_host NULL, without `second_order`).  Takes three more padded meshes (two without second order) from the
+ * library's scratch.  (L + 1)^2 J C2R in first order, (L + 1)^2 J (J - 1) / 2 C2R and (L + 1) (J - 1) R2C in second; one copy of
+ * the sums and one synchronisation at the end. */
+int abacus_wst_coefficients_dev(void *spec_padded, int n, int J, int L, double sigma0_cells, const double *q_host, int nq, int contrast,
+                                int second_order, double *S0_host, double *S1_host, double *S2_host);
+
 /* ---- ZCV mode-coupling window (window.hip) ---------------------------------------------------------------------------------
  * replaces: the mesh loop of periodic_window_function (abacusnbody/hod/zcv/zenbu_window.py:75-89, :103, :126-174): for every mode
  * (i, j, k) of the n x n x n/2 half mesh (the Nyquist plane of the last axis is not visited) knorm = sqrt((kvals[k]^2 + kvals[j]^2)
