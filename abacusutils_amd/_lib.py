@@ -81,6 +81,7 @@ def lib():
         L.abacus_power_geometry_ms.restype = C.c_double
         L.abacus_pairvel.restype = L.abacus_pairvel_dev.restype = C.c_int    # analysis/pairwise_velocity.py
         L.abacus_fof.restype = L.abacus_fof_dev.restype = L.abacus_fof_stats.restype = C.c_int     # analysis/groups.py
+        L.abacus_mst.restype = L.abacus_mst_dev.restype = L.abacus_mst_stats.restype = C.c_int     # analysis/mst.py
         for name in ('tophat_dev', 'create', 'level_dev', 'count', 'fetch', 'free', 'check_memory'):                # analysis/voids.py
             getattr(L, 'abacus_void_' + name).restype = C.c_int
         L.abacus_void_tophat_dev.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p]

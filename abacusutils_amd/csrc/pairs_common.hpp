@@ -2,17 +2,19 @@
 // around the cell sort.  Everything here is declared once, in abacus::pairs; the sources keep what is theirs alone in an anonymous
 // namespace.
 //   pairs_common.hpp  this file
-//   cellsort.hip      the cell sort of every family (counting sort, radix sort, the label-aware sort of the jackknife - the only
-//                     file that includes hipCUB), staging of the caller's columns, the grids, g_work / g_stats / g_jk
+//   cellsort.hip      the cell sort of every family (counting sort, radix sort, the label-aware sort of the jackknife - with
+//                     mst.hip the only file that includes hipCUB), staging of the caller's columns, the grids, g_work / g_stats / g_jk
 //   pairs.hip         pair_count, pair_count2, pair_count3, pair_count_w, pair_vel, pair_count_los with their launches; the
 //                     drivers count_box (periodic) and count_los (open grid); the C ABI of the plain and jackknife counters
 //   pairs_jk.hip      pair_count_jk, pair_count_los_jk (the two walks with per-region histograms), their outputs and launches
 //   spheres.hip       sphere_count and its driver (abacus_spherecount)
 //   threepcf.hip      threepcf_walk and its driver (abacus_threepcf)
 //   fof.hip           fof_link, fof_flatten, fof_reduce, fof_emit and their driver (abacus_fof)
+//   mst.hip           mst_scan, mst_tie, mst_hook, mst_flatten (Boruvka's rounds), the edge sort (hipCUB, the second file that
+//                     includes it), mst_unpack, mst_reduce, mst_label and their driver (abacus_mst)
 // The cell walk stands in pair_count_w, pair_vel, pair_count_los (pairs.hip), pair_count_jk, pair_count_los_jk (pairs_jk.hip),
-// sphere_count (spheres.hip), threepcf_walk (threepcf.hip) and fof_link (fof.hip): a fix to one walk belongs in all of them
-// (profiles/pairs_shared_walk/README.md).
+// sphere_count (spheres.hip), threepcf_walk (threepcf.hip), fof_link (fof.hip) and mst_scan (mst.hip): a fix to one walk belongs
+// in all of them (profiles/pairs_shared_walk/README.md).
 #pragma once
 
 #include <cstring>

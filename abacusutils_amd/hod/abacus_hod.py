@@ -653,6 +653,15 @@ class AbacusHOD:
         return {tr: fof_groups(*self._xyz(mock_dict, tr), self.lbox, b_perp, b_par=b_par, nmax=nmax, return_labels=return_labels)
                 for tr in mock_dict.keys()}
 
+    def compute_mst(self, mock_dict, rmax, return_degree=True, return_labels=False):
+        """{tracer: the minimum spanning forest of the tracer} (analysis/mst.py: `minimum_spanning_tree` - 'i', 'j', 'r2',
+        'length', 'degree', 'labels', 'nedges', 'ncomp', 'n'); rmax in box units (`groups.linking_lengths` turns a fraction of the
+        mean separation into them).  The galaxies stay in HBM when `mock_dict` is the untouched result of the latest run_hod; one
+        catalogue per call - no tree across tracers; `mst.mst_branches` and `mst.mst_statistics` take it from there on the host"""
+        from ..analysis.mst import minimum_spanning_tree
+        return {tr: minimum_spanning_tree(*self._xyz(mock_dict, tr), self.lbox, rmax, return_degree=return_degree, return_labels=return_labels)
+                for tr in mock_dict.keys()}
+
     def compute_knn(self, mock_dict, radii, ks, nquery, seed=42, pimax=None, data_queries=False):
         """{tracer: the kNN-CDFs (len(ks), len(radii)) of `nquery` random centres} (analysis/spheres.py: `knn_cdf`); pimax: the
         (rp, pi) form.  data_queries: also '{a}_{b}' for every ORDERED tracer pair - the galaxies of a as queries around the

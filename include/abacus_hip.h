@@ -725,6 +725,41 @@ int abacus_fof_dev(const void *x, const void *y, const void *z, int64_t n, int p
 int abacus_fof_stats(uint64_t *candidates, uint64_t *links, int *ncell_xy, int *ncell_z);
 
 /*
+ * Minimum spanning forest of one catalogue on the periodic box: the edges, the degree of every point and the label of its tree,
+ * from which the minimum-spanning-tree statistics (degree, edge length, branch length, branch shape) follow (analysis/mst.py).
+ * No reference code stands behind this: the conventions below are the contract, pinned against the NumPy statement
+ * tests/mst_statement.py (Kruskal over the sorted edges, and Boruvka by rank).
+ *   graph    G(rmax): i != j are joined under the float32 expressions of abacus_spherecount and abacus_fof, bit for bit: d = p_i -
+ *            p_j per component, one -+boxsize when |d| > boxsize / 2, r2 = dx dx + dy dy + dz dz left to right, no FMA; an edge iff
+ *            r2 < rmax * rmax (a float32 product), strictly; a coincident twin is a neighbour at r2 = 0.  The edge set is that of
+ *            abacus_fof with b_perp = rmax and b_par = 0; spheres only.
+ *   order    edges compare by the key (r2, lo, hi), lo < hi the caller's indices of the two ends: strict and total, so the
+ *            minimum spanning forest is unique although float32 values of r2 tie.  It is the Euclidean minimum spanning tree
+ *            with its edges of r2 >= rmax * rmax removed: the Euclidean tree itself whenever ncomp == 1.
+ *   edges    edge_i, edge_j (uint32: lo and hi) and edge_r2 (float32), [n] each, the first nedges entries valid and ascending in
+ *            the key - the same bytes from every run and from both sort paths; the entries behind are zero;
+ *   degree   NULL, or [n] uint32 in the CALLER's order: the number of forest edges at the point;
+ *   labels   NULL, or [n] uint32 in the CALLER's order: the smallest caller index in the point's tree - the labels of abacus_fof;
+ *   nedges, ncomp   the number of edges and of trees: nedges + ncomp == n.
+ * Checked before the device is touched (every message starts with "abacus_mst: ", from both entries): x, y, z, edge_i, edge_j,
+ * edge_r2, nedges, ncomp not NULL; pos_dtype ABACUS_F32 or ABACUS_F64; boxsize > 0; 0 < rmax <= boxsize / 2 (the minimum image is
+ * not unique beyond); 0 <= n < 2^31.  A refused call writes nothing.
+ * Empty cases: n = 0 gives nedges = ncomp = 0; n = 1 no edge and one tree.
+ * The device runs Boruvka's rounds, at most 32 of them (the trees with an outgoing edge at least halve per round); a call that
+ * would need more returns an error.
+ * _dev: the columns in HBM, of ONE dtype (pos_dtype; float64 is cast to float32 on the device); every output is a host pointer in
+ * both forms.  Coordinates may lie in any interval, as for abacus_paircount_dev.
+ * abacus_mst_stats: of the last call, the candidate pairs evaluated over all rounds, the rounds that emitted edges, the cells per
+ * dimension in xy / z and - per_round not NULL - [32][3] uint64: per round the points scanned, those that found an edge out of
+ * their tree, and the edges emitted (the round after the last that emitted is listed too: it finds nothing).
+ */
+int abacus_mst(const float *x, const float *y, const float *z, int64_t n, float boxsize, float rmax, uint32_t *edge_i, uint32_t *edge_j,
+               float *edge_r2, uint32_t *degree, uint32_t *labels, uint64_t *nedges, uint64_t *ncomp);
+int abacus_mst_dev(const void *x, const void *y, const void *z, int64_t n, int pos_dtype, float boxsize, float rmax, uint32_t *edge_i,
+                   uint32_t *edge_j, float *edge_r2, uint32_t *degree, uint32_t *labels, uint64_t *nedges, uint64_t *ncomp);
+int abacus_mst_stats(uint64_t *candidates, int *rounds, int *ncell_xy, int *ncell_z, uint64_t *per_round);
+
+/*
  * Galaxy-galaxy lensing on the periodic box: the projected mass sums around galaxies, from which the excess surface density
  * Delta Sigma(R) follows (analysis/lensing.py).  The line of sight is a box axis and the projection runs along the whole box,
  * so both sets are pairs of TRANSVERSE columns.  The particles are sorted once into a 2-D periodic cell grid and stay in HBM
