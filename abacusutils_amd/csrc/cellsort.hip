@@ -16,8 +16,6 @@ using namespace abacus;
 using namespace abacus::pairs;
 
 namespace abacus {
-int exclusive_scan_u32(unsigned int *counters, int64_t n, int64_t *out, DevBuf &scratch, int zero_counters);
-
 namespace pairs {
 
 // the one set of work buffers, the bookkeeping of the last call and the jackknife's labels (pairs_common.hpp)

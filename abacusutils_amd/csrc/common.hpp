@@ -24,10 +24,8 @@ int scratch_trim_idle();
 // mesh of the out-of-place passes) hold nothing between calls: given back when an allocation of the caller's fails (abacus_malloc)
 int power_trim_caches();
 int fft_trim_scratch();
-// the in-place hipFFT plans shear.hip keeps for the last mesh size (their work areas are device memory)
-int shear_release_plans();
-// the same for zcv.hip
-int zcv_release_plans();
+// the in-place hipFFT plans mesh.hip keeps for the mesh families (their work areas are device memory)
+int release_plans();
 
 #define HIP_TRY(expr)                                                                                       \
     do {                                                                                                    \
@@ -100,6 +98,63 @@ struct DevBuf {
 };
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- what scan.hip, fft.hip, gfft.hip, xbin.hip and tsc.hip offer the other sources: each declared here and nowhere else.  The five
+// files include this header, so a default argument stands beside a definition the compiler has checked it against.
+struct BinArgs;   // bin_device.hpp
+// scan.hip
+int exclusive_scan_u32(unsigned int *counters, int64_t n, int64_t *out, DevBuf &scratch, int zero_counters);
+// fft.hip: the native transforms of a padded float32 mesh (power-of-two sizes here, the mixed-radix ones through gfft.hip)
+bool fft_native_supported(int n);
+bool fft_native_pow2(int n);
+int fft_native_r2c_inplace(float *mesh, int n, int pitch_r, float xcut = 0.f);
+int fft_native_zy(float *mesh, int n, int pitch_r, int64_t nx_local);
+int fft_native_x(float *mesh, int n, int pitch_r, int64_t ny_local, int64_t x_stride, int64_t y_stride);
+int fft_native_fused_supported(int n);
+int fft_native_r2c_fused(float *mesh, int n, int pitch_r, float xcut = 0.f);   // rows come out in the permuted order of fft.hip's fused form
+int fft_native_r2c_fused_zy(float *mesh, int n, int pitch_r, float xcut = 0.f);
+int fft_native_fused_zy_slab(float *mesh, int n, int pitch_r, int h, int64_t xsep, int xg0, int p0, int pc, float *pack_out, int world,
+                             float cut = 0.f);
+int fft_native_fused_x_slab(float *mesh, int n, int pitch_r, int64_t ny_local);
+int slab_layout_query(int n, int W, float cut, int pitch_c, int64_t *P_out, const unsigned int **row_off_dev);
+int fft_native_release();
+int fft_num_cus();
+const float2 *fft_twiddles(int n);   // exp(-2 pi i m / n), m < n, device table
+// gfft.hip
+bool gfft_supported(int n, int is_double);
+int gfft_r2c_inplace_f32(float *mesh, int n, int pitch_r, float xcut);
+int gfft_r2c_inplace_f64(double *mesh, int n, int pitch_r);
+int gfft_r2c_zy_f32(float *mesh, int n, int pitch_r);
+bool gfft_xbin_supported(int n, const BinArgs &b, bool comp, bool inter = false);
+int gfft_x_bin_run(const float *mesh, int n, int pitch_r, float inv_size, const float *W_dev, const BinArgs &b, const float *mesh2 = nullptr,
+                   const void *phase = nullptr);
+int gfft_release();
+// xbin.hip: the last transform pass fused with the binning
+bool xbin_supported(int n, int Nk, int Nmu, const BinArgs &b, bool comp);
+bool xbin2_supported(int n, const BinArgs &b, bool comp);
+int fft_x_bin_run(const float *mesh, int n, int pitch_r, float inv_size, const float *W_dev, const BinArgs &b, int dbg, int y0 = 0,
+                  int ny_local = 0, int put_geom = 1, int layout = 0, int world = 1, const float *mesh_shifted = nullptr,
+                  const float2 *phase = nullptr, const unsigned int *row_off = nullptr, int64_t plane_elems = 0, const float *mesh_b = nullptr,
+                  const float *mesh_b_shifted = nullptr);
+int xdesc_lookup(int n, const BinArgs &b, bool comp, size_t lds_other, const unsigned int **lut, const int **U, int *ncell, int *sh, int *off,
+                 int *vtop, const unsigned long long **cnt, const double **ksum, int *ok);
+double xbin_last_build_ms();
+int xbin_last_gen();
+int xbin_release();
+// tsc.hip: deposits into device meshes and their bookkeeping
+int tsc_deposit_f32(float *pos, int64_t n, const float *w, float *grid, int nmesh, int64_t zstride, double box, double offset, int wrap,
+                    double norm, int cic, int list_mode = 0, double sub = 1.0, int zero_grid = 1);
+int tsc_deposit_f64pos(double *pos, int64_t n, const double *w, float *grid, int nmesh, int64_t zstride, double box, double offset, int wrap,
+                       double norm, int cic, double sub = 1.0);
+int tsc_deposit_f64mesh(void *pos, int pos_f64, int64_t n, const void *w, double *grid, int nmesh, int64_t zstride, double box, double offset,
+                        int wrap, double norm, int cic, double sub);
+int tsc_deposit_slab_f32(float *pos, int64_t n, const float *w, float *grid, int nmesh, int xoff, int nx_local, int64_t zstride, double box,
+                         double offset, int wrap, double norm, int cic, double sub, int xoff2, int nx_alloc = 0);
+void tsc_wrapped_reset();
+int tsc_wrapped_seen();
+void tsc_lines_defer(int on);
+int tsc_lines_deferred_check();
+int tsc_release_work();
 
 // Orders the LDS traffic of ONE wave: its lanes' earlier LDS writes are visible to its lanes' later LDS reads (the LDS
 // executes a wave's instructions in order; the fences keep the compiler from moving accesses across).  Lets a wave that

@@ -535,10 +535,6 @@ int fft_x(float2 *data, int pitch_c, Tables *t, int64_t ny_local, int64_t x_stri
 
 namespace abacus {
 
-bool gfft_supported(int n, int is_double);
-int gfft_r2c_inplace_f32(float *mesh, int n, int pitch_r, float xcut);
-int gfft_release();
-
 // the tuned power-of-two kernels of this file (also what the slab-decomposed transform needs)
 bool fft_native_pow2(int n) { return n >= 64 && n <= 2048 && (n & (n - 1)) == 0; }
 // ... or the mixed-radix kernels of gfft.hip (even sizes with factors 2, 3, 5, 7, 11, 13: 72, 96, 384, 550, 768, 1536 ...).

@@ -21,11 +21,6 @@
 
 using namespace abacus;
 
-namespace abacus {
-int xdesc_lookup(int n, const BinArgs &b, bool comp, size_t lds_other, const unsigned int **lut, const int **U, int *ncell, int *sh, int *off,
-                 int *vtop, const unsigned long long **cnt, const double **ksum, int *ok);   // xbin.hip
-}
-
 namespace {
 
 constexpr int G_NT = 512;

@@ -31,39 +31,17 @@
 #include <cmath>
 #include <vector>
 
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "mesh_common.hpp"
 
 using namespace abacus;
 
-namespace abacus {
-int zcv_smooth_c2r_inplace(float *D, int n, double Lbox, double R);
-size_t zcv_padded_bytes(int n);
-}  // namespace abacus
-
 namespace {
 
-constexpr int BLK = 256;
 constexpr int MF_MAX_THR = 64, MF_BINS = MF_MAX_THR + 1, MF_OUT = 4 * MF_BINS;
 constexpr int MF_TY = 16, MF_TZ = 64, MF_XC = 32;        // tile rows, tile cells along z, planes per chunk
 constexpr int MF_ROWS = MF_TY + 1, MF_WORDS = MF_TZ / 4 + 1, MF_TASKS = MF_ROWS * MF_WORDS;
 constexpr int MF_TABLE = 128;                            // the thresholds, NaN beyond them: 9 groups of 8 are read at most
 constexpr int MOM_GRID = 2048;                           // the fixed partition of the moments: rows are dealt to this many workgroups
-
-struct Scratch {   // scratch_acquire'd blocks released when the entry point returns
-    std::vector<void *> blocks;
-    ~Scratch() {
-        for (void *p : blocks) scratch_release(p);
-    }
-    template <class T>
-    int get(T **out, size_t bytes) {
-        void *p = nullptr;
-        ABACUS_TRY(scratch_acquire(&p, bytes));
-        blocks.push_back(p);
-        *out = static_cast<T *>(p);
-        return 0;
-    }
-};
 
 // one load task of a plane: a row of the tile (already wrapped) and four cells of it
 struct MfTask {
@@ -234,19 +212,6 @@ __global__ __launch_bounds__(320) void mf_count_final(const unsigned int *__rest
     if (s) atomicAdd(out + t, s);
 }
 
-// fixed-order sum of one double per thread over the workgroup; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *lds) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = BLK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
-}
-
 // partial[b] = sum x, partial[gridDim.x + b] = sum x^2 over the rows b, b + gridDim.x, ... in float64; every product x * x of two
 // float32 is exact in float64.  VEC: float4 loads (rows aligned to 16 bytes), the cells beyond the last full float4 one by one.
 template <bool VEC>
@@ -306,18 +271,8 @@ int abacus_mf_check_memory(int n, int64_t np) {
     ABACUS_ENTER();
     // the spectrum (smoothed in place), the two work meshes of an interlaced deposit + transform (or the work area of the C2R), the
     // packed copy of the particles and the lists of the deposit (about one position's worth again)
-    auto bytes_of = [=](int m) { return 3 * zcv_padded_bytes(m) + (size_t)np * 24; };
-    const size_t slack = (size_t)256 << 20;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes_of(n) + slack <= free_b) return 0;
-    ABACUS_TRY(scratch_trim_idle());
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes_of(n) + slack <= free_b) return 0;
-    int m = n;
-    while (m > 2 && bytes_of(m) + slack > free_b) m -= 2;
-    return fail("%s: the meshes of %d^3 need %.1f GB of HBM, %.1f GB are free; the largest mesh that fits is %d^3", who, n,
-                1e-9 * (double)bytes_of(n), 1e-9 * (double)free_b, m);
+    auto bytes_of = [=](int m) { return 3 * padded_bytes(m) + (size_t)np * 24; };
+    return check_memory(who, n, 2, bytes_of);
 }
 
 int abacus_mf_counts_dev(const float *mesh, int n, int pitch, const float *thresholds_host, int nthr, int64_t *counts_host) {
@@ -398,7 +353,7 @@ int abacus_mf_smooth_spectrum_dev(void *spec_padded, int n, double Lbox, double 
     if (!(Lbox > 0) || !std::isfinite(Lbox)) return fail("%s: Lbox must be positive", who);
     if (!(R >= 0) || !std::isfinite(R)) return fail("%s: R must be finite and not negative, got %g", who, R);
     ABACUS_ENTER();
-    return zcv_smooth_c2r_inplace((float *)spec_padded, n, Lbox, R);
+    return smooth_c2r_inplace((float *)spec_padded, n, Lbox, R);
 }
 
 }  // extern "C"

@@ -22,64 +22,16 @@
 // when the bin changes.  Histograms are float64 / integer and are flushed to HBM with one atomic per non-empty bin
 // per workgroup at the very end.  (The reference keeps float32 per-thread accumulators, :221-229; float64 sums are
 // strictly more accurate and thread-count independent.)
-#include <hipfft/hipfft.h>
-
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <vector>
 
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "mesh_common.hpp"
 #include "bin_device.hpp"
 
 using namespace abacus;
-
-namespace abacus {
-int tsc_deposit_f32(float *pos, int64_t n, const float *w, float *grid, int nmesh, int64_t zstride, double box,
-                    double offset, int wrap, double norm, int cic, int list_mode = 0, double sub = 1.0, int zero_grid = 1);
-void tsc_wrapped_reset();
-int tsc_wrapped_seen();
-void tsc_lines_defer(int on);
-int tsc_lines_deferred_check();
-int tsc_deposit_f64mesh(void *pos, int pos_f64, int64_t n, const void *w, double *grid, int nmesh, int64_t zstride, double box,
-                        double offset, int wrap, double norm, int cic, double sub);
-bool gfft_supported(int n, int is_double);
-int gfft_r2c_inplace_f64(double *mesh, int n, int pitch_r);
-int tsc_deposit_f64pos(double *pos, int64_t n, const double *w, float *grid, int nmesh, int64_t zstride, double box,
-                       double offset, int wrap, double norm, int cic, double sub = 1.0);
-int tsc_release_work();
-bool fft_native_supported(int n);
-bool fft_native_pow2(int n);
-int fft_native_r2c_inplace(float *mesh, int n, int pitch_r, float xcut = 0.f);
-int fft_native_zy(float *mesh, int n, int pitch_r, int64_t nx_local);
-int fft_native_x(float *mesh, int n, int pitch_r, int64_t ny_local, int64_t x_stride, int64_t y_stride);
-int tsc_deposit_slab_f32(float *pos, int64_t n, const float *w, float *grid, int nmesh, int xoff, int nx_local,
-                         int64_t zstride, double box, double offset, int wrap, double norm, int cic, double sub, int xoff2, int nx_alloc = 0);
-int fft_native_release();
-int fft_native_fused_supported(int n);
-int fft_native_r2c_fused(float *mesh, int n, int pitch_r, float xcut = 0.f);   // rows come out in the permuted order of fft.hip's fused form
-int fft_native_r2c_fused_zy(float *mesh, int n, int pitch_r, float xcut = 0.f);
-bool xbin_supported(int n, int Nk, int Nmu, const BinArgs &b, bool comp);
-int fft_x_bin_run(const float *mesh, int n, int pitch_r, float inv_size, const float *W_dev, const BinArgs &b, int dbg,
-                  int y0 = 0, int ny_local = 0, int put_geom = 1, int layout = 0, int world = 1, const float *mesh_shifted = nullptr,
-                  const float2 *phase = nullptr, const unsigned int *row_off = nullptr, int64_t plane_elems = 0,
-                  const float *mesh_b = nullptr, const float *mesh_b_shifted = nullptr);
-bool xbin2_supported(int n, const BinArgs &b, bool comp);
-bool gfft_supported(int n, int is_double);
-int gfft_r2c_zy_f32(float *mesh, int n, int pitch_r);
-bool gfft_xbin_supported(int n, const BinArgs &b, bool comp, bool inter = false);
-int gfft_x_bin_run(const float *mesh, int n, int pitch_r, float inv_size, const float *W_dev, const BinArgs &b, const float *mesh2 = nullptr,
-                   const void *phase = nullptr);
-int fft_native_fused_zy_slab(float *mesh, int n, int pitch_r, int h, int64_t xsep, int xg0, int p0, int pc, float *pack_out,
-                             int world, float cut = 0.f);
-int slab_layout_query(int n, int W, float cut, int pitch_c, int64_t *P_out, const unsigned int **row_off_dev);
-int fft_native_fused_x_slab(float *mesh, int n, int pitch_r, int64_t ny_local);
-double xbin_last_build_ms();
-int xbin_last_gen();
-int xbin_release();
-}  // namespace abacus
 
 namespace {
 
@@ -720,26 +672,6 @@ int upload_batches(int64_t n, int nmesh, int interlaced) {
     const int K = (int)std::floor(0.8 * t_up / std::max(t_rmw, 1e-9));
     // batches of at least 8e6 particles: the list build of a batch must keep its two levels
     return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)K, (int64_t)8, n / 8000000}));
-}
-
-int fft_check(hipfftResult r, const char *what) {
-    if (r != HIPFFT_SUCCESS) return fail("%s failed (hipfftResult %d)", what, (int)r);
-    return 0;
-}
-
-// real-row pitch (floats): rows start on 128-B boundaries, >= n + 2 for the in-place R2C layout
-int pitch_r(int n) { return (n + 2 + 31) / 32 * 32; }
-
-// hipFFT allocates its work area when a plan is made: with idle scratch blocks of this library around, give them back and try
-// once more before reporting the failure
-template <typename F>
-hipfftResult plan_with_retry(F make) {
-    hipfftResult r = make();
-    if (r != HIPFFT_SUCCESS) {
-        (void)hipGetLastError();
-        if (scratch_trim_idle() == 0) r = make();
-    }
-    return r;
 }
 
 int get_plan(int n, hipfftHandle *out) {
@@ -1890,7 +1822,7 @@ int power_trim_caches() {
     return 0;
 }
 
-// For zcv.hip.  What get_field_fft returns (deposit, transform, interlacing combine, compensation) for DEVICE particles, written
+// For zcv.hip and the mesh statistics (mesh_common.hpp).  What get_field_fft returns (deposit, transform, interlacing combine, compensation) for DEVICE particles, written
 // into the caller's padded spectrum `dest` (n * n rows of pitch_r(n) / 2 complex): the work meshes of the context are free again
 // when this returns, the spectrum stays with the caller.
 int power_field_spectrum_dev(float *pos, int64_t n, const float *w, double Lbox, int nmesh, int paste, const float *W_host, int interlaced,
@@ -1972,7 +1904,6 @@ int abacus_power_release(void) {
 // (tsc.hip), the mixed-radix double-precision transform of gfft.hip, raw power in float64, then the usual binning (float64
 // accumulators over the weights rounded to float32).
 namespace {
-int pitch_r64(int n) { return (n + 2 + 15) / 16 * 16; }          // doubles per z row: rows start on 128-B lines
 
 // spectrum *= inv_size; /= (W[i] W[j]) W[k] (float32 products like the reference's broadcast, :1063-1069)
 __global__ void f64_scale_compensate(double2 *__restrict__ f, int n, int pitch_c, double inv_size, const float *__restrict__ W) {

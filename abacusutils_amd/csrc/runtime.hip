@@ -385,8 +385,7 @@ int abacus_profile_enable(int on) {
 }
 int abacus_scratch_release(void) {
     ABACUS_ENTER();
-    ABACUS_TRY(shear_release_plans());
-    ABACUS_TRY(zcv_release_plans());
+    ABACUS_TRY(release_plans());
     return scratch_trim();
 }
 int abacus_profile_select(const char *name) {

@@ -12,36 +12,20 @@
 //
 // Meshes: `dfour` and the work mesh are padded like power.hip's (rows of pitch_r = roundup(n + 2, 32) floats); Q is the caller's
 // output (n^3 float32).  All flat indices are 64-bit; grids are sized from the CU count.
-#include <hipfft/hipfft.h>
-
 #include <algorithm>
 #include <cmath>
 #include <map>
 #include <vector>
 
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "mesh_common.hpp"
 
 using namespace abacus;
 
-namespace abacus {
-int tsc_deposit_f32(float *pos, int64_t n, const float *w, float *grid, int nmesh, int64_t zstride, double box, double offset, int wrap,
-                    double norm, int cic, int list_mode, double sub, int zero_grid);
-bool fft_native_supported(int n);
-int fft_native_r2c_inplace(float *mesh, int n, int pitch_r, float xcut);
-int fft_num_cus();
-}  // namespace abacus
-
 namespace {
 
-constexpr int BLK = 256;
 constexpr int RING_MAX = 8;     // radii with a register-ring instantiation (sigma <= 2.1 cells)
 constexpr int ZLDS_MAX = 64;    // largest radius of the LDS row kernel
 constexpr int ZTILE = 2048;     // outputs per LDS tile of the z pass
-
-int pitch_r(int n) { return (n + 2 + 31) / 32 * 32; }
-size_t padded_bytes(int n) { return (size_t)n * n * pitch_r(n) * sizeof(float); }
-unsigned int grid_for(int64_t blocks, int per_cu) { return (unsigned int)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)fft_num_cus() * per_cu)); }
 
 // scipy's 'reflect' (d c b a | a b c d | d c b a): period 2n, any j
 __device__ __forceinline__ int reflect_any(int j, int n) {
@@ -235,53 +219,6 @@ __global__ __launch_bounds__(BLK) void mesh_gather(const float *__restrict__ mes
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-struct Scratch {   // scratch_acquire'd blocks released when the entry point returns
-    std::vector<void *> blocks;
-    ~Scratch() {
-        for (void *p : blocks) scratch_release(p);
-    }
-    template <class T>
-    int get(T **out, size_t bytes) {
-        void *p = nullptr;
-        ABACUS_TRY(scratch_acquire(&p, bytes));
-        blocks.push_back(p);
-        *out = static_cast<T *>(p);
-        return 0;
-    }
-};
-
-// in-place hipFFT plans in the padded layout: [0] R2C (sizes the native transforms do not cover), [1] C2R.  One size is kept.
-hipfftHandle g_plan[2] = {0, 0};
-int g_plan_n[2] = {0, 0};
-
-int fft_check(hipfftResult r, const char *what) {
-    if (r != HIPFFT_SUCCESS) return fail("%s failed (hipfftResult %d)", what, (int)r);
-    return 0;
-}
-
-int get_plan(int n, int inverse, hipfftHandle *out) {
-    if (g_plan_n[inverse] != n) {
-        if (g_plan_n[inverse]) (void)hipfftDestroy(g_plan[inverse]);
-        g_plan_n[inverse] = 0;
-        int dims[3] = {n, n, n};
-        int rembed[3] = {n, n, pitch_r(n)}, cembed[3] = {n, n, pitch_r(n) / 2};
-        auto make = [&] {
-            return inverse ? hipfftPlanMany(&g_plan[1], 3, dims, cembed, 1, 1, rembed, 1, 1, HIPFFT_C2R, 1)
-                           : hipfftPlanMany(&g_plan[0], 3, dims, rembed, 1, 1, cembed, 1, 1, HIPFFT_R2C, 1);
-        };
-        hipfftResult r = make();
-        if (r != HIPFFT_SUCCESS) {      // hipFFT allocates its work area with the plan: give idle scratch back and try once more
-            (void)hipGetLastError();
-            if (scratch_trim_idle() == 0) r = make();
-        }
-        ABACUS_TRY(fft_check(r, "hipfftPlanMany"));
-        g_plan_n[inverse] = n;
-    }
-    ABACUS_TRY(fft_check(hipfftSetStream(g_plan[inverse], stream()), "hipfftSetStream"));
-    *out = g_plan[inverse];
-    return 0;
-}
-
 // scipy.ndimage's _gaussian_kernel1d with truncate = 4: w[0] centre .. w[radius], normalised over the 2 radius + 1 taps
 void gauss_weights(double sigma, std::vector<double> &w) {
     const int radius = (int)(4.0 * sigma + 0.5);
@@ -369,41 +306,15 @@ int check_size(const char *who, int n) {
     return 0;
 }
 
-// two padded meshes (the spectrum and the work mesh) must fit beside what is allocated already
-int check_memory(int n) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t slack = (size_t)256 << 20;
-    if (2 * padded_bytes(n) + slack <= free_b) return 0;
-    ABACUS_TRY(scratch_trim_idle());
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (2 * padded_bytes(n) + slack <= free_b) return 0;
-    int m = n;
-    while (m > 2 && 2 * padded_bytes(m) + slack > free_b) m -= 2;
-    return fail("shear: two work meshes of %d^3 need %.1f GB of HBM, %.1f GB are free; the largest mesh that fits is %d^3", n,
-                2e-9 * (double)padded_bytes(n), 1e-9 * (double)free_b, m);
-}
-
 // D: padded mesh holding the (smoothed) density, W: padded work mesh, out: n^3 floats
 int shear_run(float *D, float *W, float *out, int n, double Lbox, double R, Scratch &sc) {
     const int pr = pitch_r(n), pc = pr / 2;
-    if (fft_native_supported(n) && !option("fft_hipfft")) {
-        ABACUS_TRY(fft_native_r2c_inplace(D, n, pr, 0.f));       // the plain three-pass form: rows in natural order
-    } else {
-        hipfftHandle fwd;
-        ABACUS_TRY(get_plan(n, 0, &fwd));
-        prof_begin("hipfft_r2c");
-        const hipfftResult r = hipfftExecR2C(fwd, (hipfftReal *)D, (hipfftComplex *)D);
-        prof_end("hipfft_r2c");
-        ABACUS_TRY(fft_check(r, "hipfftExecR2C"));
-    }
+    ABACUS_TRY(r2c_inplace(D, n));       // native: the plain three-pass form, rows in natural order
     std::vector<float> kh;
     wavenumbers(n, Lbox, kh);
     float *karr = nullptr;
     ABACUS_TRY(sc.get(&karr, kh.size() * sizeof(float)));
     ABACUS_TRY(upload(karr, kh.data(), kh.size() * sizeof(float)));
-    hipfftHandle inv;
-    ABACUS_TRY(get_plan(n, 1, &inv));
     const float scale = (float)(1.0 / ((double)n * n * n));
     const unsigned int grid = grid_for((int64_t)n * n, 16);
     static const int comp[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
@@ -415,10 +326,7 @@ int shear_run(float *D, float *W, float *out, int n, double Lbox, double R, Scra
         else
             ABACUS_LAUNCH("tidal_component", tidal_component<false>, dim3(grid), dim3(BLK), 0, (const float2 *)D, (float2 *)W, karr, n, pc, ci,
                           cj, scale, 0.0);
-        prof_begin("hipfft_c2r");
-        const hipfftResult r = hipfftExecC2R(inv, (hipfftComplex *)W, (hipfftReal *)W);
-        prof_end("hipfft_c2r");
-        ABACUS_TRY(fft_check(r, "hipfftExecC2R"));
+        ABACUS_TRY(c2r_inplace(W, n));
         const float w = ci == cj ? 1.f : 2.f;
         if (q == 0)
             ABACUS_LAUNCH("shear_accumulate", (shear_accumulate<true, false>), dim3(grid), dim3(BLK), 0, W, out, n, pr, w);
@@ -431,16 +339,6 @@ int shear_run(float *D, float *W, float *out, int n, double Lbox, double R, Scra
 }
 
 }  // namespace
-
-namespace abacus {
-int shear_release_plans() {
-    for (int i = 0; i < 2; i++) {
-        if (g_plan_n[i]) (void)hipfftDestroy(g_plan[i]);
-        g_plan_n[i] = 0;
-    }
-    return 0;
-}
-}  // namespace abacus
 
 extern "C" {
 
@@ -459,7 +357,7 @@ int abacus_shear_dev(float *dens, float *out, int n, double Lbox, double R_or_ne
     ABACUS_ENTER();
     if (!dens || !out) return fail("abacus_shear_dev: null argument");
     ABACUS_TRY(check_size("abacus_shear_dev", n));
-    ABACUS_TRY(check_memory(n));
+    ABACUS_TRY(check_memory("shear", n, 2, [](int m) { return 2 * padded_bytes(m); }));       // the spectrum and the work mesh
     Scratch sc;
     float *D = nullptr, *W = nullptr;
     ABACUS_TRY(sc.get(&D, padded_bytes(n)));
@@ -473,7 +371,7 @@ int abacus_shearmark_dev(const float *pos, int64_t np, int n, double Lbox, doubl
     ABACUS_ENTER();
     if (!pos || !out || np < 1) return fail("abacus_shearmark_dev: null argument or no particles");
     ABACUS_TRY(check_size("abacus_shearmark_dev", n));
-    ABACUS_TRY(check_memory(n));
+    ABACUS_TRY(check_memory("shear", n, 2, [](int m) { return 2 * padded_bytes(m); }));       // the spectrum and the work mesh
     Scratch sc;
     float *D = nullptr, *W = nullptr, *p = nullptr;
     ABACUS_TRY(sc.get(&D, padded_bytes(n)));

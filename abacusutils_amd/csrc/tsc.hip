@@ -31,10 +31,6 @@
 
 using namespace abacus;
 
-namespace abacus {
-int exclusive_scan_u32(unsigned int *counters, int64_t n, int64_t *out, DevBuf &scratch, int zero_counters);
-}
-
 namespace {
 
 constexpr int TSC_BLOCK = 256;

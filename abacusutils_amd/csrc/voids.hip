@@ -36,20 +36,12 @@
 #include <set>
 #include <vector>
 
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "mesh_common.hpp"
 
 using namespace abacus;
 
-namespace abacus {
-int zcv_smooth_c2r_inplace(float *D, int n, double Lbox, double R);
-size_t zcv_padded_bytes(int n);
-int exclusive_scan_u32(unsigned int *counters, int64_t n, int64_t *out, DevBuf &scratch, int zero_counters);
-}  // namespace abacus
-
 namespace {
 
-constexpr int BLK = 256;
 constexpr int VOID_MAX_LEVELS = 32, VOID_MIN_N = 4, VOID_MAX_N = 1024;
 
 __device__ __forceinline__ unsigned int void_fkey(float v) {   // fkey of pairs_common.hpp: an order-preserving integer image
@@ -377,18 +369,8 @@ int abacus_void_check_memory(int n, int64_t np) {
     // the spectrum, the smoothed mesh, the work mesh of an interlaced deposit (or the work area of the C2R), the packed copy and the
     // deposit lists of the particles, and the worst case of the selection: every cell a candidate (two keys and two flags each) in
     // bricks of one cell (a counter and an offset each)
-    auto bytes_of = [=](int m) { return 3 * zcv_padded_bytes(m) + (size_t)np * 24 + (size_t)m * m * m * 30; };
-    const size_t slack = (size_t)256 << 20;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes_of(n) + slack <= free_b) return 0;
-    ABACUS_TRY(scratch_trim_idle());
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes_of(n) + slack <= free_b) return 0;
-    int m = n;
-    while (m > VOID_MIN_N && bytes_of(m) + slack > free_b) m -= 2;
-    return fail("%s: the meshes of %d^3 need %.1f GB of HBM, %.1f GB are free; the largest mesh that fits is %d^3", who, n,
-                1e-9 * (double)bytes_of(n), 1e-9 * (double)free_b, m);
+    auto bytes_of = [=](int m) { return 3 * padded_bytes(m) + (size_t)np * 24 + (size_t)m * m * m * 30; };
+    return check_memory(who, n, 2, bytes_of);
 }
 
 int abacus_void_tophat_dev(const void *spec_padded, int n, double Lbox, double R, void *out_padded) {
@@ -408,7 +390,7 @@ int abacus_void_tophat_dev(const void *spec_padded, int n, double Lbox, double R
         ABACUS_LAUNCH("void_wtable", void_wtable, dim3(grid_for(count)), dim3(BLK), 0, (float *)table, count, 2.0 * M_PI / Lbox * R);
         ABACUS_LAUNCH("void_tophat", void_tophat, dim3((unsigned int)std::min<int64_t>((int64_t)n * n, 1 << 16)), dim3(BLK), 0,
                       (const float2 *)spec_padded, (float2 *)out_padded, n, pc, (const float *)table);
-        return zcv_smooth_c2r_inplace((float *)out_padded, n, Lbox, 0.0);
+        return smooth_c2r_inplace((float *)out_padded, n, Lbox, 0.0);
     };
     const int rc = body();
     scratch_release(table);    // the stream orders the next user of the block behind void_tophat

@@ -18,14 +18,9 @@
 #include <cmath>
 #include <vector>
 
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "mesh_common.hpp"
 
 using namespace abacus;
-
-namespace abacus {
-int fft_num_cus();
-}
 
 namespace {
 
@@ -148,21 +143,6 @@ __global__ __launch_bounds__(256) void window_reduce(const double *__restrict__ 
     for (int c = 0; c < WIN_COPIES; c++) s += acc[(int64_t)e * WIN_COPIES + c];
     out[e] = s;
 }
-
-struct Scratch {   // scratch_acquire'd blocks released when the entry point returns
-    std::vector<void *> blocks;
-    ~Scratch() {
-        for (void *p : blocks) scratch_release(p);
-    }
-    template <class T>
-    int get(T **out, size_t bytes) {
-        void *p = nullptr;
-        ABACUS_TRY(scratch_acquire(&p, bytes));
-        blocks.push_back(p);
-        *out = static_cast<T *>(p);
-        return 0;
-    }
-};
 
 }  // namespace
 

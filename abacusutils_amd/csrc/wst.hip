@@ -28,46 +28,22 @@
 #include <cmath>
 #include <vector>
 
-#include "../../include/abacus_hip.h"
-#include "common.hpp"
+#include "mesh_common.hpp"
 
 using namespace abacus;
 
-namespace abacus {
-int zcv_smooth_c2r_inplace(float *D, int n, double Lbox, double R);
-int zcv_r2c_inplace(float *D, int n);
-size_t zcv_padded_bytes(int n);
-int fft_num_cus();
-}  // namespace abacus
-
 namespace {
 
-constexpr int BLK = 256, WAVES = BLK / 64;
+constexpr int WAVES = BLK / 64;
 constexpr int WST_MIN_N = 4, WST_MAX_N = 32766, WST_MAX_J = 8, WST_MAX_L = 4, WST_MAX_Q = 8;
 constexpr double WST_MAX_EXP = 8.0;
 constexpr int MOM_GRID = 2048;   // the fixed partition of the moments: rows are dealt to this many workgroups
-
-struct Scratch {   // scratch_acquire'd blocks released when the entry point returns
-    std::vector<void *> blocks;
-    ~Scratch() {
-        for (void *p : blocks) scratch_release(p);
-    }
-    template <class T>
-    int get(T **out, size_t bytes) {
-        void *p = nullptr;
-        ABACUS_TRY(scratch_acquire(&p, bytes));
-        blocks.push_back(p);
-        *out = static_cast<T *>(p);
-        return 0;
-    }
-};
 
 struct QArgs {   // the exponents of one moment pass
     double q[WST_MAX_Q];
     int nq;
 };
 
-int pitch_of(int n) { return (n + 2 + 31) / 32 * 32; }
 int table_count(int n) { return 3 * (n / 2) * (n / 2) + 1; }     // n <= 32766: below 2^30
 unsigned int grid_rows(int64_t rows) {
     return (unsigned int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, WAVES), (int64_t)fft_num_cus() * 16));
@@ -87,7 +63,7 @@ constexpr float W_SQRT3 = 1.7320508075688772f, W_SQRT5 = 2.23606797749979f, W_SQ
                 W_SQRT15 = 3.872983346207417f, W_SQRT35 = 5.916079783099616f, W_SQRT70 = 8.366600265340756f;
 
 // S_lm, m = 0 .. 2 ELL, of the direction of (x, y, z) != 0, scaled so that sum_m S_lm(a) S_lm(b) = P_l(a . b); the order and the
-// polynomials are those of `harmonics` in tests/wst_statement.py (l = 2, 4: those of lc_ylm in zcv.hip).  m is uniform over the
+// polynomials are those of `harmonics` in tests/wst_statement.py (l = 2, 4: those of lc_ylm in lc_power.hip).  m is uniform over the
 // launch: a scalar branch.  Even l: products of two components times inv2 = 1 / |r|^2; odd l: one component times inv1 = 1 / |r|
 // and an even polynomial.  The hardware reciprocal and reciprocal square root (1 ulp) stand for the divisions.
 template <int ELL>
@@ -225,19 +201,6 @@ __global__ __launch_bounds__(BLK) void wst_scale(float4 *__restrict__ spec, int 
         }
 }
 
-// fixed-order sum of one double per thread over the workgroup; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *lds) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = BLK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
-}
-
 // partial[k gridDim.x + b] = the float64 sum of pow((double)|x|, q_k) over the rows b, b + gridDim.x, ..., k = blockIdx.y: one
 // exponent per workgroup (the double pow sets the time, not the 4 bytes per cell, which the exponents after the first read from the
 // caches), so the sum of an exponent does not depend on which others are asked for.  q = 1, 2 and 0.5 take |x|, x x (exact in
@@ -325,7 +288,7 @@ int launch_moments(const float *mesh, int n, int pitch, const QArgs &qa, double 
 
 int launch_mult(int ell, const float *spec, float *work, int n, const float *table, int m) {
     const dim3 grid(grid_rows((int64_t)n * n)), block(BLK);
-    const int pitch4 = pitch_of(n) / 4;
+    const int pitch4 = pitch_r(n) / 4;
 #define WST_MULT(E) ABACUS_LAUNCH("wst_mult", (wst_mult<E>), grid, block, 0, (const float4 *)spec, (float4 *)work, n, pitch4, table, m)
     switch (ell) {
     case 0: WST_MULT(0); break;
@@ -340,12 +303,12 @@ int launch_mult(int ell, const float *spec, float *work, int n, const float *tab
 
 // U[sigma, ell] of the padded spectrum `spec` into `out` through `work`; table: table_count(n) floats.  Arguments already checked.
 int modulus(const float *spec, int n, double sigma, int ell, float *work, float *out, float *table) {
-    const int count = table_count(n), pitch = pitch_of(n), nm = 2 * ell + 1;
+    const int count = table_count(n), pitch = pitch_r(n), nm = 2 * ell + 1;
     const dim3 grid(grid_rows((int64_t)n * n)), block(BLK);
     ABACUS_LAUNCH("wst_table", wst_table, dim3((unsigned int)ceil_div(count, BLK)), block, 0, table, count, sigma, 2.0 * M_PI / n, ell);
     for (int m = 0; m < nm; m++) {
         ABACUS_TRY(launch_mult(ell, spec, work, n, table, m));
-        ABACUS_TRY(zcv_smooth_c2r_inplace(work, n, 1.0, 0.0));      // no filter: the C2R in place
+        ABACUS_TRY(smooth_c2r_inplace(work, n, 1.0, 0.0));      // no filter: the C2R in place
         if (nm == 1)
             ABACUS_LAUNCH("wst_accum", (wst_accum<true, true>), grid, block, 0, (const float *)work, out, n, pitch);
         else if (m == 0)
@@ -359,8 +322,8 @@ int modulus(const float *spec, int n, double sigma, int ell, float *work, float 
 }
 
 int spectrum_inplace(float *mesh, int n) {
-    ABACUS_TRY(zcv_r2c_inplace(mesh, n));
-    ABACUS_LAUNCH("wst_scale", wst_scale, dim3(grid_rows((int64_t)n * n)), dim3(BLK), 0, (float4 *)mesh, n, pitch_of(n) / 4,
+    ABACUS_TRY(r2c_inplace(mesh, n));
+    ABACUS_LAUNCH("wst_scale", wst_scale, dim3(grid_rows((int64_t)n * n)), dim3(BLK), 0, (float4 *)mesh, n, pitch_r(n) / 4,
                   (float)(1.0 / ((double)n * n * n)));
     return 0;
 }
@@ -377,18 +340,8 @@ int abacus_wst_check_memory(int n, int64_t np) {
     // the four padded meshes of the chain (the spectrum, the work mesh, u2 / U and the spectrum of U; the deposit's own work meshes
     // take the place of the last three before the chain starts), the table, the partial sums, and the packed copy and deposit lists
     // of the particles
-    auto bytes_of = [=](int m) { return 4 * zcv_padded_bytes(m) + (size_t)table_count(m) * 4 + (size_t)np * 24 + ((size_t)1 << 20); };
-    const size_t slack = (size_t)256 << 20;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes_of(n) + slack <= free_b) return 0;
-    ABACUS_TRY(scratch_trim_idle());
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes_of(n) + slack <= free_b) return 0;
-    int m = n;
-    while (m > WST_MIN_N && bytes_of(m) + slack > free_b) m -= 2;
-    return fail("%s: the meshes of %d^3 need %.1f GB of HBM, %.1f GB are free; the largest mesh that fits is %d^3", who, n,
-                1e-9 * (double)bytes_of(n), 1e-9 * (double)free_b, m);
+    auto bytes_of = [=](int m) { return 4 * padded_bytes(m) + (size_t)table_count(m) * 4 + (size_t)np * 24 + ((size_t)1 << 20); };
+    return check_memory(who, n, WST_MIN_N, bytes_of);
 }
 
 int abacus_wst_modulus_dev(const void *spec_padded, int n, double sigma_cells, int ell, void *work_padded, void *out_padded) {
@@ -399,7 +352,7 @@ int abacus_wst_modulus_dev(const void *spec_padded, int n, double sigma_cells, i
     if (!(sigma_cells > 0) || !std::isfinite(sigma_cells)) return fail("%s: sigma must be positive and finite, got %g", who, sigma_cells);
     if ((uintptr_t)spec_padded % 16 || (uintptr_t)work_padded % 16 || (uintptr_t)out_padded % 16)
         return fail("%s: the meshes are not aligned to 16 bytes", who);
-    const size_t bytes = (size_t)n * n * pitch_of(n) * sizeof(float);
+    const size_t bytes = (size_t)n * n * pitch_r(n) * sizeof(float);
     if (overlap(spec_padded, work_padded, bytes) || overlap(spec_padded, out_padded, bytes) || overlap(work_padded, out_padded, bytes))
         return fail("%s: the spectrum, the work mesh and the output are aliased; they must be three different meshes", who);
     ABACUS_ENTER();
@@ -447,8 +400,8 @@ int abacus_wst_coefficients_dev(void *spec_padded, int n, int J, int L, double s
     ABACUS_TRY(check_q(who, q_host, nq));
     if ((uintptr_t)spec_padded % 16) return fail("%s: the spectrum is not aligned to 16 bytes", who);
     ABACUS_ENTER();
-    const size_t bytes = zcv_padded_bytes(n);
-    const int pitch = pitch_of(n), nl = L + 1;
+    const size_t bytes = padded_bytes(n);
+    const int pitch = pitch_r(n), nl = L + 1;
     const QArgs qa = qargs(q_host, nq);
     const int n1 = J * nl, n2 = J * J * nl, nfield = 1 + n1 + n2;
     Scratch sc;
@@ -466,7 +419,7 @@ int abacus_wst_coefficients_dev(void *spec_padded, int n, int J, int L, double s
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(spec + 1), 0, 1, stream()));
     // S0: the field itself
     HIP_TRY(hipMemcpyAsync(work, spec, bytes, hipMemcpyDeviceToDevice, stream()));
-    ABACUS_TRY(zcv_smooth_c2r_inplace(work, n, 1.0, 0.0));
+    ABACUS_TRY(smooth_c2r_inplace(work, n, 1.0, 0.0));
     ABACUS_TRY(launch_moments(work, n, pitch, qa, partial, sums));
     for (int l = 0; l < nl; l++)
         for (int j1 = 0; j1 < J; j1++) {

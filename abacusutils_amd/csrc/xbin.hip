@@ -29,11 +29,6 @@
 
 using namespace abacus;
 
-namespace abacus {
-const float2 *fft_twiddles(int n);   // exp(-2 pi i m / n), m < n, device table (fft.hip)
-int fft_num_cus();
-}  // namespace abacus
-
 namespace {
 
 #include "fft_device.hpp"

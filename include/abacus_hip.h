@@ -1047,7 +1047,7 @@ int abacus_zcv_release(void);
 
 /* ---------------------------------------------------------------- linear control variates --------------- */
 /*
- * The linear half (LCV) of abacusnbody/hod/zcv, the one reconstructed catalogues use, on DEVICE pointers (csrc/zcv.hip, beside
+ * The linear half (LCV) of abacusnbody/hod/zcv, the one reconstructed catalogues use, on DEVICE pointers (csrc/lcv.hip, beside
  * the section above whose transform, deposit and binning it shares); every call enqueues on the library stream.  Spectra are
  * padded (n * n rows of abacus_slab_pitch(n) / 2 complex, abacus_zcv_spectrum_bytes bytes) and normalised as get_field_fft
  * normalises (divided by n^3), so abacus_zcv_power_pair bins any pair of them and abacus_zcv_spectrum_fetch copies one out.
@@ -1073,7 +1073,7 @@ int abacus_lcv_combine_k3d(const void *delta_padded, const void *deltamu2_padded
 
 /* ---------------------------------------------------------------- BAO reconstruction --------------------- */
 /*
- * Standard plane-parallel reconstruction of a periodic box (line of sight = z) on DEVICE pointers (csrc/zcv.hip, beside the LCV
+ * Standard plane-parallel reconstruction of a periodic box (line of sight = z) on DEVICE pointers (csrc/recon.hip, beside the LCV
  * section whose inputs it produces); every call enqueues on the library stream.  replaces: nothing in the reference - its
  * get_recon_power takes reconstructed tracers and shifted randoms that an external CPU code made between run_hod and get_recon_power;
  * this is that step.  Conventions of Chen et al. 2019 (RecSym, RecIso), the ones tools_cv.combine_kaiser_spectra assumes:
@@ -1112,7 +1112,7 @@ int abacus_recon_shift_dev(const float *pos, int64_t np, double offset, const fl
 
 /* ---------------------------------------------------------------- light-cone power spectrum --------------- */
 /*
- * FKP field and Yamamoto multipoles of a light-cone catalogue on DEVICE pointers (csrc/zcv.hip, behind the recon section; Python:
+ * FKP field and Yamamoto multipoles of a light-cone catalogue on DEVICE pointers (csrc/lc_power.hip, behind the recon section; Python:
  * analysis/lc_power.py); every call enqueues on the library stream.  replaces: nothing in the reference, whose power spectra assume a
  * periodic box and a global line of sight.  Estimator: Feldman, Kaiser & Peacock 1994 with the end-point line of sight of Yamamoto
  * et al. 2006, through the spherical-harmonic decomposition of Hand et al. 2017 (1 + 5 + 9 transforms for l = 0, 2, 4).
@@ -1153,7 +1153,7 @@ int abacus_lc_sum_w2n_dev(const float *w, const void *nbar, int nbar_f64, int64_
 
 /* ---------------------------------------------------------------- bispectrum ------------------------------ */
 /*
- * Bispectrum of a periodic box on DEVICE pointers (csrc/zcv.hip, behind the light-cone section; Python: analysis/bispectrum.py); every
+ * Bispectrum of a periodic box on DEVICE pointers (csrc/bispectrum.hip, behind the light-cone section; Python: analysis/bispectrum.py); every
  * call enqueues on the library stream.  replaces: nothing in the reference, which has no three-point statistic.  Estimator: the FFT
  * form of Scoccimarro 2015.  From a padded spectrum delta(k), normalised as get_field_fft normalises (abacus_zcv_spectrum_dev), and
  * nb shells with the edges kedges[0 .. nb]:

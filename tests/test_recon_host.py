@@ -179,7 +179,7 @@ def test_bad_arguments_raise_before_the_library_is_loaded(no_library):
 
 def test_header_declares_the_entry_points():
     text = (REPO / 'include' / 'abacus_hip.h').read_text()
-    src = (REPO / 'abacusutils_amd' / 'csrc' / 'zcv.hip').read_text()
+    src = (REPO / 'abacusutils_amd' / 'csrc' / 'recon.hip').read_text()
     names = ('abacus_recon_check_memory', 'abacus_recon_pack_soa64_dev', 'abacus_recon_wrap_dev', 'abacus_recon_pad_dev', 'abacus_recon_delta_dev',
              'abacus_recon_displacement_dev', 'abacus_recon_shift_dev')
     for name in names:

@@ -180,3 +180,5 @@ def test_header_declares_the_zcv_entry_points():
     src = (REPO / 'abacusutils_amd' / 'csrc' / 'zcv.hip').read_text()
     assert 'zcv.hip' in (REPO / 'abacusutils_amd' / 'csrc' / 'Makefile').read_text()
     assert 'atomicAdd' not in src                          # the means are two-stage reductions, not floating-point atomics
+    for part in ('lcv.hip', 'recon.hip', 'lc_power.hip', 'bispectrum.hip', 'mesh_common.hpp'):       # what came out of zcv.hip: the same rule
+        assert 'atomicAdd' not in (REPO / 'abacusutils_amd' / 'csrc' / part).read_text(), part
