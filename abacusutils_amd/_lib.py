@@ -91,6 +91,15 @@ def lib():
         L.abacus_void_fetch.argtypes = [C.c_void_p] * 4
         L.abacus_void_free.argtypes = [C.c_void_p]
         L.abacus_void_check_memory.argtypes = [C.c_int, C.c_int64]
+        for name in ('check_memory', 'create', 'run_dev', 'fetch_zones', 'fetch_tree', 'fetch_labels', 'free'):       # analysis/watershed.py
+            getattr(L, 'abacus_ws_' + name).restype = C.c_int
+        L.abacus_ws_check_memory.argtypes = [C.c_int, C.c_int64]
+        L.abacus_ws_create.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.abacus_ws_run_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.abacus_ws_fetch_zones.argtypes = [C.c_void_p] * 6
+        L.abacus_ws_fetch_tree.argtypes = [C.c_void_p] * 6
+        L.abacus_ws_fetch_labels.argtypes = [C.c_void_p] * 2
+        L.abacus_ws_free.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 

@@ -7,3 +7,5 @@ from .mst import minimum_spanning_tree, mst_branches, mst_statistics  # noqa: F4
 from .spheres import count_in_spheres, knn_cdf, random_centres, vpf  # noqa: F401
 from .threepcf import calc_3pcf, triplet_multipoles, zeta_from_counts  # noqa: F401
 from .voids import find_voids, find_voids_mesh, tophat_smooth, void_galaxy_xi, void_size_function  # noqa: F401
+from .watershed import (find_watershed_voids, merge_zones, persistence_pairs, watershed_mesh, watershed_size_function, zone_galaxy_xi,  # noqa: F401
+                        zone_hierarchy)

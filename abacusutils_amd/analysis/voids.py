@@ -22,7 +22,7 @@ Limits: n even, 4 .. 1024; 1 .. 32 radii, positive, finite, strictly decreasing,
 host mesh must be free of NaN (checked); a device mesh is not checked.
 
 Not built: partial overlap fractions (a void is kept or dropped whole), profiles stacked in r / R_v, light cones or masks, float64
-meshes, multi-GPU slabs, voids across tracers, watershed finders.  There is no CPU fallback.
+meshes, multi-GPU slabs, voids across tracers.  Watershed voids: analysis/watershed.py.  There is no CPU fallback.
 """
 import ctypes as C
 import math

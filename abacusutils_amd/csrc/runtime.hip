@@ -219,7 +219,7 @@ extern "C" {
 int abacus_set_option(const char *name, int value) {
     if (!name) return abacus::fail("abacus_set_option: null name");
     static const char *known[] = {"dbg", "dbg_fft", "dbg_tsc", "fft_fuse_small", "fft_hipfft", "fft_inplace", "gfft_dbg", "gfft_nofixed", "fft_nofuse", "hod_eblock", "hod_f64filter",
-                                  "hod_deal", "hod_sbindex", "hod_keepmasks", "hod_nobalance", "hod_nocls", "hod_noindex", "hod_nokeys", "hod_nolazy", "hod_norec", "hod_one_stage", "hod_pipe", "hod_sbtiles", "lens_shared_rows", "mst_always_atomic", "mst_round_names", "pairs_countsort", "pairs_gen", "pairs_noblocks", "pairs_jk_grid", "pairs_nolut", "pairvel_lds_top", "pk_nobatch", "pk_noxbin", "pk_noxbin_cross", "pk_noxbin_inter", "pk_xbin_gen", "pk_xbin_pairs", "prep_columnwise", "slab_nocompact", "slab_nofuse", "slab_nopackfuse", "slab_nounpackfuse", "tsc_acc64", "tsc_atomic", "tsc_lines_cfg1", "tsc_lines_clk", "tsc_lines_sync", "tsc_noshare", "tsc_noslabfast", "tsc_oldlists"};
+                                  "hod_deal", "hod_sbindex", "hod_keepmasks", "hod_nobalance", "hod_nocls", "hod_noindex", "hod_nokeys", "hod_nolazy", "hod_norec", "hod_one_stage", "hod_pipe", "hod_sbtiles", "lens_shared_rows", "mst_always_atomic", "ws_reduce_per_cell", "mst_round_names", "pairs_countsort", "pairs_gen", "pairs_noblocks", "pairs_jk_grid", "pairs_nolut", "pairvel_lds_top", "pk_nobatch", "pk_noxbin", "pk_noxbin_cross", "pk_noxbin_inter", "pk_xbin_gen", "pk_xbin_pairs", "prep_columnwise", "slab_nocompact", "slab_nofuse", "slab_nopackfuse", "slab_nounpackfuse", "tsc_acc64", "tsc_atomic", "tsc_lines_cfg1", "tsc_lines_clk", "tsc_lines_sync", "tsc_noshare", "tsc_noslabfast", "tsc_oldlists"};
     bool ok = false;
     for (const char *k : known) ok = ok || !strcmp(k, name);
     if (!ok) return abacus::fail("abacus_set_option: unknown option '%s'", name);

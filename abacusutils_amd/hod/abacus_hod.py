@@ -816,6 +816,22 @@ class AbacusHOD:
                                  compensated=compensated, interlaced=interlaced, return_fields=return_fields)
         return out
 
+    def compute_watershed_voids(self, mock_dict, R, num_cells=256, paste='TSC', compensated=True, interlaced=True, connectivity=26,
+                                min_radius=0.0, saddle_max=None, return_field=False, return_labels=False):
+        """The watershed voids of every tracer's density contrast in the periodic box, smoothed with a Gaussian of radius `R` (no
+        reference counterpart; `analysis.watershed.find_watershed_voids`): {tracer: its result dict} - the zones, their saddle
+        tree and the ZOBOV hierarchy; with `saddle_max` the zones merged below that saddle.  The columns are taken from HBM when
+        `mock_dict` is the untouched result of the latest run_hod; a 'w' column weights its tracer.  No zones across tracers."""
+        from ..analysis.watershed import find_watershed_voids
+        out = {}
+        for tr in mock_dict.keys():
+            cols = self._xyz(mock_dict, tr)
+            pos = list(cols) if not isinstance(cols[0], np.ndarray) else np.stack([np.asarray(c) for c in cols], axis=1)
+            out[tr] = find_watershed_voids(pos, self.lbox, R, nmesh=num_cells, w=mock_dict[tr].get('w', None), paste=paste,
+                                           compensated=compensated, interlaced=interlaced, connectivity=connectivity, min_radius=min_radius,
+                                           saddle_max=saddle_max, return_field=return_field, return_labels=return_labels)
+        return out
+
     def compute_3pcf(self, mock_dict, rbins, lmax, randoms=None, seed=42):
         """The three-point correlation function multipoles zeta_l(r1, r2) of every tracer in the periodic box (no reference
         counterpart; `analysis.threepcf.calc_3pcf`): {tracer: its result dict}.  `rbins`: the edges of at most 32 radial bins, the

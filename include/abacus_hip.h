@@ -1275,6 +1275,55 @@ int abacus_void_fetch(abacus_void *handle, int32_t *cells, int32_t *levels, floa
 /* releases the handle and its device buffers (NULL: nothing to do); a freed handle is refused */
 int abacus_void_free(abacus_void *handle);
 
+/* ---------------------------------------------------------------- Watershed voids -------------------------- */
+/*
+ * Watershed zones and the saddle tree of a periodic mesh on a DEVICE pointer (csrc/watershed.hip; Python: analysis/watershed.py);
+ * every call enqueues on the library stream.  replaces: nothing in the reference, which has no void finder.  Algorithm: the zones of
+ * ZOBOV (Neyrinck 2008) / VIDE on a mesh, as the voxel finder of REVOLVER takes them, stated so that every decision is an integer
+ * comparison (tests/watershed_statement.py is the NumPy statement).
+ *   Mesh: n^3 float32 cells, n even, 4 .. 1024, flat index f = (x n + y) n + z < 2^30.  The key of a cell is (value, f), by value
+ *   first, compared in float32 with -0.0 and +0.0 one value: a strict total order.  On the device one 64-bit word: the
+ *   order-preserving bit pattern of the value in the high half, f in the low half.
+ *   Descent: connectivity 6 (faces) or 26 (faces, edges, corners); down[c] = the cell of smallest key among c and its periodic
+ *   neighbours; a cell with down[c] == c is a core.
+ *   Zones: the zone of c is the core reached by following down; zones are numbered 0 .. Z - 1 in ascending flat index of their core.
+ *   Per zone: ncell; core (x, y, z); delta_min, the keyed value of the core (-0.0 comes back as +0.0); offset_sum, per axis the sum
+ *   over its cells of (c - core) mod n, minus n where that is >= n / 2 - exact integers; delta_sum, the float64 sum of its cells'
+ *   values in no fixed order, the only inexact output (|error| <= ncell 2^-53 sum |x|).
+ *   Saddle tree: an edge is a pair of adjacent cells (the same connectivity) in different zones; hi is the cell of the larger key,
+ *   lo the other; its weight is (key(hi), key(lo)), compared lexicographically - unique per cell pair, a strict total order.  The
+ *   tree is the minimum spanning tree of the zone graph under these weights: Z - 1 edges (the torus is connected), unique, output in
+ *   ascending weight - the order in which rising water joins basins.
+ * The mesh: n * n rows of `pitch` floats, aligned to 4 bytes, not modified; pitch == n is a dense mesh, pitch ==
+ * abacus_slab_pitch(n) the real side of a padded spectrum; the floats of a row beyond its n cells are never read.  The mesh must be
+ * finite; that is not checked on the device.  Limits, checked before the device is touched, every message starting with the
+ * entry's name: n even, 4 .. 1024; connectivity 6 or 26; pitch >= n; no null argument; a freed handle is refused, not followed.
+ */
+typedef struct abacus_ws abacus_ws;
+/* fails, naming the largest mesh that fits, when the spectrum and the work area of one deposit and transform (three padded meshes),
+ * the copies and deposit lists of np particles and the finder's worst case (16 bytes per cell and 96 bytes per zone, a zone every
+ * second cell: 64 bytes per cell) do not fit the free device memory */
+int abacus_ws_check_memory(int n, int64_t np);
+/* a finder for a mesh of n^3 cells.  Touches no device memory. */
+int abacus_ws_create(int n, int connectivity, abacus_ws **handle);
+/* the whole finder on one mesh; the results stay in the handle until the next run or abacus_ws_free.  ws_descend (one pass: 4 bytes
+ * read and 4 written per cell, the stencil from the caches), ws_jump (pointer jumping in place, a launch per pass until one changes
+ * nothing, at most 40), ws_mark + the prefix scan of scan.hip + ws_number (zone numbers), ws_reduce (the sums: runs of one zone
+ * inside a wave are combined before the atomics), then Boruvka's rounds over the zones: ws_edges twice (a 64-bit atomicMin of
+ * key(hi) per component, then of key(lo) among the pairs that matched; every cell looks at the forward half of its neighbours, so
+ * every pair is seen once), ws_hook, ws_flatten; the edge count is read back per round; at most 32 rounds, beyond that the call
+ * fails.  No thread waits for another.  The Z - 1 edges are sorted on the host.  HOST out: *nzones = Z; *rounds (may be NULL): the
+ * rounds of the tree; *jumps (may be NULL): the passes of ws_jump - neither is part of the result. */
+int abacus_ws_run_dev(abacus_ws *handle, const float *mesh, int pitch, int64_t *nzones, int *rounds, int *jumps);
+/* HOST arrays of the last run: ncell[Z], core[Z][3], delta_min[Z], offset_sum[Z][3], delta_sum[Z] */
+int abacus_ws_fetch_zones(abacus_ws *handle, int64_t *ncell, int32_t *core, float *delta_min, int64_t *offset_sum, double *delta_sum);
+/* HOST arrays of Z - 1 entries in ascending weight: the flat indices of hi and lo, their zones, saddle = the value at hi (as keyed) */
+int abacus_ws_fetch_tree(abacus_ws *handle, int64_t *hi_cell, int64_t *lo_cell, int32_t *zone_hi, int32_t *zone_lo, float *saddle);
+/* labels[n][n][n] (HOST, dense): the zone number of every cell */
+int abacus_ws_fetch_labels(abacus_ws *handle, int32_t *labels);
+/* releases the handle and its device buffers (NULL: nothing to do); a freed handle is refused */
+int abacus_ws_free(abacus_ws *handle);
+
 /* ---------------------------------------------------------------- Wavelet scattering transform ------------- */
 /*
  * Solid-harmonic wavelet scattering coefficients S0, S1, S2 of a periodic mesh on DEVICE pointers (csrc/wst.hip; Python:
